@@ -1,7 +1,14 @@
 """bench.py -- plan-steps/sec of TDMPC.plan on MI355X (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config humanoid-run] [--envs-per-gpu B]
+                    [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up and exactly K timed steps, writes the last timed step's outputs when
+--dump-outputs is given (DIR/actions.npy [envs, A] and DIR/metrics.npy [envs, 2] = reward mean, std; float32, as
+EnvShardedPlanner.plan returned them; seeded weights, observations and device generator, so two builds can be
+compared output for output) and prints the headline line. Every other leg described below (roofline, cpu_baseline,
+batch_sweep, single_env, exact_f32_mfma, configs, replay_sampler, learner, train_loop, icem) runs only with --full.
 
 Workload (BASELINE.json configs[2], the north-star target): humanoid-run, N=512 candidates, H=5, 6 CEM
 iterations, mixture 0.5 (P=256 pi trajectories, T=768 rows), K=64 elites, latent 100 (cfgs/tasks/humanoid.yaml:6),
@@ -11,14 +18,14 @@ single-env calls, tests/test_gpu_plan.py::test_batched_equals_single). The defau
 smallest vectorised batch that fills the chip: its rollout launches are 1024 chain workgroups (4 per CU, two
 co-resident), where B = 8 (BASELINE.json configs[3]'s "8 per GPU") is exactly one per CU and leaves latency
 exposed (plan FP32 fraction 0.56 at B = 8, 0.76 at B = 32, 0.78 at B = 64). B = 8 and the
-single-env drop-in path (B = 1, one plan() per call, latency-bound) are timed in the same run and reported
-under "batch_sweep" and "single_env".
+single-env drop-in path (B = 1, one plan() per call, latency-bound) are timed in the same run with --full and
+reported under "batch_sweep" and "single_env".
 
 Multi-GPU: environments are independent units, so every rank plans its own B envs on its own
 weight replica (weak scaling) and each step ends with one RCCL all-gather over xGMI of the per-env results
 ([B, A+2]: action, reward mean, std) so that every rank holds the whole vectorised batch.
 
-Rank 0 prints ONE JSON line with, besides the driver's contract fields,
+Rank 0 prints ONE JSON line; with --full it holds, besides the headline fields,
   roofline     : the dominant kernel -- the CEM rollout step (TOLD.next over the B*N candidate rows, 5 launches
                  per iteration): algorithmic FLOPs per launch / average launch time, HIP events around every
                  launch on its stream over an eager replay of the same steps; traffic from
@@ -871,7 +878,18 @@ def main():
     ap.add_argument("--no-learner", action="store_true")
     ap.add_argument("--no-icem", action="store_true")
     ap.add_argument("--no-exact", action="store_true", help="skip the exact-f32-MFMA comparison run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (actions, metrics of every env) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: roofline, CPU baselines, the exact f32 run, the "
+                         "single env, the batch sweep, the other configs, replay, learner, train loop and iCEM "
+                         "(each still switched off by its --no-* option)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the outputs, the headline line -- nothing else
+        args.no_cpu = args.no_roofline = args.no_single = args.no_replay = True
+        args.no_learner = args.no_icem = args.no_exact = True
+        args.sweep = args.also = ""
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -895,12 +913,21 @@ def main():
     obs = sharded.local_obs(global_obs)
     step = 10**6
 
+    last = [None]
+
     def one_step(i):
-        return sharded.plan(global_obs, step, t0=(i % 100 == 0))
+        last[0] = sharded.plan(global_obs, step, t0=(i % 100 == 0))
+        return last[0]
 
     elapsed = time_steps(one_step, args.warmup, args.steps, dist)
     elapsed, value = job_rate(elapsed, B * args.steps, dist, dev)
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0 and last[0] is not None:
+        # what the last timed step returned (views of the planner's result block: copied out before any other leg
+        # plans again), every env of the global batch: [envs, A] actions, [envs, 2] reward mean and std
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in zip(("actions", "metrics"), last[0]):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
 
     # ---- roofline of the dominant kernel class: HIP events around each launch, eager replay of the same
     # steps on the same stream (graph replays cannot carry the events)

@@ -4,7 +4,7 @@
 # Stages (results under gpurun_out/OUT/):
 #   tests            the whole `pytest -m gpu` suite
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (bench.json)
+#   bench            the bench line with every leg (bench.py --full; bench.json)
 #   prof             rocprofv3 kernel trace of a short bench run, summarised by kernel and grid (prof_summary.txt)
 #   pmc              PMC passes of the dominant kernel (FETCH_SIZE, WRITE_SIZE, MFMA busy), merged into
 #                    profiles/pmc_traffic.json / pmc_mfma.json copies under OUT
@@ -43,10 +43,10 @@ for stage in "$@"; do
         || { tail -20 "$OUT/smoke.log"; exit 1; }
       tail -1 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+      timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
       python3 -c "import json; d=json.load(open('$OUT/bench.json')); print('bench', d['value'], d['roofline']['frac'], d['roofline']['avg_launch_us'])" ;;
     prof)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -- python3 bench.py --steps 10 --warmup 3 \
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -- python3 bench.py --full --steps 10 --warmup 3 \
         --no-cpu --no-single --no-replay --no-learner --no-icem --no-exact --also= > "$OUT/prof.log" 2>&1 \
         || { tail -20 "$OUT/prof.log"; exit 1; }
       python3 tools/rocpd_summary.py "$OUT/prof/run_results.db" 16 --grid > "$OUT/prof_summary.txt" 2>&1
