@@ -6,6 +6,7 @@ The drop-in names:
     from tdmpc_amd import TOLD             # src/algorithm/tdmpc.py:9 (same module tree and state_dict keys)
     from tdmpc_amd import ReplayBuffer     # src/algorithm/helper.py:434 (device prioritized replay)
     from tdmpc_amd import TdICEM           # src/algorithm/tdmpc_icem_similarity_mlp.py:116 (iCEM planner)
+    from tdmpc_amd import TdMpcDrnn        # src/algorithm/tdmpc_similarity_drnn.py:87 (GRU-dynamics DSSM planner)
     from tdmpc_amd import EnvShardedPlanner  # vectorised envs over the GPUs of one node
 
 Imports are resolved lazily, so `import tdmpc_amd` does not load torch or the HIP library.
@@ -21,6 +22,8 @@ _EXPORTS = {
     "TOLD": "told",
     "ReplayBuffer": "replay",
     "TdICEM": "icem",
+    "TdMpcDrnn": "drnn",
+    "DSSM": "dssm",
     "EnvShardedPlanner": "parallel",
     "shard_bounds": "parallel",
     "make_cfg": "config",

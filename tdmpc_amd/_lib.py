@@ -26,7 +26,12 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_loss_forward", "tdmpc_loss_backward", "tdmpc_random_shift", "tdmpc_random_shift_scaled",
             "tdmpc_lg_gemm", "tdmpc_lg_rows_fwd", "tdmpc_lg_rows_bwd", "tdmpc_lg_pi_loss", "tdmpc_lg_finalize",
             "tdmpc_lg_adam", "tdmpc_lg_lerp", "tdmpc_lg_act", "tdmpc_lg_conv_fwd", "tdmpc_lg_conv_bwd_data",
-            "tdmpc_lg_conv_bwd_weight")
+            "tdmpc_lg_conv_bwd_weight",
+            # include/tdmpc_drnn.h
+            "tdmpc_drnn_version", "tdmpc_drnn_sizes_for", "tdmpc_drnn_num_param_tensors", "tdmpc_drnn_pack_weights",
+            "tdmpc_drnn_next", "tdmpc_drnn_estimate_value", "tdmpc_drnn_pi_rollout", "tdmpc_drnn_plan",
+            "tdmpc_drnn_profile_begin", "tdmpc_drnn_profile_end")
+DRNN_VERSION = 1
 
 
 # tdmpc_plan_params.status bits (include/tdmpc_hip.h)
@@ -54,6 +59,10 @@ class Dims(C.Structure):
         "modality", "obs_dim", "img_c", "img_hw", "num_channels", "action_dim", "latent_dim", "mlp_dim",
         "enc_dim", "num_samples", "num_pi", "num_elites", "max_horizon", "max_iterations", "max_batch",
         "enc_norm")]
+
+
+class DrnnDims(C.Structure):   # tdmpc_drnn_dims (include/tdmpc_drnn.h)
+    _fields_ = [("base", Dims), ("hidden_dim", C.c_int32)]
 
 
 class PlanParams(C.Structure):
@@ -193,6 +202,16 @@ def lib():
     L.tdmpc_lg_conv_fwd.argtypes = [C.POINTER(LgConv), vp]
     L.tdmpc_lg_conv_bwd_data.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.tdmpc_lg_conv_bwd_weight.argtypes = [vp, vp, C.c_float, vp, i32, i32, i32, i32, i32, vp]
+    dd, pp = C.POINTER(DrnnDims), C.POINTER(PlanParams)
+    L.tdmpc_drnn_sizes_for.argtypes = [dd, C.POINTER(Sizes)]
+    L.tdmpc_drnn_num_param_tensors.argtypes = [dd]
+    L.tdmpc_drnn_pack_weights.argtypes = [dd, C.POINTER(vp), i32, vp, sz, vp]
+    L.tdmpc_drnn_next.argtypes = [dd, vp, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]
+    L.tdmpc_drnn_estimate_value.argtypes = [dd, pp, vp, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]
+    L.tdmpc_drnn_pi_rollout.argtypes = [dd, pp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.tdmpc_drnn_plan.argtypes = [dd, pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.tdmpc_drnn_profile_begin.argtypes = [i32, i32]
+    L.tdmpc_drnn_profile_end.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     for name in EXPORTED:
         if not hasattr(L, name) and not (name.startswith("tdmpc_debug_") and os.environ.get("TDMPC_LIB_PATH")):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")
@@ -227,6 +246,17 @@ def dims_from_cfg(cfg, max_batch: int = 1, max_horizon=None, max_iterations=None
     d.max_iterations = int(max_iterations or cfg.iterations)
     d.max_batch = int(max_batch)
     d.enc_norm = int(bool(enc_norm))
+    return d
+
+
+def drnn_dims_from_cfg(cfg, max_batch: int = 1, num_pi=None) -> DrnnDims:
+    """tdmpc_drnn_dims of a DSSM cfg (state observations, the LayerNorm encoder); num_pi: the call's
+    int(mixture_coef * num_samples), default cfg.mixture_coef's."""
+    d = DrnnDims()
+    C.memmove(C.byref(d.base), C.byref(dims_from_cfg(cfg, max_batch=max_batch, enc_norm=True)), C.sizeof(Dims))
+    if num_pi is not None:
+        d.base.num_pi = int(num_pi)
+    d.hidden_dim = int(cfg.hidden_dim)
     return d
 
 

@@ -52,6 +52,10 @@ DEFAULTS = dict(
     keep_previous_elites=True,   # :23
     noise_beta=2.5,              # :24
     regularization_schedule="linear(0.05, 0.5, 1, 5000)",  # :47 (mixture_coef substituted)
+    hidden_dim=128,              # :75 (DSSM: the GRU cell's width)
+    norm_cell=True,              # :76 (DSSM: NormGRUCell, not nn.GRUCell)
+    warmup_len=0,                # :30 (DSSM: length of the replayed latent memory)
+    plan2expl=False,             # :108
     normalize=True,              # :97 (DSSM encoder: helper.dmlab_enc_norm; TOLD ignores it)
     norm_type="ln",              # :98
     # pixels.yaml

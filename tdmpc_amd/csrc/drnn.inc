@@ -1,0 +1,714 @@
+// drnn.inc -- the recurrent-latent (DSSM) rollout step for gfx950 and its C ABI (include/tdmpc_drnn.h).
+// Included twice from tdmpc_kernels.hip: once beside plan1.inc / wide_step.inc for the device code (it shares the x6
+// helpers and the row-block idiom of chain_kernel), once at the end of the file (DRNN_HOST) for the host side, which
+// shares Ctx, the pack table and the profiler.
+//
+// Reference: DSSM.next (src/algorithm/tdmpc_similarity_drnn.py:57-60) = DGruDyna (models/gru_dyna.py:25-29: a
+// NormGRUCell over [z, a], then prior_mlp = Linear - BatchNorm1d - ELU - Linear on the new hidden) and the reward MLP
+// on the new hidden; NormGRUCell.forward is models/rnns.py:19-29.
+//
+// drnn_step_kernel: one launch per rollout step. A workgroup of 8 waves owns 32 rows and keeps their activations in
+// LDS from layer to layer (fp32 [K/4][32][4] blocks, the x6 B operand of ring6_run); products are the x6 form
+// (fp32 = three bf16 planes, six v_mfma_f32_32x32x16_bf16 per 16 k). Per block:
+//   1. stage [a | z] (the X_t panel) and h; BatchNorm's running statistics become a per-column scale / shift
+//   2. gates: wave b < Hd / 32 owns hidden features [32 b, 32 b + 32) of all three gates: W_ih [a | z] and W_hh h
+//      accumulate into the same tiles for reset / update; the new-value gate keeps its two parts apart
+//   3. the three row LayerNorms (eps 1e-3, two passes, per-row moments through LDS), sigmoid / tanh, blend -> h'
+//   4. prior: ELU(BN(W_p0 h' + b)) -> LDS, then W_p3 . + b split over k slices -> z' (X_{t+1}'s latent columns)
+//   5. reward: ELU(W_r0 h' + b) -> LDS, ELU(W_r2 . + b) . w_r4 + b -> r; G (+)= gamma^t r
+// Rows never share a statistic: every reduction is over one row's features, so a non-finite row stays alone.
+#ifndef DRNN_HOST
+
+struct DrnnArgs {
+    int rows, Hd, Kx, L, Lp, nb3;        // logical rows; GRU width; X panel width; latent dims; Lr / 32
+    RowMap amap;                         // logical row -> X row
+    const float* X; float* Xo; long x_ts; int out_q0;   // X_t in; X_{t+1} out: latent quads from out_q0
+    const float* hin; int h_G;           // h_G > 0: row m starts from hin[m / h_G] (its env's hidden), else hin[X row]
+    float* hout;                         // [X row][Hd]
+    const unsigned short* Xih; const unsigned short* Xhh;     // x6 [3 Hd][Kx], [3 Hd][Hd]
+    const unsigned short* Xp0r0;         // x6 [2 M][Hd]: prior_mlp.0 rows, then _reward.0 rows
+    const unsigned short* Xp3;           // x6 [Lr][M]
+    const unsigned short* Xr2;           // x6 [M][M]
+    const float* ln;                     // [6][Hd]: reset gain, shift; update gain, shift; newval gain, shift
+    const float* b_p0; const float* bn_w; const float* bn_b; const float* bn_m; const float* bn_v;   // [M]
+    const float* b_p3;                   // [Lr]
+    const float* b_r0; const float* b_r2; const float* w_r4; const float* b_r4;
+    float* G; float* rlast; float disc; int first, last;   // G null: no return; rlast written when last
+};
+
+constexpr int DRNN_M = 512, DRNN_NW = 8;
+// LDS floats: activation block | h block | prior last-layer partial tiles | row reductions | parameter vectors
+__host__ __device__ inline int drnn_lds_floats(int Hd, int Lr) {
+    return DRNN_M * 32 + Hd * 32 + 8 * 1024 + 4 * DRNN_NW * 32 + 6 * Hd + 6 * DRNN_M + Lr;
+}
+// k slices of the prior's last layer (Lr / 32 column blocks x slices <= 8 waves)
+__host__ __device__ inline int drnn_ks(int nb3) { return nb3 >= 5 ? 1 : nb3 >= 3 ? 2 : nb3 == 2 ? 4 : 8; }
+
+DEVI float drnn_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// Per-row mean and 1 / sqrt(var + 1e-3) over the Hd features of two gate tiles at once (biased variance, two
+// passes): each active wave holds 32 features of every row, lanes (r, h) 16 of them.
+DEVI void drnn_moments2(const floatx16& a, const floatx16& b, bool active, float* red, int wave, int r, int h, int nb,
+                        float inv_n, float& ma, float& ra, float& mb, float& rb) {
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { sa += a[i]; sb += b[i]; }
+    sa += __shfl_xor(sa, 32);
+    sb += __shfl_xor(sb, 32);
+    if (active && h == 0) { red[wave * 32 + r] = sa; red[(DRNN_NW + wave) * 32 + r] = sb; }
+    lds_barrier();
+    float ta = 0.f, tb = 0.f;
+    for (int w = 0; w < nb; ++w) { ta += red[w * 32 + r]; tb += red[(DRNN_NW + w) * 32 + r]; }
+    ma = ta * inv_n; mb = tb * inv_n;
+    float qa = 0.f, qb = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float da = a[i] - ma, db = b[i] - mb;
+        qa += da * da; qb += db * db;
+    }
+    qa += __shfl_xor(qa, 32);
+    qb += __shfl_xor(qb, 32);
+    if (active && h == 0) { red[(2 * DRNN_NW + wave) * 32 + r] = qa; red[(3 * DRNN_NW + wave) * 32 + r] = qb; }
+    lds_barrier();
+    float va = 0.f, vb = 0.f;
+    for (int w = 0; w < nb; ++w) { va += red[(2 * DRNN_NW + w) * 32 + r]; vb += red[(3 * DRNN_NW + w) * 32 + r]; }
+    ra = 1.0f / sqrtf(fmaxf(va * inv_n, 0.f) + 1e-3f);
+    rb = 1.0f / sqrtf(fmaxf(vb * inv_n, 0.f) + 1e-3f);
+}
+
+__global__ void __launch_bounds__(64 * DRNN_NW) drnn_step_kernel(const DrnnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    constexpr int M = DRNN_M, NTH = 64 * DRNN_NW;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int Hd = a.Hd, nb = Hd / 32, Lr = a.nb3 * 32;
+    const int m0 = blockIdx.x * 32;
+    float* sX = sm;                       // [max(Kx16, M) / 4][32][4]
+    float* sH = sX + M * 32;              // [Hd / 4][32][4]
+    float* sR = sH + Hd * 32;             // [8][32 features][32 rows]
+    float* red = sR + 8 * 1024;           // [4][NW][32]
+    float* sln = red + 4 * DRNN_NW * 32;  // [6][Hd]
+    float* sbp0 = sln + 6 * Hd;           // [M] each: prior.0 bias, BN scale, BN shift, reward.0 bias, reward.2 bias,
+    float* sal = sbp0 + M;                //           reward.4 weight
+    float* sbe = sal + M;
+    float* sbr0 = sbe + M;
+    float* sbr2 = sbr0 + M;
+    float* swr4 = sbr2 + M;
+    float* sbp3 = swr4 + M;               // [Lr]
+    const int kq1 = (a.Kx + 15) / 16 * 4; // quads of the staged input (k padded to 16 with zeros)
+
+    // ---- 1. stage
+    for (int i = tid; i < kq1 * 32; i += NTH) {
+        const int q = i >> 5, rr = i & 31, m = m0 + rr;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (m < a.rows && q * 4 < a.Kx) {
+            const int x = map_row(a.amap, m);
+            v = *(const float4*)(a.X + (size_t)(x >> 5) * a.x_ts + (size_t)q * 128 + (x & 31) * 4);
+        }
+        *(float4*)(sX + (q * 32 + rr) * 4) = v;
+    }
+    for (int i = tid; i < (Hd / 4) * 32; i += NTH) {
+        const int q = i >> 5, rr = i & 31, m = m0 + rr;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (m < a.rows) {
+            const size_t hr = a.h_G > 0 ? (size_t)(m / a.h_G) : (size_t)map_row(a.amap, m);
+            v = *(const float4*)(a.hin + hr * Hd + q * 4);
+        }
+        *(float4*)(sH + (q * 32 + rr) * 4) = v;
+    }
+    for (int i = tid; i < 6 * Hd; i += NTH) sln[i] = a.ln[i];
+    for (int i = tid; i < M; i += NTH) {
+        // eval-mode BatchNorm1d as ATen's CPU kernel forms it: alpha = weight / sqrt(var + eps), beta = bias - mean alpha
+        const float al = fmul(a.bn_w[i], 1.0f / sqrtf(a.bn_v[i] + 1e-5f));
+        sbp0[i] = a.b_p0[i]; sal[i] = al; sbe[i] = fadd(a.bn_b[i], -fmul(a.bn_m[i], al));
+        sbr0[i] = a.b_r0[i]; sbr2[i] = a.b_r2[i]; swr4[i] = a.w_r4[i];
+    }
+    for (int i = tid; i < Lr; i += NTH) sbp3[i] = a.b_p3[i];
+    lds_barrier();
+
+    // ---- 2. gates (waves b < nb)
+    const bool gate = wave < nb;
+    floatx16 g3[3], gni;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) g3[j][i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gni[i] = 0.f;
+    if (gate) {
+        uint4 wr[2][3][3];
+        const int kg1 = kq1 / 4, kg2 = Hd / 16;
+        const unsigned short* Wi = a.Xih + (size_t)wave * kg1 * 1536 + lane * 8;
+        const long wbi = (long)nb * kg1 * 1536;
+        ring6_fill<3, 2>(wr, Wi, wbi, 0, kg1);
+        ring6_run<3, 2>(g3, wr, sX, Wi, wbi, 0, kg1, r, h);
+        gni = g3[2];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) g3[2][i] = 0.f;
+        const unsigned short* Wh = a.Xhh + (size_t)wave * kg2 * 1536 + lane * 8;
+        const long wbh = (long)nb * kg2 * 1536;
+        ring6_fill<3, 2>(wr, Wh, wbh, 0, kg2);
+        ring6_run<3, 2>(g3, wr, sH, Wh, wbh, 0, kg2, r, h);
+    }
+
+    // ---- 3. LayerNorms, gate non-linearities, blend
+    const float inv_n = 1.0f / (float)Hd;
+    float mr, rr_, mu, ru;
+    drnn_moments2(g3[0], g3[1], gate, red, wave, r, h, nb, inv_n, mr, rr_, mu, ru);
+    floatx16 upd, npre;
+    if (gate) {
+        const float shr = -rr_ * mr, shu = -ru * mu;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int f = wave * 32 + 8 * (i >> 2) + 4 * h + (i & 3);
+            const float rs = drnn_sigmoid(fadd(fmul(fadd(fmul(g3[0][i], rr_), shr), sln[f]), sln[Hd + f]));
+            upd[i] = drnn_sigmoid(fadd(fmul(fadd(fmul(g3[1][i], ru), shu), sln[2 * Hd + f]), sln[3 * Hd + f]));
+            npre[i] = fadd(gni[i], fmul(rs, g3[2][i]));
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { upd[i] = 0.f; npre[i] = 0.f; }
+    }
+    float mn, rn, m_unused, r_unused;
+    drnn_moments2(npre, npre, gate, red, wave, r, h, nb, inv_n, mn, rn, m_unused, r_unused);
+    if (gate) {
+        const float shn = -rn * mn;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int cq = wave * 8 + 2 * q + h;
+            float* hp = sH + (cq * 32 + r) * 4;
+            const float4 ho = *(const float4*)hp;
+            const float hv[4] = {ho.x, ho.y, ho.z, ho.w};
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = 4 * q + j, f = cq * 4 + j;
+                const float nv = tanhf(fadd(fmul(fadd(fmul(npre[i], rn), shn), sln[4 * Hd + f]), sln[5 * Hd + f]));
+                o[j] = fadd(fmul(upd[i], nv), fmul(fadd(1.0f, -upd[i]), hv[j]));
+            }
+            *(float4*)hp = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+    lds_barrier();
+    for (int i = tid; i < (Hd / 4) * 32; i += NTH) {
+        const int q = i >> 5, rr = i & 31, m = m0 + rr;
+        if (m < a.rows)
+            *(float4*)(a.hout + (size_t)map_row(a.amap, m) * Hd + q * 4) = *(const float4*)(sH + (q * 32 + rr) * 4);
+    }
+
+    // ---- 4. prior MLP
+    const int kgh = Hd / 16, cw0 = wave * 2;
+    {
+        floatx16 acc[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+        uint4 wr[2][2][3];
+        const unsigned short* Wp = a.Xp0r0 + (size_t)cw0 * kgh * 1536 + lane * 8;
+        const long wbs = (long)kgh * 1536;
+        ring6_fill<2, 2>(wr, Wp, wbs, 0, kgh);
+        ring6_run<2, 2>(acc, wr, sH, Wp, wbs, 0, kgh, r, h);
+        // (every wave is past the gates' reads of sX: the barriers above)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = (cw0 + j) * 32 + 8 * q + 4 * h;
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    o[e] = elu_f(fadd(fmul(fadd(acc[j][4 * q + e], sbp0[c + e]), sal[c + e]), sbe[c + e]));
+                *(float4*)(sX + (((cw0 + j) * 8 + 2 * q + h) * 32 + r) * 4) = make_float4(o[0], o[1], o[2], o[3]);
+            }
+    }
+    lds_barrier();
+    {
+        const int ks = drnn_ks(a.nb3), units = a.nb3 * ks;
+        if (wave < units) {
+            const int b3 = wave % a.nb3, s = wave / a.nb3, gs = (M / 16) / ks;
+            floatx16 acc[1];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
+            uint4 wr[2][1][3];
+            const unsigned short* Wp = a.Xp3 + (size_t)b3 * (M / 16) * 1536 + lane * 8;
+            ring6_fill<1, 2>(wr, Wp, 0, s * gs, (s + 1) * gs);
+            ring6_run<1, 2>(acc, wr, sX, Wp, 0, s * gs, (s + 1) * gs, r, h);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sR[wave * 1024 + (8 * (i >> 2) + 4 * h + (i & 3)) * 32 + r] = acc[0][i];
+        }
+        lds_barrier();
+        // z' = sum over the k slices + bias -> X_{t+1}'s latent quads (columns >= L are written as 0)
+        for (int i = tid; i < (a.Lp / 4) * 32; i += NTH) {
+            const int fq = i >> 5, rr = i & 31, m = m0 + rr;
+            if (m >= a.rows) continue;
+            const int b3 = fq >> 3, fl = (fq & 7) * 4;
+            float o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float t = 0.f;
+                for (int s = 0; s < ks; ++s) t += sR[(s * a.nb3 + b3) * 1024 + (fl + e) * 32 + rr];
+                o[e] = fq * 4 + e < a.L ? t + sbp3[fq * 4 + e] : 0.f;
+            }
+            const int x = map_row(a.amap, m);
+            *(float4*)(a.Xo + (size_t)(x >> 5) * a.x_ts + (size_t)(a.out_q0 + fq) * 128 + (x & 31) * 4) =
+                make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+
+    // ---- 5. reward MLP on h'
+    {
+        floatx16 acc[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+        uint4 wr[2][2][3];
+        const unsigned short* Wp = a.Xp0r0 + (size_t)(M / 32 + cw0) * kgh * 1536 + lane * 8;
+        const long wbs = (long)kgh * 1536;
+        ring6_fill<2, 2>(wr, Wp, wbs, 0, kgh);
+        ring6_run<2, 2>(acc, wr, sH, Wp, wbs, 0, kgh, r, h);
+        // (every wave is past the prior's reads of sX: the barrier after its partial tiles)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = (cw0 + j) * 32 + 8 * q + 4 * h;
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = elu_f(acc[j][4 * q + e] + sbr0[c + e]);
+                *(float4*)(sX + (((cw0 + j) * 8 + 2 * q + h) * 32 + r) * 4) = make_float4(o[0], o[1], o[2], o[3]);
+            }
+    }
+    lds_barrier();
+    {
+        floatx16 acc[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+        uint4 wr[2][2][3];
+        const unsigned short* Wp = a.Xr2 + (size_t)cw0 * (M / 16) * 1536 + lane * 8;
+        const long wbs = (long)(M / 16) * 1536;
+        ring6_fill<2, 2>(wr, Wp, wbs, 0, M / 16);
+        ring6_run<2, 2>(acc, wr, sX, Wp, wbs, 0, M / 16, r, h);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = (cw0 + j) * 32 + 8 * q + 4 * h;
+                s += (elu_f(acc[j][4 * q] + sbr2[c]) * swr4[c] + elu_f(acc[j][4 * q + 1] + sbr2[c + 1]) * swr4[c + 1]) +
+                     (elu_f(acc[j][4 * q + 2] + sbr2[c + 2]) * swr4[c + 2] +
+                      elu_f(acc[j][4 * q + 3] + sbr2[c + 3]) * swr4[c + 3]);
+            }
+        s += __shfl_xor(s, 32);
+        if (h == 0) red[wave * 32 + r] = s;
+        lds_barrier();
+        if (tid < 32 && m0 + tid < a.rows) {
+            const int x = map_row(a.amap, m0 + tid);
+            float tot = 0.f;
+#pragma unroll
+            for (int w = 0; w < DRNN_NW; ++w) tot += red[w * 32 + tid];
+            const float o = tot + a.b_r4[0];
+            if (a.G) {
+                // G += discount * reward (tdmpc_similarity_drnn.py:141), float32(discount) like ATen's scalar mul
+                const float dr = fmul(a.disc, o);
+                a.G[x] = a.first ? dr : fadd(a.G[x], dr);
+            }
+            if (a.last && a.rlast) a.rlast[x] = o;
+        }
+    }
+}
+
+// z [rows][L], a [rows][A] -> the [a | 0 | z | 0] rows of an X panel (padding written as 0)
+__global__ void drnn_scatter_kernel(const float* z, const float* act, float* X, int rows, int L, int A, int Ap, int Kx) {
+    const size_t total = (size_t)rows * Kx;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t m = i / Kx;
+        const int c = (int)(i % Kx);
+        const float v = c < A ? act[m * A + c] : (c >= Ap && c < Ap + L ? z[m * L + (c - Ap)] : 0.f);
+        X[pidx(m, c, Kx)] = v;
+    }
+}
+
+// two vectors of n floats in one launch (estimate_value's outputs)
+__global__ void drnn_copy2_kernel(const float* s0, float* d0, const float* s1, float* d1, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        d0[i] = s0[i];
+        d1[i] = s1[i];
+    }
+}
+
+// src [rows][sld] -> dst [rows][dld], the first n columns
+__global__ void drnn_copy_rows_kernel(const float* src, int sld, float* dst, int dld, int n, int rows) {
+    const int total = rows * n;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+        dst[(size_t)(i / n) * dld + i % n] = src[(size_t)(i / n) * sld + i % n];
+}
+
+#else  // ================================================================================================ DRNN_HOST
+
+namespace {
+
+// The packed buffer of a DSSM planner: the TOLD layout of its base dims (encoder, pi, Q1, Q2 and the job table; the
+// TOLD dynamics / reward regions stay unused), then the regions below (float offsets from the buffer's start).
+struct DrnnLayout {
+    int Hd;
+    size_t x_ih, x_hh, ln, x_p0r0, b_p0, bn_w, bn_b, bn_m, bn_v, x_p3, b_p3, b_r0, x_r2, b_r2, w_r4, b_r4;
+    size_t total;
+};
+
+bool drnn_check(const tdmpc_drnn_dims* d, Layout* w, DrnnLayout* dl) {
+    if (!check_dims(&d->base)) { snprintf(g_err, sizeof g_err, "drnn: bad planner dims"); return false; }
+    make_layout(&d->base, w);
+    const int Hd = d->hidden_dim;
+    if (d->base.modality != 0 || !d->base.enc_norm) {
+        snprintf(g_err, sizeof g_err, "drnn: state observations with the LayerNorm encoder only (modality %d, enc_norm %d)",
+                 d->base.modality, d->base.enc_norm);
+        return false;
+    }
+    if (w->M != DRNN_M) { snprintf(g_err, sizeof g_err, "drnn: mlp_dim %d (512 only)", w->M); return false; }
+    if (Hd < 32 || Hd > 256 || Hd % 32) {
+        snprintf(g_err, sizeof g_err, "drnn: hidden_dim %d (a multiple of 32 up to 256)", Hd);
+        return false;
+    }
+    if (w->Lr > 256 || rup(w->Kx, 16) > (size_t)DRNN_M || !chain_shape_ok(*w)) {
+        snprintf(g_err, sizeof g_err, "drnn: latent_dim %d / action_dim %d outside the step and chain kernels' range",
+                 w->L, w->A);
+        return false;
+    }
+    if ((size_t)drnn_lds_floats(Hd, w->Lr) * 4 > 160 * 1024) { snprintf(g_err, sizeof g_err, "drnn: LDS"); return false; }
+    size_t o = w->total;
+    auto take = [&](size_t n) { size_t r = o; o += rup(n, 64); return r; };
+    auto x6f = [](size_t r, size_t k) { return rup(r, 32) * rup(k, 16) * 3 / 2; };
+    const size_t M = DRNN_M;
+    dl->Hd = Hd;
+    dl->x_ih = take(x6f(3 * Hd, w->Kx)); dl->x_hh = take(x6f(3 * Hd, Hd)); dl->ln = take(6 * Hd);
+    dl->x_p0r0 = take(x6f(2 * M, Hd));
+    dl->b_p0 = take(M); dl->bn_w = take(M); dl->bn_b = take(M); dl->bn_m = take(M); dl->bn_v = take(M);
+    dl->x_p3 = take(x6f(w->Lr, M)); dl->b_p3 = take(w->Lr);
+    dl->b_r0 = take(M); dl->x_r2 = take(x6f(M, M)); dl->b_r2 = take(M); dl->w_r4 = take(M); dl->b_r4 = take(1);
+    dl->total = o;
+    return true;
+}
+
+// workspace: the planner's (make_work), then two hidden-state buffers [xrows][Hd] (ping-pong over the steps)
+struct DrnnWork { float* hb[2]; size_t total; };
+void drnn_work(const tdmpc_drnn_dims* d, const Layout& w, char* base, DrnnWork* dw) {
+    Work k;
+    make_work(&d->base, w, nullptr, &k);
+    size_t o = k.total;
+    for (int i = 0; i < 2; ++i) {
+        dw->hb[i] = base ? (float*)(base + o) : nullptr;
+        o += rup((size_t)k.xrows * d->hidden_dim * 4, 256);
+    }
+    dw->total = o;
+}
+
+constexpr int DRNN_NT = 62;   // tensors of tdmpc_drnn_pack_weights (tdmpc_drnn.h)
+constexpr int DRNN_PROF_CFG = 7;
+
+struct DrnnCtx { Ctx c; DrnnLayout dl; DrnnWork dw; };
+
+// drnn_step_kernel's dynamic LDS limit (once; the pack sets it too, so a first plan under capture makes no such call)
+int drnn_attrs() {
+    static int done = 0;
+    if (done) return 0;
+    HIPCHK(hipFuncSetAttribute((const void*)drnn_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    done = 1;
+    return 0;
+}
+
+int drnn_setup(DrnnCtx& x, const tdmpc_drnn_dims* d, const void* packed, void* ws, size_t ws_bytes, int batch, int H,
+               int I, hipStream_t s) {
+    Layout w;
+    if (!drnn_check(d, &w, &x.dl)) return TDMPC_E_DIMS;
+    drnn_work(d, w, nullptr, &x.dw);
+    if (ws_bytes < x.dw.total) { snprintf(g_err, sizeof g_err, "drnn: workspace too small"); return TDMPC_E_SIZE; }
+    drnn_work(d, w, (char*)ws, &x.dw);
+    int rc = setup_ctx(x.c, &d->base, packed, ws, ws_bytes, batch, H, I, s);
+    if (rc) return rc;
+    // one kernel family for every launch size, so a row's arithmetic does not depend on the batch it is planned in
+    x.c.path = TDMPC_PATH_CHAIN_X6;
+    return drnn_attrs();
+}
+
+// One DSSM.next over `rows` logical rows of X_t (+ the return update). hin / h_G as DrnnArgs; step t reads the
+// hidden buffer t & 1 unless hin is given, and writes buffer (t + 1) & 1 unless hout is given.
+int drnn_step(const DrnnCtx& x, int t, int rows, RowMap map, const float* hin, int h_G, float* hout, float* G,
+              float* rlast, float disc, int first, int last) {
+    if (rows <= 0) return 0;
+    const Ctx& c = x.c;
+    const Layout& w = c.w;
+    const DrnnLayout& dl = x.dl;
+    DrnnArgs a;
+    memset(&a, 0, sizeof a);
+    a.rows = rows; a.Hd = dl.Hd; a.Kx = c.Kx; a.L = w.L; a.Lp = w.Lp; a.nb3 = w.Lr / 32; a.amap = map;
+    a.X = Xt(c, t); a.Xo = Xt(c, t + 1); a.x_ts = (long)c.Kx * 32; a.out_q0 = w.Ap / 4;
+    a.hin = hin ? hin : x.dw.hb[t & 1]; a.h_G = hin ? h_G : 0;
+    a.hout = hout ? hout : x.dw.hb[(t + 1) & 1];
+    auto us = [&](size_t off) { return (const unsigned short*)(c.pw + off); };
+    a.Xih = us(dl.x_ih); a.Xhh = us(dl.x_hh); a.Xp0r0 = us(dl.x_p0r0); a.Xp3 = us(dl.x_p3); a.Xr2 = us(dl.x_r2);
+    a.ln = c.pw + dl.ln; a.b_p0 = c.pw + dl.b_p0; a.bn_w = c.pw + dl.bn_w; a.bn_b = c.pw + dl.bn_b;
+    a.bn_m = c.pw + dl.bn_m; a.bn_v = c.pw + dl.bn_v; a.b_p3 = c.pw + dl.b_p3; a.b_r0 = c.pw + dl.b_r0;
+    a.b_r2 = c.pw + dl.b_r2; a.w_r4 = c.pw + dl.w_r4; a.b_r4 = c.pw + dl.b_r4;
+    a.G = G; a.rlast = rlast; a.disc = disc; a.first = first; a.last = last;
+    Profiler& pf = g_prof;
+    const bool prof = pf.armed && pf.cfg == DRNN_PROF_CFG && pf.n + 2 <= pf.cap && (pf.rows == 0 || rows == pf.rows);
+    if (prof) {
+        snprintf(pf.kernel, sizeof pf.kernel, "drnn_step_kernel");
+        HIPCHK(hipEventRecord(pf.ev[pf.n], c.s));
+    }
+    const size_t lds = (size_t)drnn_lds_floats(dl.Hd, w.Lr) * 4;
+    hipLaunchKernelGGL(drnn_step_kernel, dim3((rows + 31) / 32), dim3(64 * DRNN_NW), lds, c.s, a);
+    HIPCHK(hipGetLastError());
+    if (prof) {
+        HIPCHK(hipEventRecord(pf.ev[pf.n + 1], c.s));
+        pf.n += 2;
+        const double Hd = dl.Hd, M = DRNN_M;
+        pf.flops += 2.0 * rows * (3 * Hd * (w.L + w.A + Hd) + 2 * Hd * M + M * w.L + M * M + M);
+    }
+    return 0;
+}
+
+int drnn_bad_path(const tdmpc_plan_params* prm) {
+    if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tdmpc_drnn_version(void) { return TDMPC_DRNN_VERSION; }
+
+int tdmpc_drnn_sizes_for(const tdmpc_drnn_dims* d, tdmpc_sizes* out) {
+    if (!d || !out) return TDMPC_E_NULL;
+    Layout w;
+    DrnnLayout dl;
+    if (!drnn_check(d, &w, &dl)) return TDMPC_E_DIMS;
+    DrnnWork dw;
+    drnn_work(d, w, nullptr, &dw);
+    out->packed_weight_bytes = rup(dl.total * 4, 256);
+    out->workspace_bytes = dw.total;
+    out->noise_floats_per_env = tdmpc_noise_floats(&d->base, d->base.max_horizon, d->base.max_iterations);
+    return 0;
+}
+
+int tdmpc_drnn_num_param_tensors(const tdmpc_drnn_dims* d) {
+    if (!d) return TDMPC_E_NULL;
+    return DRNN_NT;
+}
+
+int tdmpc_drnn_pack_weights(const tdmpc_drnn_dims* d, const float* const* t, int32_t n, void* packed, size_t bytes,
+                            void* stream) {
+    if (!d || !t || !packed) return TDMPC_E_NULL;
+    Layout w;
+    DrnnLayout dl;
+    if (!drnn_check(d, &w, &dl)) return TDMPC_E_DIMS;
+    if (n != DRNN_NT) { snprintf(g_err, sizeof g_err, "drnn pack: %d tensors, %d expected", n, DRNN_NT); return TDMPC_E_DIMS; }
+    if (bytes < dl.total * 4) return TDMPC_E_SIZE;
+    if (init_attrs() || drnn_attrs()) return TDMPC_E_HIP;
+    for (int i = 0; i < n; ++i)
+        if (!t[i]) return TDMPC_E_NULL;
+    // the shared heads in the planner's own layout: encoder (48..53), pi (22..27), Q1 (28..37), Q2 (38..47)
+    const float* heads[32];
+    for (int i = 0; i < 6; ++i) heads[i] = t[48 + i];
+    for (int i = 0; i < 26; ++i) heads[6 + i] = t[22 + i];
+    std::vector<PackJob> jobs;
+    pack_jobs(w, heads, jobs, true);
+    const int M = DRNN_M, Hd = dl.Hd, L = w.L, A = w.A;
+    auto job = [&](int kind, size_t dst, long work) -> PackJob& {
+        PackJob j;
+        memset(&j, 0, sizeof j);
+        j.kind = kind; j.dst = dst; j.work = work;
+        jobs.push_back(j);
+        return jobs.back();
+    };
+    auto cp = [&](size_t dst, const float* src, int cnt) {
+        PackJob& j = job(PJ_COPY, dst, (long)rup(cnt, 64));
+        j.src = src; j.n = cnt;
+    };
+    auto x6 = [&](size_t dst, const float* p0, const float* p1, int r0, int r1, int sld, int ncols, int first, int pk) {
+        PackJob& j = job(PJ_X6, dst, (long)((r0 + r1 + 31) / 32) * ((pk + 15) / 16) * 512);
+        memset(&j.m, 0, sizeof j.m);
+        j.m.p0 = p0; j.m.p1 = p1 ? p1 : p0; j.m.r0 = r0; j.m.r1 = r1; j.m.sld = sld; j.m.ncols = ncols;
+        j.m.first = first; j.m.L = L; j.m.A = A; j.m.Ap = w.Ap;
+        j.prow = r0 + r1; j.pk = pk;
+    };
+    x6(dl.x_ih, t[8], nullptr, 3 * Hd, 0, L + A, L, 1, w.Kx);          // gru_cell.weight_ih: [z | a] -> [a | 0 | z | 0]
+    x6(dl.x_hh, t[9], nullptr, 3 * Hd, 0, Hd, Hd, 0, Hd);
+    for (int i = 0; i < 6; ++i) cp(dl.ln + (size_t)i * Hd, t[10 + i], Hd);
+    x6(dl.x_p0r0, t[0], t[16], M, M, Hd, Hd, 0, Hd);                    // prior_mlp.0 rows, then _reward.0 rows
+    cp(dl.b_p0, t[1], M); cp(dl.bn_w, t[2], M); cp(dl.bn_b, t[3], M); cp(dl.bn_m, t[4], M); cp(dl.bn_v, t[5], M);
+    x6(dl.x_p3, t[6], nullptr, L, 0, M, M, 0, M);
+    {   // (the bias slot holds Lr floats: zeros past L)
+        PackJob& j = job(PJ_COPY, dl.b_p3, (long)rup(w.Lr, 64));
+        j.src = t[7]; j.n = L;
+    }
+    cp(dl.b_r0, t[17], M);
+    x6(dl.x_r2, t[18], nullptr, M, 0, M, M, 0, M);
+    cp(dl.b_r2, t[19], M); cp(dl.w_r4, t[20], M); cp(dl.b_r4, t[21], 1);
+    return launch_pack(jobs, w, (float*)packed, (hipStream_t)stream);
+}
+
+int tdmpc_drnn_next(const tdmpc_drnn_dims* d, const void* packed, const float* z, const float* act, const float* h,
+                    int32_t rows, float* z_out, float* h_out, float* r_out, void* workspace, size_t ws_bytes,
+                    void* stream) {
+    if (!d || !packed || !z || !act || !h || !z_out || !h_out || !r_out || !workspace) return TDMPC_E_NULL;
+    DrnnCtx x;
+    int rc;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, 1, 1, 1, (hipStream_t)stream))) return rc;
+    const Ctx& c = x.c;
+    if (rows <= 0 || rows > c.k.xrows) {
+        snprintf(g_err, sizeof g_err, "drnn_next: %d rows (1..%d)", rows, c.k.xrows);
+        return TDMPC_E_DIMS;
+    }
+    const long total = (long)rows * c.Kx;
+    hipLaunchKernelGGL(drnn_scatter_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, c.s,
+                       z, act, c.k.X, rows, c.w.L, c.w.A, c.w.Ap, c.Kx);
+    HIPCHK(hipGetLastError());
+    if ((rc = drnn_step(x, 0, rows, RowMap{1 << 30, 0, 0}, h, 0, h_out, nullptr, r_out, 1.f, 1, 1))) return rc;
+    hipLaunchKernelGGL(gather_z_kernel, dim3(256), dim3(256), 0, c.s, Xt(c, 1), c.Kx, c.w.Ap, c.w.L, rows, z_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdmpc_drnn_estimate_value(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, const void* packed,
+                              const float* z0, const float* h0, const float* actions, const float* eps_term,
+                              int32_t rows, float* value, float* reward_last, void* workspace, size_t ws_bytes,
+                              void* stream) {
+    if (!d || !prm || !packed || !z0 || !h0 || !actions || !eps_term || !value || !reward_last || !workspace)
+        return TDMPC_E_NULL;
+    DrnnCtx x;
+    int rc;
+    const int H = prm->horizon, B = prm->batch;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
+    if ((rc = drnn_bad_path(prm))) return rc;
+    Ctx& c = x.c;
+    if (rows != c.T) { snprintf(g_err, sizeof g_err, "rows must equal N+P"); return TDMPC_E_DIMS; }
+    const int T = c.T;
+    if ((rc = load_z0(c, z0))) return rc;
+    hipLaunchKernelGGL(scatter_actions_kernel, dim3(512), dim3(256), 0, c.s, actions, c.k.X, c.k.x_stride, H, T, c.A,
+                       c.w.Ap, c.Kx, B, T, 0);
+    HIPCHK(hipGetLastError());
+    const RowMap all = {T, T, 0};
+    for (int t = 0; t < H; ++t)
+        if ((rc = drnn_step(x, t, B * T, all, t == 0 ? h0 : nullptr, T, nullptr, c.k.G, c.k.rlast, prm->discount_pow[t],
+                            t == 0, t == H - 1)))
+            return rc;
+    if ((rc = policy(c, H, B * T, all, eps_term, (long)T * c.A, T, 0, prm->min_std))) return rc;
+    if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
+    hipLaunchKernelGGL(qvalue_kernel, dim3((B * T + 255) / 256), dim3(256), 0, c.s, c.k.G, c.k.qv, c.k.xrows,
+                       prm->discount_pow[H], c.k.value, B * T);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(drnn_copy2_kernel, dim3(64), dim3(256), 0, c.s, c.k.value, value, c.k.rlast, reward_last, B * T);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdmpc_drnn_pi_rollout(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, const void* packed, const float* z0,
+                          const float* h0, const float* eps_pi, float* pi_actions, void* workspace, size_t ws_bytes,
+                          void* stream) {
+    if (!d || !prm || !packed || !z0 || !h0 || !eps_pi || !pi_actions || !workspace) return TDMPC_E_NULL;
+    DrnnCtx x;
+    int rc;
+    const int H = prm->horizon, B = prm->batch;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
+    if ((rc = drnn_bad_path(prm))) return rc;
+    Ctx& c = x.c;
+    const int N = c.N, P = c.P, T = c.T;
+    const long A = c.A;
+    if (P <= 0) { snprintf(g_err, sizeof g_err, "num_pi is 0"); return TDMPC_E_DIMS; }
+    if ((rc = load_z0(c, z0))) return rc;
+    const RowMap pm = {P, T, N};
+    for (int t = 0; t < H; ++t) {
+        if ((rc = policy(c, t, B * P, pm, eps_pi, (long)H * P * A, P, (long)t * P * A, prm->min_std))) return rc;
+        if (t < H - 1 && (rc = drnn_step(x, t, B * P, pm, t == 0 ? h0 : nullptr, P, nullptr, nullptr, nullptr, 1.f,
+                                          t == 0, 0)))
+            return rc;
+    }
+    hipLaunchKernelGGL(gather_actions_kernel, dim3(512), dim3(256), 0, c.s, c.k.X, c.k.x_stride, H, P, c.A, c.Kx, B, T,
+                       N, pi_actions);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdmpc_drnn_plan(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, const void* packed, const void* obs,
+                    const float* hidden, const float* noise, const double* u, float* prev_mean, float* action,
+                    float* metrics, float* z_out, float* elite_out, float* score_out, float* value_out,
+                    float* mean_out, float* std_out, void* workspace, size_t ws_bytes, void* stream) {
+    if (!d || !prm || !packed || !obs || !hidden || !noise || !u || !prev_mean || !action || !metrics || !workspace)
+        return TDMPC_E_NULL;
+    DrnnCtx x;
+    int rc;
+    const int H = prm->horizon, I = prm->iterations, B = prm->batch;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream))) return rc;
+    if ((rc = drnn_bad_path(prm))) return rc;   // (checked like the other entry points; the path itself is fixed)
+    Ctx& c = x.c;
+    const int N = c.N, P = c.P, T = c.T;
+    // z0 = h(obs) and mean = 0 (warm: prev_mean shifted), std = 2
+    if ((rc = encode(c, obs, 0, B, prev_mean, prm->warm_start, 0, 2.f, prm->warm_flags))) return rc;
+    if (z_out) {
+        hipLaunchKernelGGL(drnn_copy_rows_kernel, dim3(B), dim3(256), 0, c.s, c.k.z0, c.w.Lp, z_out, c.w.L, c.w.L, B);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = prep(c, noise, 0, c.k.z0))) return rc;
+    // The policy pre-rollout (tdmpc_similarity_drnn.py:203-209) fused with CEM iteration 0, as tdmpc_plan: at each
+    // step the policy rows get pi(z_t), then one step launch advances all T rows of every env from the env's hidden.
+    // The policy rows' rollout is the same in every iteration, so later iterations roll out the N sampled rows only.
+    const RowMap all = {T, T, 0}, pm = {P, T, N}, rm = {N, T, 0};
+    if (P > 0) {
+        for (int t = 0; t < H; ++t) {
+            if ((rc = policy(c, t, B * P, pm, noise, c.eps_env, P, (long)t * P * c.A, prm->min_std))) return rc;
+            if ((rc = drnn_step(x, t, B * T, all, t == 0 ? hidden : nullptr, T, nullptr, c.k.G, c.k.rlast,
+                                prm->discount_pow[t], t == 0, t == H - 1)))
+                return rc;
+        }
+    }
+    CemArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.H = H; ca.N = N; ca.P = P; ca.T = T; ca.A = c.A; ca.K = d->base.num_elites; ca.Kx = c.Kx;
+    ca.Hmax = d->base.max_horizon; ca.I = I;
+    ca.Tw = T; ca.NE = T; ca.pi_base = 0;
+    ca.X = c.k.X; ca.x_stride = c.k.x_stride; ca.value = c.k.value; ca.rlast = c.k.rlast;
+    ca.mean = c.k.mean; ca.stdv = c.k.stdv;
+    ca.eps = noise; ca.eps_env = c.eps_env; ca.eps_cem_off = c.eps_cem_off; ca.eps_iter = c.eps_iter;
+    ca.eps_act_off = c.eps_act_off; ca.u = u; ca.prev_mean = prev_mean;
+    ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
+    ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
+    ca.std_floor_p = prm->std_floor_dev;
+    ca.elite_out = elite_out; ca.score_out = score_out; ca.mean_out = mean_out; ca.std_out = std_out;
+    ca.value_out = value_out;
+    ca.pstatus = pack_status(c); ca.status = prm->status;
+    ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H];   // (chain Q: q1, q2 per row)
+    const size_t cem_lds = cem_lds_bytes(T, H, ca.K, c.A);
+    for (int i = 0; i < I; ++i) {
+        const long toff = c.eps_cem_off + (long)i * c.eps_iter + c.eps_term_off;
+        if (i > 0 && (rc = prep(c, noise, i, nullptr))) return rc;
+        if (i > 0 || P == 0)
+            for (int t = 0; t < H; ++t)
+                if ((rc = drnn_step(x, t, B * N, rm, t == 0 ? hidden : nullptr, N, nullptr, c.k.G, c.k.rlast,
+                                    prm->discount_pow[t], t == 0, t == H - 1)))
+                    return rc;
+        if ((rc = policy(c, H, B * T, all, noise, c.eps_env, T, toff, prm->min_std))) return rc;
+        if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
+        ca.final_iter = i == I - 1;
+        ca.iter = i;
+        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+int tdmpc_drnn_profile_begin(int32_t rows, int32_t max_launches) {
+    return tdmpc_profile_begin(DRNN_PROF_CFG, -1, 0, rows, max_launches);
+}
+
+int tdmpc_drnn_profile_end(int32_t* launches, double* total_ms, double* flops) {
+    return tdmpc_profile_end(launches, total_ms, flops);
+}
+
+}  // extern "C"
+
+#endif  // DRNN_HOST

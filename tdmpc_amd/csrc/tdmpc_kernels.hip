@@ -3224,6 +3224,7 @@ int set_lds_attr() {
 #include "plan1.inc"
 #include "wide_step.inc"
 #include "wide_heads.inc"
+#include "drnn.inc"
 
 #define FOR_EACH_LINEAR(X)                                                                          \
     X(1, 1, 1, 1, 0, 32, false) X(1, 1, 1, 1, 0, 64, false) X(1, 1, 1, 1, 0, 128, false)              \
@@ -4688,8 +4689,10 @@ int pack_fold(const Layout& w, float* pw, hipStream_t s) {
     return fold_one(w, pw, s, w.wq1x, 2 * w.M, w.Kx, w.Ap, w.bq1x, w.fold_q, w.fq_b, w.fq_x6, 1, k);
 }
 
-// The job list of a layout and the reference tensors t (state_dict order, tdmpc_num_param_tensors of them)
-void pack_jobs(const Layout& w, const float* const* t, std::vector<PackJob>& jobs) {
+// The job list of a layout and the reference tensors t (state_dict order, tdmpc_num_param_tensors of them).
+// heads_only (the DSSM planner, drnn.inc): t holds the encoder, pi, Q1 and Q2 tensors only, and the TOLD dynamics /
+// reward regions get no job.
+void pack_jobs(const Layout& w, const float* const* t, std::vector<PackJob>& jobs, bool heads_only = false) {
     const int M = w.M, L = w.L, A = w.A;
     auto job = [&](int kind, size_t dst, long work) -> PackJob& {
         PackJob j;
@@ -4740,7 +4743,7 @@ void pack_jobs(const Layout& w, const float* const* t, std::vector<PackJob>& job
     const int KI = L + A;
     const float* const* dyn = t + i;        // 0.w 0.b 2.w 2.b 4.w 4.b
     const float* const* rew = dyn + 6;
-    const float* const* pi = rew + 6;
+    const float* const* pi = heads_only ? dyn : rew + 6;
     const float* const* q1 = pi + 6;        // 0.w 0.b 1.w 1.b 3.w 3.b 4.w 4.b 6.w 6.b
     const float* const* q2 = q1 + 10;
     const PackSrc sW1X = msrc(dyn[0], rew[0], M, M, KI, L, 1), sW2D = msrc(dyn[2], nullptr, M, 0, M, M, 0),
@@ -4748,12 +4751,14 @@ void pack_jobs(const Layout& w, const float* const* t, std::vector<PackJob>& job
                   sWP1 = msrc(pi[0], nullptr, M, 0, L, L, 0), sWP2 = msrc(pi[2], nullptr, M, 0, M, M, 0),
                   sWP3 = msrc(pi[4], nullptr, A, 0, M, M, 0), sWQ1X = msrc(q1[0], q2[0], M, M, KI, L, 1),
                   sWQ2 = msrc(q1[4], q2[4], M, M, M, M, 0);
-    panel(w.w1x, sW1X, 2 * M, w.Kx);
-    cp(w.b1x, dyn[1], M); cp(w.b1x + M, rew[1], M);
-    panel(w.w2d, sW2D, M, M); cp(w.b2d, dyn[3], M);
-    panel(w.w3d, sW3D, w.Lr, M); cp(w.b3d, dyn[5], L);
-    panel(w.w2r, sW2R, M, M); cp(w.b2r, rew[3], M);
-    cp(w.w3r, rew[4], M); cp(w.b3r, rew[5], 1);
+    if (!heads_only) {
+        panel(w.w1x, sW1X, 2 * M, w.Kx);
+        cp(w.b1x, dyn[1], M); cp(w.b1x + M, rew[1], M);
+        panel(w.w2d, sW2D, M, M); cp(w.b2d, dyn[3], M);
+        panel(w.w3d, sW3D, w.Lr, M); cp(w.b3d, dyn[5], L);
+        panel(w.w2r, sW2R, M, M); cp(w.b2r, rew[3], M);
+        cp(w.w3r, rew[4], M); cp(w.b3r, rew[5], 1);
+    }
     panel(w.wp1, sWP1, M, w.Lp); cp(w.bp1, pi[1], M);
     panel(w.wp2, sWP2, M, M); cp(w.bp2, pi[3], M);
     panel(w.wp3, sWP3, w.Ar, M); cp(w.bp3, pi[5], A);
@@ -4771,13 +4776,13 @@ void pack_jobs(const Layout& w, const float* const* t, std::vector<PackJob>& job
         jb->src = Q[9]; jb->n = 1;
     }
     const PackSrc* xs[X6_N] = {&sW1X, &sW2D, &sW2R, &sW3D, &sWP1, &sWP2, &sWP3, &sWQ1X, &sWQ2};
-    for (int x = 0; x < X6_N; ++x) {
+    for (int x = heads_only ? X6_WP1 : 0; x < X6_N; ++x) {
         int rows, k;
         x6_shape(w, x, &rows, &k);
         PackJob& j = job(PJ_X6, w.x6[x], (long)((rows + 31) / 32) * ((k + 15) / 16) * 512);
         j.m = *xs[x]; j.prow = rows; j.pk = k;
     }
-    for (int x = 0; x < X6_N; ++x) {
+    for (int x = heads_only ? X6_WP1 : 0; x < X6_N; ++x) {
         int rows, k;
         x6_shape(w, x, &rows, &k);
         PackJob& j = job(PJ_X6Q, w.x6q[x], (long)((rows + 15) / 16) * ((k + 31) / 32) * 512);
@@ -5574,3 +5579,7 @@ int tdmpc_profile_end(int32_t* launches, double* total_ms, double* flops) {
 const char* tdmpc_profile_kernel(void) { return g_prof.kernel; }
 
 }  // extern "C"
+
+#define DRNN_HOST
+#include "../../include/tdmpc_drnn.h"
+#include "drnn.inc"

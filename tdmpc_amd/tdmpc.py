@@ -118,9 +118,8 @@ class HipPlanner:
         self.path = path
         self.device = torch.device(device or "cuda")
         self.L = _lib.lib()
-        self.dims = _lib.dims_from_cfg(cfg, max_batch=max_batch)
-        sz = _lib.Sizes()
-        _lib.check(self.L.tdmpc_sizes_for(C.byref(self.dims), C.byref(sz)), "tdmpc_sizes_for")
+        self.dims = self._make_dims(cfg, max_batch)
+        sz = self._query_sizes()
         self.sizes = sz
         dev = self.device
         # zeroed once: tdmpc_pack_weights writes every tensor's region (padding included) but not the alignment gaps
@@ -192,6 +191,15 @@ class HipPlanner:
         self._st_ev = [None, None]
         self._st_pending = [False, False]
         self._st_k = 0
+
+    # (hooks of the planners built on this one: tdmpc_amd/drnn.py)
+    def _make_dims(self, cfg, max_batch):
+        return _lib.dims_from_cfg(cfg, max_batch=max_batch)
+
+    def _query_sizes(self):
+        sz = _lib.Sizes()
+        _lib.check(self.L.tdmpc_sizes_for(C.byref(self.dims), C.byref(sz)), "tdmpc_sizes_for")
+        return sz
 
     # ------------------------------------------------------------------ weights
     def pack(self, model: TOLD):
