@@ -51,6 +51,12 @@ int tdmpc_drnn_num_param_tensors(const tdmpc_drnn_dims* dims);
 int tdmpc_drnn_pack_weights(const tdmpc_drnn_dims* dims, const float* const* tensors, int32_t n_tensors,
                             void* packed, size_t packed_bytes, void* stream);
 
+/* Diagnostic, host only (no HIP call), as tdmpc_debug_pack_check: builds the job table of tdmpc_drnn_pack_weights over
+ * fake tensor bases and checks that the shared heads' jobs write inside the planner layout, the DSSM jobs behind it and
+ * inside the packed size, that no two DSSM jobs write the same float, and that every job reads inside its source
+ * tensor of numel[i] floats. Returns the job count, or a negative TDMPC_E_* code with a message. */
+int tdmpc_drnn_debug_pack_check(const tdmpc_drnn_dims* dims, const int64_t* numel, int32_t n_tensors);
+
 /* DSSM.next (tdmpc_similarity_drnn.py:57-60) for `rows` independent rows (rows <= max_batch * (N + P) rounded up to
  * 32): z [rows, L], a [rows, A], h [rows, Hd] -> z_out [rows, L], h_out [rows, Hd] (may alias h), r_out [rows]. */
 int tdmpc_drnn_next(const tdmpc_drnn_dims* dims, const void* packed, const float* z, const float* a, const float* h,

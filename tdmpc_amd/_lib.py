@@ -29,7 +29,7 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_lg_conv_bwd_weight",
             # include/tdmpc_drnn.h
             "tdmpc_drnn_version", "tdmpc_drnn_sizes_for", "tdmpc_drnn_num_param_tensors", "tdmpc_drnn_pack_weights",
-            "tdmpc_drnn_next", "tdmpc_drnn_estimate_value", "tdmpc_drnn_pi_rollout", "tdmpc_drnn_plan",
+            "tdmpc_drnn_debug_pack_check", "tdmpc_drnn_next", "tdmpc_drnn_estimate_value", "tdmpc_drnn_pi_rollout", "tdmpc_drnn_plan",
             "tdmpc_drnn_profile_begin", "tdmpc_drnn_profile_end")
 DRNN_VERSION = 1
 
@@ -206,6 +206,7 @@ def lib():
     L.tdmpc_drnn_sizes_for.argtypes = [dd, C.POINTER(Sizes)]
     L.tdmpc_drnn_num_param_tensors.argtypes = [dd]
     L.tdmpc_drnn_pack_weights.argtypes = [dd, C.POINTER(vp), i32, vp, sz, vp]
+    L.tdmpc_drnn_debug_pack_check.argtypes = [dd, C.POINTER(C.c_int64), i32]
     L.tdmpc_drnn_next.argtypes = [dd, vp, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]
     L.tdmpc_drnn_estimate_value.argtypes = [dd, pp, vp, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     L.tdmpc_drnn_pi_rollout.argtypes = [dd, pp, vp, vp, vp, vp, vp, vp, sz, vp]

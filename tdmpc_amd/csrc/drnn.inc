@@ -471,6 +471,57 @@ int drnn_step(const DrnnCtx& x, int t, int rows, RowMap map, const float* hin, i
     return 0;
 }
 
+// The job list of tdmpc_drnn_pack_weights from the DRNN_NT tensors t: the shared heads' jobs (pack_jobs, heads only),
+// then the DSSM regions' (DrnnLayout). Returns the number of head jobs in front.
+int drnn_pack_jobs(const Layout& w, const DrnnLayout& dl, const float* const* t, std::vector<PackJob>& jobs) {
+    // the shared heads in the planner's own layout: encoder (48..53), pi (22..27), Q1 (28..37), Q2 (38..47)
+    const float* heads[32];
+    for (int i = 0; i < 6; ++i) heads[i] = t[48 + i];
+    for (int i = 0; i < 26; ++i) heads[6 + i] = t[22 + i];
+    pack_jobs(w, heads, jobs, true);
+    const int nheads = (int)jobs.size();
+    const int M = DRNN_M, Hd = dl.Hd, L = w.L, A = w.A;
+    auto job = [&](int kind, size_t dst, long work) -> PackJob& {
+        PackJob j;
+        memset(&j, 0, sizeof j);
+        j.kind = kind; j.dst = dst; j.work = work;
+        jobs.push_back(j);
+        return jobs.back();
+    };
+    auto cp = [&](size_t dst, const float* src, int cnt) {
+        PackJob& j = job(PJ_COPY, dst, (long)rup(cnt, 64));
+        j.src = src; j.n = cnt;
+    };
+    auto x6 = [&](size_t dst, const float* p0, const float* p1, int r0, int r1, int sld, int ncols, int first, int pk) {
+        PackJob& j = job(PJ_X6, dst, (long)((r0 + r1 + 31) / 32) * ((pk + 15) / 16) * 512);
+        memset(&j.m, 0, sizeof j.m);
+        j.m.p0 = p0; j.m.p1 = p1 ? p1 : p0; j.m.r0 = r0; j.m.r1 = r1; j.m.sld = sld; j.m.ncols = ncols;
+        j.m.first = first; j.m.L = L; j.m.A = A; j.m.Ap = w.Ap;
+        j.prow = r0 + r1; j.pk = pk;
+    };
+    x6(dl.x_ih, t[8], nullptr, 3 * Hd, 0, L + A, L, 1, w.Kx);          // gru_cell.weight_ih: [z | a] -> [a | 0 | z | 0]
+    x6(dl.x_hh, t[9], nullptr, 3 * Hd, 0, Hd, Hd, 0, Hd);
+    // The six LayerNorm vectors lie Hd apart, so a copy's zero tail must not run to the next 64: with Hd % 64 == 32 it
+    // would zero the next vector's first 32 floats, and the jobs of one launch run unordered. Only the last one pads
+    // the slot out.
+    for (int i = 0; i < 6; ++i) {
+        const size_t work = i < 5 ? (size_t)Hd : rup(6 * (size_t)Hd, 64) - 5 * (size_t)Hd;
+        PackJob& j = job(PJ_COPY, dl.ln + (size_t)i * Hd, (long)work);
+        j.src = t[10 + i]; j.n = Hd;
+    }
+    x6(dl.x_p0r0, t[0], t[16], M, M, Hd, Hd, 0, Hd);                    // prior_mlp.0 rows, then _reward.0 rows
+    cp(dl.b_p0, t[1], M); cp(dl.bn_w, t[2], M); cp(dl.bn_b, t[3], M); cp(dl.bn_m, t[4], M); cp(dl.bn_v, t[5], M);
+    x6(dl.x_p3, t[6], nullptr, L, 0, M, M, 0, M);
+    {   // (the bias slot holds Lr floats: zeros past L)
+        PackJob& j = job(PJ_COPY, dl.b_p3, (long)rup(w.Lr, 64));
+        j.src = t[7]; j.n = L;
+    }
+    cp(dl.b_r0, t[17], M);
+    x6(dl.x_r2, t[18], nullptr, M, 0, M, M, 0, M);
+    cp(dl.b_r2, t[19], M); cp(dl.w_r4, t[20], M); cp(dl.b_r4, t[21], 1);
+    return nheads;
+}
+
 int drnn_bad_path(const tdmpc_plan_params* prm) {
     if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
     return 0;
@@ -511,45 +562,46 @@ int tdmpc_drnn_pack_weights(const tdmpc_drnn_dims* d, const float* const* t, int
     if (init_attrs() || drnn_attrs()) return TDMPC_E_HIP;
     for (int i = 0; i < n; ++i)
         if (!t[i]) return TDMPC_E_NULL;
-    // the shared heads in the planner's own layout: encoder (48..53), pi (22..27), Q1 (28..37), Q2 (38..47)
-    const float* heads[32];
-    for (int i = 0; i < 6; ++i) heads[i] = t[48 + i];
-    for (int i = 0; i < 26; ++i) heads[6 + i] = t[22 + i];
     std::vector<PackJob> jobs;
-    pack_jobs(w, heads, jobs, true);
-    const int M = DRNN_M, Hd = dl.Hd, L = w.L, A = w.A;
-    auto job = [&](int kind, size_t dst, long work) -> PackJob& {
-        PackJob j;
-        memset(&j, 0, sizeof j);
-        j.kind = kind; j.dst = dst; j.work = work;
-        jobs.push_back(j);
-        return jobs.back();
-    };
-    auto cp = [&](size_t dst, const float* src, int cnt) {
-        PackJob& j = job(PJ_COPY, dst, (long)rup(cnt, 64));
-        j.src = src; j.n = cnt;
-    };
-    auto x6 = [&](size_t dst, const float* p0, const float* p1, int r0, int r1, int sld, int ncols, int first, int pk) {
-        PackJob& j = job(PJ_X6, dst, (long)((r0 + r1 + 31) / 32) * ((pk + 15) / 16) * 512);
-        memset(&j.m, 0, sizeof j.m);
-        j.m.p0 = p0; j.m.p1 = p1 ? p1 : p0; j.m.r0 = r0; j.m.r1 = r1; j.m.sld = sld; j.m.ncols = ncols;
-        j.m.first = first; j.m.L = L; j.m.A = A; j.m.Ap = w.Ap;
-        j.prow = r0 + r1; j.pk = pk;
-    };
-    x6(dl.x_ih, t[8], nullptr, 3 * Hd, 0, L + A, L, 1, w.Kx);          // gru_cell.weight_ih: [z | a] -> [a | 0 | z | 0]
-    x6(dl.x_hh, t[9], nullptr, 3 * Hd, 0, Hd, Hd, 0, Hd);
-    for (int i = 0; i < 6; ++i) cp(dl.ln + (size_t)i * Hd, t[10 + i], Hd);
-    x6(dl.x_p0r0, t[0], t[16], M, M, Hd, Hd, 0, Hd);                    // prior_mlp.0 rows, then _reward.0 rows
-    cp(dl.b_p0, t[1], M); cp(dl.bn_w, t[2], M); cp(dl.bn_b, t[3], M); cp(dl.bn_m, t[4], M); cp(dl.bn_v, t[5], M);
-    x6(dl.x_p3, t[6], nullptr, L, 0, M, M, 0, M);
-    {   // (the bias slot holds Lr floats: zeros past L)
-        PackJob& j = job(PJ_COPY, dl.b_p3, (long)rup(w.Lr, 64));
-        j.src = t[7]; j.n = L;
-    }
-    cp(dl.b_r0, t[17], M);
-    x6(dl.x_r2, t[18], nullptr, M, 0, M, M, 0, M);
-    cp(dl.b_r2, t[19], M); cp(dl.w_r4, t[20], M); cp(dl.b_r4, t[21], 1);
+    drnn_pack_jobs(w, dl, t, jobs);
     return launch_pack(jobs, w, (float*)packed, (hipStream_t)stream);
+}
+
+int tdmpc_drnn_debug_pack_check(const tdmpc_drnn_dims* d, const int64_t* numel, int32_t n) {
+    // Host-only, as tdmpc_debug_pack_check (no HIP call; tensor i at the fake base (i + 1) << 40): the shared heads'
+    // jobs write inside the base layout, the DSSM jobs behind it and inside DrnnLayout::total, no two DSSM jobs write
+    // the same float (the jobs of one launch run unordered), and every job reads inside its source tensor.
+    if (!d || !numel) return TDMPC_E_NULL;
+    Layout w;
+    DrnnLayout dl;
+    if (!drnn_check(d, &w, &dl)) return TDMPC_E_DIMS;
+    if (n != DRNN_NT) return TDMPC_E_DIMS;
+    std::vector<const float*> t(n);
+    for (int i = 0; i < n; ++i) t[i] = (const float*)((uintptr_t)(i + 1) << 40);
+    std::vector<PackJob> jobs;
+    const int nheads = drnn_pack_jobs(w, dl, t.data(), jobs);
+    if (jobs.size() > (size_t)PACK_MAX_JOBS) {
+        snprintf(g_err, sizeof g_err, "drnn pack: %zu jobs > %d", jobs.size(), PACK_MAX_JOBS);
+        return TDMPC_E_SIZE;
+    }
+    auto end_of = [](const PackJob& J) {
+        return J.kind == PJ_X6 || J.kind == PJ_X6Q ? (double)J.dst + 1.5 * J.work : (double)(J.dst + J.work);
+    };
+    for (int j = 0; j < (int)jobs.size(); ++j) {
+        const PackJob& J = jobs[j];
+        const bool head = j < nheads;
+        if (!pack_job_in_bounds(J, numel, n, head ? 0 : w.total, head ? w.total : dl.total)) {
+            snprintf(g_err, sizeof g_err, "drnn pack job %d (kind %d, dst %zu) out of bounds", j, J.kind, J.dst);
+            return TDMPC_E_SIZE;
+        }
+        for (int k = nheads; k < j; ++k)
+            if ((double)J.dst < end_of(jobs[k]) && (double)jobs[k].dst < end_of(J)) {
+                snprintf(g_err, sizeof g_err, "drnn pack jobs %d (dst %zu) and %d (dst %zu) overlap", k, jobs[k].dst, j,
+                         J.dst);
+                return TDMPC_E_SIZE;
+            }
+    }
+    return (int)jobs.size();
 }
 
 int tdmpc_drnn_next(const tdmpc_drnn_dims* d, const void* packed, const float* z, const float* act, const float* h,

@@ -4914,6 +4914,30 @@ int launch_pack(std::vector<PackJob>& jobs, const Layout& w, float* pw, hipStrea
     return 0;
 }
 
+// Host-only bounds check of one pack job (no HIP call), shared by tdmpc_debug_pack_check and
+// tdmpc_drnn_debug_pack_check: its writes inside the float offsets [lo, hi) of the packed buffer, its reads inside its
+// source tensor, where tensor i of n has the fake base address (i + 1) << 40 and numel[i] floats.
+bool pack_job_in_bounds(const PackJob& J, const int64_t* numel, int n, size_t lo, size_t hi) {
+    auto in_tensor = [&](const float* p, long last) -> bool {   // reads p[0 .. last]
+        const uintptr_t u = (uintptr_t)p;
+        const long i = (long)(u >> 40) - 1;
+        if (i < 0 || i >= n) return false;
+        const long off = (long)((u & (((uintptr_t)1 << 40) - 1)) / 4);
+        return off + last < numel[i];
+    };
+    auto src_ok = [&](const PackSrc& m, int maxk) -> bool {
+        const int maxcol = m.first ? m.L + m.A - 1 : std::min(maxk, m.ncols - 1);
+        if (m.r0 > 0 && !in_tensor(m.p0, (long)(m.r0 - 1) * m.sld + maxcol)) return false;
+        if (m.r1 > 0 && !in_tensor(m.p1, (long)(m.r1 - 1) * m.sld + maxcol)) return false;
+        return true;
+    };
+    const double end = J.kind == PJ_X6 || J.kind == PJ_X6Q ? (double)J.dst + 1.5 * J.work : (double)(J.dst + J.work);
+    if (J.dst < lo || end > (double)hi) return false;
+    if (J.kind == PJ_COPY) return J.n <= J.work && in_tensor(J.src, J.n - 1);
+    if (J.kind == PJ_TRANS) return in_tensor(J.src, (long)J.rows * J.cols - 1);
+    return src_ok(J.m, J.pk - 1);
+}
+
 }  // namespace
 
 namespace tdmpc_internal {
@@ -5129,27 +5153,9 @@ int tdmpc_debug_pack_check(const tdmpc_dims* d, const int64_t* numel, int32_t n)
     for (int i = 0; i < n; ++i) t[i] = (const float*)((uintptr_t)(i + 1) << 40);
     std::vector<PackJob> jobs;
     pack_jobs(w, t.data(), jobs);
-    auto in_tensor = [&](const float* p, long last) -> bool {   // reads p[0 .. last]
-        const uintptr_t u = (uintptr_t)p;
-        const long i = (long)(u >> 40) - 1;
-        if (i < 0 || i >= n) return false;
-        const long off = (long)((u & (((uintptr_t)1 << 40) - 1)) / 4);
-        return off + last < numel[i];
-    };
-    auto src_ok = [&](const PackSrc& m, int maxk) -> bool {
-        const int maxcol = m.first ? m.L + m.A - 1 : std::min(maxk, m.ncols - 1);
-        if (m.r0 > 0 && !in_tensor(m.p0, (long)(m.r0 - 1) * m.sld + maxcol)) return false;
-        if (m.r1 > 0 && !in_tensor(m.p1, (long)(m.r1 - 1) * m.sld + maxcol)) return false;
-        return true;
-    };
     for (size_t j = 0; j < jobs.size(); ++j) {
         const PackJob& J = jobs[j];
-        const double end = J.kind == PJ_X6 || J.kind == PJ_X6Q ? (double)J.dst + 1.5 * J.work : (double)(J.dst + J.work);
-        bool ok = end <= (double)w.total;
-        if (J.kind == PJ_COPY) ok = ok && J.n <= J.work && in_tensor(J.src, J.n - 1);
-        else if (J.kind == PJ_TRANS) ok = ok && in_tensor(J.src, (long)J.rows * J.cols - 1);
-        else ok = ok && src_ok(J.m, J.pk - 1);
-        if (!ok) {
+        if (!pack_job_in_bounds(J, numel, n, 0, w.total)) {
             snprintf(g_err, sizeof g_err, "pack job %d (kind %d, dst %zu) out of bounds", (int)j, J.kind, J.dst);
             return TDMPC_E_SIZE;
         }
