@@ -454,20 +454,14 @@ int drnn_step(const DrnnCtx& x, int t, int rows, RowMap map, const float* hin, i
     a.b_r2 = c.pw + dl.b_r2; a.w_r4 = c.pw + dl.w_r4; a.b_r4 = c.pw + dl.b_r4;
     a.G = G; a.rlast = rlast; a.disc = disc; a.first = first; a.last = last;
     Profiler& pf = g_prof;
-    const bool prof = pf.armed && pf.cfg == DRNN_PROF_CFG && pf.n + 2 <= pf.cap && (pf.rows == 0 || rows == pf.rows);
-    if (prof) {
-        snprintf(pf.kernel, sizeof pf.kernel, "drnn_step_kernel");
-        HIPCHK(hipEventRecord(pf.ev[pf.n], c.s));
-    }
+    const bool prof = prof_armed() && pf.cfg == DRNN_PROF_CFG && (pf.rows == 0 || rows == pf.rows);
+    if (prof) snprintf(pf.kernel, sizeof pf.kernel, "drnn_step_kernel");
+    HIPCHK(prof_begin(prof, c.s));
     const size_t lds = (size_t)drnn_lds_floats(dl.Hd, w.Lr) * 4;
     hipLaunchKernelGGL(drnn_step_kernel, dim3((rows + 31) / 32), dim3(64 * DRNN_NW), lds, c.s, a);
     HIPCHK(hipGetLastError());
-    if (prof) {
-        HIPCHK(hipEventRecord(pf.ev[pf.n + 1], c.s));
-        pf.n += 2;
-        const double Hd = dl.Hd, M = DRNN_M;
-        pf.flops += 2.0 * rows * (3 * Hd * (w.L + w.A + Hd) + 2 * Hd * M + M * w.L + M * M + M);
-    }
+    const double Hd = dl.Hd, M = DRNN_M;
+    HIPCHK(prof_end(prof, c.s, 2.0 * rows * (3 * Hd * (w.L + w.A + Hd) + 2 * Hd * M + M * w.L + M * M + M)));
     return 0;
 }
 
@@ -520,11 +514,6 @@ int drnn_pack_jobs(const Layout& w, const DrnnLayout& dl, const float* const* t,
     x6(dl.x_r2, t[18], nullptr, M, 0, M, M, 0, M);
     cp(dl.b_r2, t[19], M); cp(dl.w_r4, t[20], M); cp(dl.b_r4, t[21], 1);
     return nheads;
-}
-
-int drnn_bad_path(const tdmpc_plan_params* prm) {
-    if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
-    return 0;
 }
 
 }  // namespace
@@ -636,7 +625,7 @@ int tdmpc_drnn_estimate_value(const tdmpc_drnn_dims* d, const tdmpc_plan_params*
     int rc;
     const int H = prm->horizon, B = prm->batch;
     if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
-    if ((rc = drnn_bad_path(prm))) return rc;
+    if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
     Ctx& c = x.c;
     if (rows != c.T) { snprintf(g_err, sizeof g_err, "rows must equal N+P"); return TDMPC_E_DIMS; }
     const int T = c.T;
@@ -667,7 +656,7 @@ int tdmpc_drnn_pi_rollout(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm
     int rc;
     const int H = prm->horizon, B = prm->batch;
     if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
-    if ((rc = drnn_bad_path(prm))) return rc;
+    if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
     Ctx& c = x.c;
     const int N = c.N, P = c.P, T = c.T;
     const long A = c.A;
@@ -696,7 +685,7 @@ int tdmpc_drnn_plan(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, cons
     int rc;
     const int H = prm->horizon, I = prm->iterations, B = prm->batch;
     if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream))) return rc;
-    if ((rc = drnn_bad_path(prm))) return rc;   // (checked like the other entry points; the path itself is fixed)
+    if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
     Ctx& c = x.c;
     const int N = c.N, P = c.P, T = c.T;
     // z0 = h(obs) and mean = 0 (warm: prev_mean shifted), std = 2
@@ -718,13 +707,8 @@ int tdmpc_drnn_plan(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, cons
                 return rc;
         }
     }
-    CemArgs ca;
-    memset(&ca, 0, sizeof ca);
-    ca.H = H; ca.N = N; ca.P = P; ca.T = T; ca.A = c.A; ca.K = d->base.num_elites; ca.Kx = c.Kx;
-    ca.Hmax = d->base.max_horizon; ca.I = I;
-    ca.Tw = T; ca.NE = T; ca.pi_base = 0;
-    ca.X = c.k.X; ca.x_stride = c.k.x_stride; ca.value = c.k.value; ca.rlast = c.k.rlast;
-    ca.mean = c.k.mean; ca.stdv = c.k.stdv;
+    CemArgs ca = cem_args0(c);
+    ca.I = I;
     ca.eps = noise; ca.eps_env = c.eps_env; ca.eps_cem_off = c.eps_cem_off; ca.eps_iter = c.eps_iter;
     ca.eps_act_off = c.eps_act_off; ca.u = u; ca.prev_mean = prev_mean;
     ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
@@ -732,7 +716,7 @@ int tdmpc_drnn_plan(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, cons
     ca.std_floor_p = prm->std_floor_dev;
     ca.elite_out = elite_out; ca.score_out = score_out; ca.mean_out = mean_out; ca.std_out = std_out;
     ca.value_out = value_out;
-    ca.pstatus = pack_status(c); ca.status = prm->status;
+    ca.status = prm->status;
     ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H];   // (chain Q: q1, q2 per row)
     const size_t cem_lds = cem_lds_bytes(T, H, ca.K, c.A);
     for (int i = 0; i < I; ++i) {

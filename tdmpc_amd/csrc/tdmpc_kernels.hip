@@ -1053,9 +1053,9 @@ struct ChainArgs {
     int rows, M, K1, q1;                 // logical rows; hidden width; first-layer K and its X quad offset
     int k1_alg;                          // the first layer's real input width (L + A or L), for the profiler's FLOPs
     int rb;                              // row block: 32 (chain_kernel) or 16 (chain16_kernel)
-    int nw;                              // waves per workgroup of chain_kernel: 8 or 16
+    int nw;                              // waves per workgroup of chain_kernel: 8, or 4 (x6 mode 3)
     int hfl;                             // floats of the LDS activation block (max(K1, M) * rb, K1 to 16)
-    int il;                              // (retired: 0, the problems along blockIdx.y)
+    int il;                              // (unused, keeps the layout)
     int x6;                              // chain_kernel<..., X6 = true>: fp32 products from split bf16
     RowMap amap;                         // logical row -> X row (input and output)
     const float* X; long x_ts;           // X_t panel (input)
@@ -1431,7 +1431,7 @@ DEVI void chain_store_lds(float* sH, const float (&v)[TN * 16], int cw0, int r, 
         }
 }
 
-// NW = 8 or 16 waves per workgroup (16: 4 waves per SIMD on one 32-row block, TN = M / 512).
+// NW waves per workgroup, TN = M / (32 NW): the instances (CHAIN_FOR_EACH) have 8, or 4 for x6 on 128 columns per wave.
 // X6: 0 = f32 MFMA; 1 = x6 with the activations kept fp32 in LDS and split as read (a split-planes form in LDS
 // measured 2-3 % slower and was retired in round 3).
 template <int MODE, int TN, int NW = 8, int D = 4, int D3 = 8, int X6 = 0>
@@ -3214,10 +3214,10 @@ __global__ void gather_z_kernel(const float* X, int Kx, int Ap, int L, int rows,
         }                                                                                         \
     } while (0)
 
-template <int TM, int TN, int WGM, int WGN, int PRO, int KCH, bool ROLL>
-int set_lds_attr() {
-    HIPCHK(hipFuncSetAttribute((const void*)linear_kernel<TM, TN, WGM, WGN, PRO, KCH, ROLL>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+// Raises a kernel's dynamic LDS limit to the CU's 160 KB.
+template <auto KERNEL>
+int set_max_lds() {
+    HIPCHK(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return 0;
 }
 
@@ -3233,56 +3233,58 @@ int set_lds_attr() {
     X(1, 2, 1, 1, 1, 32, false) X(1, 2, 1, 1, 1, 64, false) X(1, 2, 1, 1, 1, 128, false)              \
     X(2, 2, 2, 2, 1, 1, true)
 
+// The instantiated kernels, one table per family: init_attrs() and the family's launch site both expand it, so a new
+// instance is one entry here (WIDE_FOR_EACH / WIDE_HEADS_FOR_EACH: wide_step.inc / wide_heads.inc).
+// linear_lds_kernel (TM, TN, WGM, WGN, KT), each with the full-K-tile and the K-tail form; selected by its tile rows
+#define LDS_FOR_EACH(X) X(2, 1, 2, 4, 32) X(3, 1, 2, 4, 32) X(1, 1, 2, 2, 32)
+// chain_kernel (MODE, TN, NW, D, D3, X6): selected by mode, TN = M / (32 NW), the waves NW and x6 on / off
+#define CHAIN_FOR_EACH(X)                                                                            \
+    X(CH_STEP, 1, 8, 4, 8, 0) X(CH_STEP, 2, 8, 4, 8, 0) X(CH_STEP, 4, 8, 4, 8, 0)                     \
+    X(CH_PI, 1, 8, 4, 8, 0) X(CH_PI, 2, 8, 4, 8, 0) X(CH_PI, 4, 8, 4, 8, 0)                           \
+    X(CH_Q, 1, 8, 4, 8, 0) X(CH_Q, 2, 8, 4, 8, 0) X(CH_Q, 4, 8, 4, 8, 0)                              \
+    X(CH_STEP, 2, 8, 2, X6_D3, 1) X(CH_STEP, 4, 4, 2, 2, 1) X(CH_PI, 2, 8, 2, X6_D3, 1)               \
+    X(CH_PI, 4, 4, 2, 2, 1) X(CH_Q, 2, 8, 2, X6_D3, 1) X(CH_Q, 4, 4, 2, 2, 1)
+// chain16_kernel (MODE, NT, D, D3, X6): selected by mode, NT = M / 128 and x6 on / off
+#define CHAIN16_FOR_EACH(X)                                                                          \
+    X(CH_STEP, 2, 4, 4, 0) X(CH_STEP, 4, 4, 4, 0) X(CH_PI, 2, 4, 4, 0) X(CH_PI, 4, 4, 4, 0)           \
+    X(CH_Q, 2, 4, 4, 0) X(CH_Q, 4, 4, 4, 0)                                                           \
+    X(CH_STEP, 4, 4, 4, 1) X(CH_PI, 4, 4, 4, 1) X(CH_Q, 4, 4, 4, 1)
+// split_step_kernel (NT, D, X6): M = 512 only, selected by x6 on / off (its LDS stays within the default 64 KB)
+#define SPLIT_FOR_EACH(X) X(4, 4, 1) X(4, 4, 0)
+// conv_tile_kernel (PX: output pixels per item)
+#define CONV_TILE_FOR_EACH(X) X(1) X(2) X(4)
+// plan1_kernel (KS: 32-k groups of the first layer's x slice, p1_ks())
+#define PLAN1_FOR_EACH(X) X(4) X(6)
+
 int init_attrs() {
     static int done = 0;
     if (done) return 0;
     int rc = 0;
-#define SET_ATTR(TM, TN, WGM, WGN, PRO, KCH, ROLL) rc |= set_lds_attr<TM, TN, WGM, WGN, PRO, KCH, ROLL>();
-    FOR_EACH_LINEAR(SET_ATTR)
-#undef SET_ATTR
-    HIPCHK(hipFuncSetAttribute((const void*)cem_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)plan1_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)plan1_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define WIDE_ATTR(G1, NB3, MODE) \
-    HIPCHK(hipFuncSetAttribute((const void*)wide_step_kernel<G1, NB3, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define LINEAR_ATTR(...) rc |= set_max_lds<linear_kernel<__VA_ARGS__>>();
+    FOR_EACH_LINEAR(LINEAR_ATTR)
+#undef LINEAR_ATTR
+    rc |= set_max_lds<cem_kernel>();
+#define PLAN1_ATTR(KS) rc |= set_max_lds<plan1_kernel<KS>>();
+    PLAN1_FOR_EACH(PLAN1_ATTR)
+#undef PLAN1_ATTR
+#define WIDE_ATTR(...) rc |= set_max_lds<wide_step_kernel<__VA_ARGS__>>();
     WIDE_FOR_EACH(WIDE_ATTR)
 #undef WIDE_ATTR
-#define WIDE_HEADS_ATTR(G1P, NB3P, G1Q, NSTQ) \
-    HIPCHK(hipFuncSetAttribute((const void*)wide_heads_kernel<G1P, NB3P, G1Q, NSTQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define WIDE_HEADS_ATTR(...) rc |= set_max_lds<wide_heads_kernel<__VA_ARGS__>>();
     WIDE_HEADS_FOR_EACH(WIDE_HEADS_ATTR)
 #undef WIDE_HEADS_ATTR
-    HIPCHK(hipFuncSetAttribute((const void*)qstat_chol_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)conv_tile_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)conv_tile_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)conv_tile_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define LDS_ATTR1(...) \
-    HIPCHK(hipFuncSetAttribute((const void*)linear_lds_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define LDS_ATTR(...) LDS_ATTR1(__VA_ARGS__, true) LDS_ATTR1(__VA_ARGS__, false)
-    LDS_ATTR(2, 1, 2, 4, 32) LDS_ATTR(3, 1, 2, 4, 32) LDS_ATTR(1, 1, 2, 2, 32)
+    rc |= set_max_lds<qstat_chol_kernel>();
+#define CONV_ATTR(PX) rc |= set_max_lds<conv_tile_kernel<PX>>();
+    CONV_TILE_FOR_EACH(CONV_ATTR)
+#undef CONV_ATTR
+#define LDS_ATTR(...) rc |= set_max_lds<linear_lds_kernel<__VA_ARGS__, true>>() | set_max_lds<linear_lds_kernel<__VA_ARGS__, false>>();
+    LDS_FOR_EACH(LDS_ATTR)
 #undef LDS_ATTR
-#undef LDS_ATTR1
-#define CHAIN_ATTR(MODE, TN) \
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<MODE, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    CHAIN_ATTR(CH_STEP, 1) CHAIN_ATTR(CH_STEP, 2) CHAIN_ATTR(CH_STEP, 4)
-    CHAIN_ATTR(CH_PI, 1) CHAIN_ATTR(CH_PI, 2) CHAIN_ATTR(CH_PI, 4)
-    CHAIN_ATTR(CH_Q, 1) CHAIN_ATTR(CH_Q, 2) CHAIN_ATTR(CH_Q, 4)
+#define CHAIN_ATTR(...) rc |= set_max_lds<chain_kernel<__VA_ARGS__>>();
+    CHAIN_FOR_EACH(CHAIN_ATTR)
 #undef CHAIN_ATTR
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_STEP, 2, 8, 2, X6_D3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_STEP, 4, 4, 2, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_PI, 2, 8, 2, X6_D3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_PI, 4, 4, 2, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_Q, 2, 8, 2, X6_D3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_Q, 4, 4, 2, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_STEP, 1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_PI, 1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain_kernel<CH_Q, 1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define CHAIN16_ATTR(MODE, NT) \
-    HIPCHK(hipFuncSetAttribute((const void*)chain16_kernel<MODE, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    CHAIN16_ATTR(CH_STEP, 2) CHAIN16_ATTR(CH_STEP, 4) CHAIN16_ATTR(CH_PI, 2) CHAIN16_ATTR(CH_PI, 4)
-    CHAIN16_ATTR(CH_Q, 2) CHAIN16_ATTR(CH_Q, 4)
-    HIPCHK(hipFuncSetAttribute((const void*)chain16_kernel<CH_STEP, 4, 4, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain16_kernel<CH_PI, 4, 4, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void*)chain16_kernel<CH_Q, 4, 4, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define CHAIN16_ATTR(...) rc |= set_max_lds<chain16_kernel<__VA_ARGS__>>();
+    CHAIN16_FOR_EACH(CHAIN16_ATTR)
 #undef CHAIN16_ATTR
     if (rc) return TDMPC_E_HIP;
     done = 1;
@@ -3300,6 +3302,20 @@ struct Profiler {
     char kernel[128] = "";   // the last timed launch's kernel (tdmpc_profile_kernel)
 };
 thread_local Profiler g_prof;
+
+// The bracket of one timed launch. A launch site forms `on` from prof_armed() and its own match condition, names its
+// kernel in g_prof.kernel, then: HIPCHK(prof_begin(on, s)); launch; HIPCHK(prof_end(on, s, flops)).
+bool prof_armed() { return g_prof.armed && g_prof.n + 2 <= g_prof.cap; }
+hipError_t prof_begin(bool on, hipStream_t s) { return on ? hipEventRecord(g_prof.ev[g_prof.n], s) : hipSuccess; }
+hipError_t prof_end(bool on, hipStream_t s, double flops) {
+    if (!on) return hipSuccess;
+    Profiler& pf = g_prof;
+    const hipError_t e = hipEventRecord(pf.ev[pf.n + 1], s);
+    if (e != hipSuccess) return e;
+    pf.n += 2;
+    pf.flops += flops;
+    return hipSuccess;
+}
 
 // Launch geometry chosen for a linear layer.
 struct LinCfg {
@@ -3320,6 +3336,13 @@ LinCfg pick_cfg(int M, int nmax, int K, int wide64) {
     return LinCfg{1, 32, 32};
 }
 
+// Algorithmic FLOPs of a fused linear launch (the profiler's count)
+double lin_flops(const LinArgs& a, int nprob, int nmax) {
+    double f = 0.0;
+    for (int q = 0; q < nprob; ++q) f += 2.0 * a.M * std::min(a.p[q].N, nmax) * a.K;
+    return f;
+}
+
 template <int TM, int TN, int WGM, int WGN, int PRO, int KCH, bool ROLL>
 int launch_lin_t(const LinArgs& a, int nprob, int nmax, int cfg_id, hipStream_t s) {
     constexpr int R = 32 * TM * WGM, C = 32 * TN * WGN;
@@ -3330,18 +3353,13 @@ int launch_lin_t(const LinArgs& a, int nprob, int nmax, int cfg_id, hipStream_t 
     dim3 grid((a.M + R - 1) / R, (nmax + C - 1) / C, nprob);
     dim3 block(64 * WGM * WGN * KS);
     const size_t lds = ((size_t)KS * R * (C + 4) + 2 * C + (size_t)R * std::max(a.rpart_nt, 1)) * 4;
-    Profiler& pf = g_prof;
-    const bool prof = pf.armed && (pf.cfg == 0 || pf.cfg == cfg_id) && (pf.pro < 0 || pf.pro == PRO) &&
-                      pf.n + 2 <= pf.cap && (pf.kdim == 0 || (a.K == pf.kdim && nmax == pf.kdim)) &&
-                      (pf.rows == 0 || a.M == pf.rows);
-    if (prof) HIPCHK(hipEventRecord(pf.ev[pf.n], s));
+    const Profiler& pf = g_prof;
+    const bool prof = prof_armed() && (pf.cfg == 0 || pf.cfg == cfg_id) && (pf.pro < 0 || pf.pro == PRO) &&
+                      (pf.kdim == 0 || (a.K == pf.kdim && nmax == pf.kdim)) && (pf.rows == 0 || a.M == pf.rows);
+    HIPCHK(prof_begin(prof, s));
     hipLaunchKernelGGL((linear_kernel<TM, TN, WGM, WGN, PRO, KCH, ROLL>), grid, block, lds, s, b);
     HIPCHK(hipGetLastError());
-    if (prof) {
-        HIPCHK(hipEventRecord(pf.ev[pf.n + 1], s));
-        pf.n += 2;
-        for (int q = 0; q < nprob; ++q) pf.flops += 2.0 * a.M * std::min(a.p[q].N, nmax) * a.K;
-    }
+    HIPCHK(prof_end(prof, s, lin_flops(a, nprob, nmax)));
     return 0;
 }
 
@@ -3357,19 +3375,15 @@ int launch_lds_t(const LinArgs& a, int nprob, int nmax, hipStream_t s) {
             return TDMPC_E_DIMS;
         }
     const size_t lds = ((size_t)3 * BUF + 2 * C + (size_t)R * (C / 32) * 2) * 4;
-    Profiler& pf = g_prof;
-    const bool prof = pf.armed && (pf.cfg == 0 || pf.cfg == 3) && (pf.pro <= 0) && pf.n + 2 <= pf.cap &&
+    const Profiler& pf = g_prof;
+    const bool prof = prof_armed() && (pf.cfg == 0 || pf.cfg == 3) && (pf.pro <= 0) &&
                       (pf.kdim == 0 || (a.K == pf.kdim && nmax == pf.kdim)) && (pf.rows == 0 || a.M == pf.rows);
-    if (prof) HIPCHK(hipEventRecord(pf.ev[pf.n], s));
+    HIPCHK(prof_begin(prof, s));
     const dim3 block(64 * WGM * WGN);
     if (a.K % KT == 0) hipLaunchKernelGGL((linear_lds_kernel<TM, TN, WGM, WGN, KT, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((linear_lds_kernel<TM, TN, WGM, WGN, KT, false>), grid, block, lds, s, a);
     HIPCHK(hipGetLastError());
-    if (prof) {
-        HIPCHK(hipEventRecord(pf.ev[pf.n + 1], s));
-        pf.n += 2;
-        for (int q = 0; q < nprob; ++q) pf.flops += 2.0 * a.M * std::min(a.p[q].N, nmax) * a.K;
-    }
+    HIPCHK(prof_end(prof, s, lin_flops(a, nprob, nmax)));
     return 0;
 }
 
@@ -3389,6 +3403,7 @@ int num_cus() {
 // (8 waves of 96x32) or 64x64 (4 waves of 32x32) when the work per CU says so.
 int launch_lds(const LinArgs& a, int nprob, int nmax, hipStream_t s) {
     const int ctiles128 = (nmax + 127) / 128, rtiles = (a.M + 127) / 128;
+    int tile_rows = 128;
     {   // Tile by the work of the busiest CU: ceil(WGs / CUs) x tile area, over the tile's efficiency.
         // 192x128 when 128x128 would need a second, partly idle round (6144 rows x 2 problems: 256 WGs
         // instead of 384); 64x64 (4 waves, 4 resident per CU) when 128x128 leaves CUs idle.
@@ -3399,10 +3414,14 @@ int launch_lds(const LinArgs& a, int nprob, int nmax, hipStream_t s) {
         const double c192 = (double)((w192 + cus - 1) / cus) * 192 * 128 / 1.05;
         const long r64 = (w64 + cus - 1) / cus;
         const double c64 = (double)r64 * 64 * 64 / (r64 >= 2 ? 0.8 : 0.4);
-        if (c192 < c128 && c192 <= c64) return launch_lds_t<3, 1, 2, 4, 32>(a, nprob, nmax, s);
-        if (c64 < c128) return launch_lds_t<1, 1, 2, 2, 32>(a, nprob, nmax, s);
+        if (c192 < c128 && c192 <= c64) tile_rows = 192;
+        else if (c64 < c128) tile_rows = 64;
     }
-    return launch_lds_t<2, 1, 2, 4, 32>(a, nprob, nmax, s);
+#define LDS_LAUNCH(TM, TN, WGM, WGN, KT) \
+    if (tile_rows == 32 * TM * WGM) return launch_lds_t<TM, TN, WGM, WGN, KT>(a, nprob, nmax, s);
+    LDS_FOR_EACH(LDS_LAUNCH)
+#undef LDS_LAUNCH
+    return TDMPC_E_DIMS;
 }
 
 // Launch one fused linear layer with the configuration pick_cfg selects.
@@ -3410,27 +3429,27 @@ int launch_lin(const LinArgs& a, int nprob, int nmax, int wide64, int pro, hipSt
     if (a.M <= 0) return 0;
     if (a.K % 8) { snprintf(g_err, sizeof g_err, "bad K %d", a.K); return TDMPC_E_DIMS; }
     const LinCfg cfg = pick_cfg(a.M, nmax, a.K, wide64);
-    if (cfg.id == 3) {   // (the register-direct 128-row variants of rounds 1-2 measured slower: git history)
-        if (pro == PRO_PLAIN) return launch_lds(a, nprob, nmax, s);
-        return launch_lin_t<2, 2, 2, 2, 1, 1, true>(a, nprob, nmax, 3, s);
-    }
+    // (the register-direct 128-row variants of rounds 1-2 measured slower: git history)
+    if (cfg.id == 3 && pro == PRO_PLAIN) return launch_lds(a, nprob, nmax, s);
+    // FOR_EACH_LINEAR's key: the latency tiles (ROLL = false) by (TN, PRO, K chunk), the one rolled 128x128 tile by
+    // (PRO, its single K split)
+    const bool roll = cfg.id == 3;
     int kch = 32;
     if ((a.K + 31) / 32 > 8) kch = 64;
     if ((a.K + 63) / 64 > 8) kch = 128;
-    if ((a.K + kch - 1) / kch > 8) { snprintf(g_err, sizeof g_err, "bad K %d", a.K); return TDMPC_E_DIMS; }
-    const int tn = cfg.id == 2 ? 2 : 1;
-#define DISPATCH(TN_, PRO_, KCH_) \
-    if (tn == TN_ && pro == PRO_ && kch == KCH_) return launch_lin_t<1, TN_, 1, 1, PRO_, KCH_, false>(a, nprob, nmax, cfg.id, s);
-    DISPATCH(1, 0, 32) DISPATCH(1, 0, 64) DISPATCH(1, 0, 128)
-    DISPATCH(2, 0, 32) DISPATCH(2, 0, 64) DISPATCH(2, 0, 128)
-    DISPATCH(1, 1, 32) DISPATCH(1, 1, 64) DISPATCH(1, 1, 128)
-    DISPATCH(2, 1, 32) DISPATCH(2, 1, 64) DISPATCH(2, 1, 128)
+    if (roll) kch = 1;
+    else if ((a.K + kch - 1) / kch > 8) { snprintf(g_err, sizeof g_err, "bad K %d", a.K); return TDMPC_E_DIMS; }
+    const int tn = cfg.id == 1 ? 1 : 2;
+#define DISPATCH(TM_, TN_, WGM_, WGN_, PRO_, KCH_, ROLL_) \
+    if (tn == TN_ && pro == PRO_ && kch == KCH_ && roll == ROLL_) \
+        return launch_lin_t<TM_, TN_, WGM_, WGN_, PRO_, KCH_, ROLL_>(a, nprob, nmax, cfg.id, s);
+    FOR_EACH_LINEAR(DISPATCH)
 #undef DISPATCH
     return TDMPC_E_DIMS;
 }
 
 // ---- chain path (chain_kernel / chain16_kernel): on the auto path used for launches of at least chain_wgs()
-// 32-row-block equivalents x problems (TDMPC_CHAIN_WGS, default 64, 0 disables). Narrow launches run on 16-row
+// 32-row-block equivalents x problems (per head: chain_wgs_kind()). Narrow launches run on 16-row
 // blocks (chain_rb), so from 64 32-row blocks on they still spread over 128+ CUs; below that the layered
 // GEMMs, whose K-split tiles spread the same rows over more CUs, finish first. Measured on MI355X (humanoid
 // plan, round-1 run): threshold 64 vs 128: B = 2 envs 1.65 vs 1.87 ms, B = 4 1.88 vs 1.98 ms; 32 loses
@@ -3485,61 +3504,46 @@ int launch_chain(int mode, const ChainArgs& a0, int nprob, hipStream_t s) {
     const int nblk = (a.rows + a.rb - 1) / a.rb;
     // (the problems along blockIdx.y: co-resident same-head workgroups on a CU share the weight stream through its L1;
     // interleaving the heads along x, or grouping them by XCD, measured 3-6 % slower -- round 1, git history)
-    a.il = 0;
     const dim3 grid(nblk, nprob), block(64 * nw);
     const int tn = a.M / (32 * nw);
     // diagnostic timer (tdmpc_profile_begin cfg 4 + mode): HIP events around matching chain launches
-    Profiler& pf = g_prof;
     // (t = 0 steps with the z0c first layer do less than the algorithmic work: not timed, so the roofline's
     // achieved rate is not flattered by them)
-    const bool prof = pf.armed && pf.cfg == 4 + mode && pf.n + 2 <= pf.cap && (pf.rows == 0 || a.rows == pf.rows) &&
-                      a.z0c == nullptr;
+    Profiler& pf = g_prof;
+    const bool prof = prof_armed() && pf.cfg == 4 + mode && (pf.rows == 0 || a.rows == pf.rows) && a.z0c == nullptr;
     if (prof) {
         static const char* mname[3] = {"CH_STEP", "CH_PI", "CH_Q"};
         snprintf(pf.kernel, sizeof pf.kernel, "%s<%s%s>", a.rb == 16 ? "chain16_kernel" : "chain_kernel", mname[mode],
                  a.x6 ? ", x6" : ", f32");
-        HIPCHK(hipEventRecord(pf.ev[pf.n], s));
     }
+    HIPCHK(prof_begin(prof, s));
+    const bool x6 = a.x6 != 0;
+    bool done = false;
     if (a.rb == 16) {
         const int nt = a.M / 128;
-#define CHAIN16_LAUNCH(MODE, NT) \
-        if (mode == MODE && nt == NT) { \
-            if (a.x6 && NT == 4) hipLaunchKernelGGL((chain16_kernel<MODE, 4, 4, 4, 1>), grid, block, lds, s, a); \
-            else hipLaunchKernelGGL((chain16_kernel<MODE, NT>), grid, block, lds, s, a); \
-            HIPCHK(hipGetLastError()); \
-            if (prof) { \
-                HIPCHK(hipEventRecord(pf.ev[pf.n + 1], s)); \
-                pf.n += 2; \
-                pf.flops += 2.0 * a.rows * chain_macs_per_row(mode, a, nprob); \
-            } \
-            return 0; \
+#define CHAIN16_LAUNCH(MODE, NT, D, D3, X6) \
+        if (!done && mode == MODE && nt == NT && x6 == (X6 != 0)) { \
+            hipLaunchKernelGGL((chain16_kernel<MODE, NT, D, D3, X6>), grid, block, lds, s, a); \
+            done = true; \
         }
-        CHAIN16_LAUNCH(CH_STEP, 2) CHAIN16_LAUNCH(CH_STEP, 4) CHAIN16_LAUNCH(CH_PI, 2) CHAIN16_LAUNCH(CH_PI, 4)
-        CHAIN16_LAUNCH(CH_Q, 2) CHAIN16_LAUNCH(CH_Q, 4)
+        CHAIN16_FOR_EACH(CHAIN16_LAUNCH)
 #undef CHAIN16_LAUNCH
-        snprintf(g_err, sizeof g_err, "chain16: unsupported mode %d / M %d", mode, a.M);
+    } else {
+#define CHAIN_LAUNCH(MODE, TN, NW, D, D3, X6) \
+        if (!done && mode == MODE && tn == TN && nw == NW && x6 == (X6 != 0)) { \
+            hipLaunchKernelGGL((chain_kernel<MODE, TN, NW, D, D3, X6>), grid, block, lds, s, a); \
+            done = true; \
+        }
+        CHAIN_FOR_EACH(CHAIN_LAUNCH)
+#undef CHAIN_LAUNCH
+    }
+    if (!done) {
+        snprintf(g_err, sizeof g_err, "%s: unsupported mode %d / M %d", a.rb == 16 ? "chain16" : "chain", mode, a.M);
         return TDMPC_E_DIMS;
     }
-#define CHAIN_LAUNCH(MODE, TN) \
-    if (mode == MODE && tn == TN) { \
-        if (a.x6 == 3 && TN == 4 && nw == 4) hipLaunchKernelGGL((chain_kernel<MODE, 4, 4, 2, 2, 1>), grid, block, lds, s, a); \
-        else if (a.x6 && TN == 2) hipLaunchKernelGGL((chain_kernel<MODE, 2, 8, 2, X6_D3, 1>), grid, block, lds, s, a); \
-        else if (nw == 16 && TN == 1) hipLaunchKernelGGL((chain_kernel<MODE, 1, 16>), grid, block, lds, s, a); \
-        else hipLaunchKernelGGL((chain_kernel<MODE, TN>), grid, block, lds, s, a); \
-        HIPCHK(hipGetLastError()); \
-        if (prof) { \
-            HIPCHK(hipEventRecord(pf.ev[pf.n + 1], s)); \
-            pf.n += 2; \
-            pf.flops += 2.0 * a.rows * chain_macs_per_row(mode, a, nprob); \
-        } \
-        return 0; \
-    }
-    CHAIN_LAUNCH(CH_STEP, 1) CHAIN_LAUNCH(CH_STEP, 2) CHAIN_LAUNCH(CH_STEP, 4)
-    CHAIN_LAUNCH(CH_PI, 1) CHAIN_LAUNCH(CH_PI, 2) CHAIN_LAUNCH(CH_PI, 4)
-    CHAIN_LAUNCH(CH_Q, 1) CHAIN_LAUNCH(CH_Q, 2) CHAIN_LAUNCH(CH_Q, 4)
-#undef CHAIN_LAUNCH
-    snprintf(g_err, sizeof g_err, "chain: unsupported mode %d / M %d", mode, a.M);
-    return TDMPC_E_DIMS;
+    HIPCHK(hipGetLastError());
+    HIPCHK(prof_end(prof, s, 2.0 * a.rows * chain_macs_per_row(mode, a, nprob)));
+    return 0;
 }
 
 LinArgs args0() {
@@ -3592,21 +3596,6 @@ bool use_chain(const Ctx& c, int rows, int nprob, int kind) {
     return c.path != TDMPC_PATH_AUTO || (th > 0 && (rows + 31) / 32 * nprob >= th);
 }
 
-// 16-wave 32-row chain workgroups: M = 512 (TN = 1), last-layer items <= 32 within the activation block.
-bool chain_nw16_ok(const Layout& w) {
-    if (w.M != 512) return false;
-    const size_t hfl = (size_t)std::max((int)rup(w.Kx, 16), w.M) * 32;
-    for (int n3 : {w.Lr, w.Ar}) {
-        const int nb3 = n3 / 32, ks = nb3 >= 16 ? 1 : 16 / nb3, items = nb3 * ks;
-        if (items > 32 || (size_t)items * 1024 > hfl || (w.M / 8) % ks) return false;
-    }
-    const int pmax = std::max(chain_param_floats(CH_Q, w.M, 0), chain_param_floats(CH_STEP, w.M, std::max(w.Lr, w.Ar)));
-    return (hfl + 1024 + pmax) * 4 <= 160 * 1024;
-}
-
-// Waves per 32-row chain workgroup (TDMPC_CHAIN_NW: 8 or 16; 16 needs M = 512).
-int chain_nw() { return 8; }
-
 // x6 chain kernels (fp32 products from a three-way bf16 split, chain_kernel<..., X6>) for 32-row chain launches:
 // forced by TDMPC_PATH_CHAIN_X6, the default of the auto / chain paths (TDMPC_X6=0 turns it off there); the
 // chain32 / chain16 paths keep the exact f32 MFMA. M = 512 only (the one instantiated width). Measured on MI355X
@@ -3632,7 +3621,7 @@ int use_x6(const Ctx& c) {
 // fragments serve twice the rows; measured on MI355X, humanoid: 57.5 vs 61 us for the 256-workgroup B = 8
 // step, 99 vs 114 us at B = 16, and 16-row blocks lose on the 192-workgroup pi launch too), else 16-row
 // blocks, which double the workgroups of a narrow launch (B = 4 step: 36.7 us vs 56 us on 128 32-row
-// workgroups). TDMPC_CHAIN_RB forces 16 or 32 for experiments.
+// workgroups). TDMPC_PATH_CHAIN16 / TDMPC_PATH_CHAIN32 force 16 / 32.
 int chain_rb(const Ctx& c, int rows, int nprob) {
     if (!chain16_shape_ok(c.w) || c.path == TDMPC_PATH_CHAIN32 || c.path == TDMPC_PATH_CHAIN_X6 ||
         c.path == TDMPC_PATH_WIDE)
@@ -3652,7 +3641,7 @@ ChainArgs chain0(const Ctx& c, int rows, RowMap map, int t, int K1, int q1, int 
     // head's noise prefetch (two quads per thread) needs Ap / 4 * 32 <= 512, and the last layer's 32-column blocks
     // (at most four per wave) Lr, Ar <= 512; otherwise mode 1
     if (a.x6 == 3 && (c.w.Ap / 4 * 32 > 512 || std::max(c.w.Lr, c.w.Ar) > 4 * 4 * 32)) a.x6 = 1;
-    a.nw = a.x6 == 3 ? 4 : a.rb == 32 && !a.x6 && chain_nw() == 16 && chain_nw16_ok(c.w) ? 16 : 8;
+    a.nw = a.x6 == 3 ? 4 : 8;
     // activation block: fp32 [K/4][rb][4]
     a.hfl = std::max((int)rup(c.Kx, 32), c.M) * a.rb;
     a.X = Xt(c, t); a.x_ts = (long)c.Kx * 32;
@@ -3664,8 +3653,8 @@ Opnd hop(const float* H, const Ctx& c, int q0) { return Opnd{H, (long)2 * c.M * 
 Outp hout(float* H, const Ctx& c, int q0) { return Outp{H, (long)2 * c.M * 32, q0}; }
 Opnd wop(const Ctx& c, size_t off, int K) { return Opnd{c.pw + off, (long)K * 32, 0}; }
 
-// split_step_kernel for a step launch: auto where the chain kernels are not used (narrow launches, TDMPC_SPLIT=0
-// disables), forced by TDMPC_PATH_SPLIT; M = 512 (NT = 4), the rows fit the partial buffers, LDS fits.
+// split_step_kernel for a step launch: auto where the chain kernels are not used (narrow launches), forced by
+// TDMPC_PATH_SPLIT; M = 512 (NT = 4), the rows fit the partial buffers, LDS fits.
 bool use_split(const Ctx& c, int rows) {
     const Layout& w = c.w;
     if (w.M != 512 || rows > c.k.split_rows || (size_t)split_lds_floats(w.Kx, w.M) * 4 > 64 * 1024) return false;
@@ -3733,6 +3722,12 @@ unsigned long long* g_p1_stamps = nullptr;   // tdmpc_debug_plan1_stamps (diagno
 int wide_g1(const Ctx& c, bool z0c) {   // first-layer 32-k groups the kernel runs
     return (int)rup(z0c ? z0c_k1c(c) : c.Kx, 32) / 32;
 }
+bool wide_instance(int g1, int nb3, int mode) {
+#define WIDE_HAS(G1, NB3, MODE) if (g1 == G1 && nb3 == NB3 && mode == (MODE)) return true;
+    WIDE_FOR_EACH(WIDE_HAS)
+#undef WIDE_HAS
+    return false;
+}
 bool use_wide(const Ctx& c, int rows, const RowMap& map, bool z0c) {
     static const int en = [] { const char* e = getenv("TDMPC_WIDE"); return e ? atoi(e) : 1; }();
     if (c.w.M != 512 || !use_x6(c) || !num_cus()) return false;
@@ -3740,9 +3735,9 @@ bool use_wide(const Ctx& c, int rows, const RowMap& map, bool z0c) {
     if (c.path != TDMPC_PATH_WIDE && !en) return false;
     if (rows % 16 || map.G % 16 || map.S % 16 || map.O % 16) return false;   // a wave's 16 rows in one X panel block
     if (z0c && map.G % 128) return false;   // the per-env first-layer bias is per workgroup
-    const int g1 = wide_g1(c, z0c), nb3 = (int)rup(c.w.L, 16) / 16;
-    const bool inst = (g1 <= 5 && (nb3 == 4 || nb3 == 7)) || (nb3 == 32 && (g1 == 1 || g1 == 17));
-    if (!inst) return false;
+    // every mode launch_wide() can ask for has an instance: x streamed from g1 > 5 on, h2 out only on a fold layout
+    const int g1 = wide_g1(c, z0c), nb3 = (int)rup(c.w.L, 16) / 16, mode = g1 > 5 ? WS_XS : 0;
+    if (!wide_instance(g1, nb3, mode) || (c.w.fold && !wide_instance(g1, nb3, mode | WS_OUTH))) return false;
     return c.path == TDMPC_PATH_WIDE || (rows + 127) / 128 * 2 >= num_cus();
 }
 // the folded first layer for a plan's sampled-row rollout (latent_dim == mlp_dim; TDMPC_FOLD=0 turns it off)
@@ -3785,13 +3780,13 @@ int launch_wide(const Ctx& c, int t, int rows, RowMap map, float disc, int first
     // diagnostic timer (tdmpc_profile_begin cfg 4: the step kernel); t = 0 launches with the z0c first layer are not
     // timed (less than the algorithmic work), as in launch_chain
     Profiler& pf = g_prof;
-    const bool prof = pf.armed && pf.cfg == 4 + CH_STEP && pf.n + 2 <= pf.cap && (pf.rows == 0 || rows == pf.rows) && !z0c;
+    const bool prof = prof_armed() && pf.cfg == 4 + CH_STEP && (pf.rows == 0 || rows == pf.rows) && !z0c;
     if (prof) {
         if (mode) snprintf(pf.kernel, sizeof pf.kernel, "wide_step_kernel<%d, %d, %s%s%s>", g1, nb3,
                            mode & WS_XS ? "XS" : "", mode == (WS_XS | WS_OUTH) ? "|" : "", mode & WS_OUTH ? "OUTH" : "");
         else snprintf(pf.kernel, sizeof pf.kernel, "wide_step_kernel<%d, %d>", g1, nb3);
-        HIPCHK(hipEventRecord(pf.ev[pf.n], c.s));
     }
+    HIPCHK(prof_begin(prof, c.s));
     bool done = false;
 #define WIDE_LAUNCH(G1, NB3, MODE) \
     if (!done && g1 == G1 && nb3 == NB3 && mode == (MODE)) { \
@@ -3802,12 +3797,42 @@ int launch_wide(const Ctx& c, int t, int rows, RowMap map, float disc, int first
 #undef WIDE_LAUNCH
     if (!done) { snprintf(g_err, sizeof g_err, "wide step: no instance for G1 %d NB3 %d mode %d", g1, nb3, mode); return TDMPC_E_DIMS; }
     HIPCHK(hipGetLastError());
-    if (prof) {
-        HIPCHK(hipEventRecord(pf.ev[pf.n + 1], c.s));
-        pf.n += 2;
-        const double K1 = w.L + w.A;   // (executed products: WS_OUTH launches skip layer 3)
-        pf.flops += 2.0 * rows * (2 * (K1 * M + (double)M * M) + (outh ? 0.0 : (double)M * w.L) + M);
+    const double K1 = w.L + w.A;   // (executed products: WS_OUTH launches skip layer 3)
+    HIPCHK(prof_end(prof, c.s, 2.0 * rows * (2 * (K1 * M + (double)M * M) + (outh ? 0.0 : (double)M * w.L) + M)));
+    return 0;
+}
+
+// bf16 per head (M rows) of a first layer over [a|z] in the x6 layout: W1X, WQ1X and their folded forms
+size_t x6_w1_rows_stride(const Ctx& c) { return (size_t)(c.M / 32) * (rup(c.Kx, 16) / 16) * 1536; }
+
+// The first two layers of TOLD.next's dynamics (p[0]) and reward (p[1]) heads (pi_prob: of pi), for the chain and split kernels
+void step_probs(const Ctx& c, ChainProb (&p)[2], bool x6) {
+    const Layout& w = c.w;
+    ChainProb& d = p[0];
+    d.W1 = c.pw + w.w1x; d.b1 = c.pw + w.b1x; d.W2 = c.pw + w.w2d; d.b2 = c.pw + w.b2d;
+    ChainProb& r = p[1];
+    r.W1 = c.pw + w.w1x + (size_t)c.M * c.Kx; r.b1 = c.pw + w.b1x + c.M; r.W2 = c.pw + w.w2r; r.b2 = c.pw + w.b2r;
+    r.w3v = c.pw + w.w3r;
+    if (x6) {
+        d.X1 = x6p(c, X6_W1X); r.X1 = d.X1 + x6_w1_rows_stride(c);
+        d.X2 = x6p(c, X6_W2D); r.X2 = x6p(c, X6_W2R);
     }
+}
+void pi_prob(const Ctx& c, ChainProb& p, bool x6) {
+    const Layout& w = c.w;
+    p.W1 = c.pw + w.wp1; p.b1 = c.pw + w.bp1; p.W2 = c.pw + w.wp2; p.b2 = c.pw + w.bp2;
+    if (x6) { p.X1 = x6p(c, X6_WP1); p.X2 = x6p(c, X6_WP2); }
+}
+
+// split_step_kernel over a.rows rows for `heads` heads (2: dynamics + reward, 1: pi)
+int launch_split(const Ctx& c, const SplitArgs& a, int heads, bool x6) {
+    const dim3 grid((a.rows + 15) / 16, SPLIT_S, heads);
+    const size_t lds = (size_t)split_lds_floats(a.K1, a.M) * 4;
+#define SPLIT_LAUNCH(NT, D, X6) \
+    if (a.M == 128 * NT && x6 == (X6 != 0)) hipLaunchKernelGGL((split_step_kernel<NT, D, X6>), grid, dim3(512), lds, c.s, a);
+    SPLIT_FOR_EACH(SPLIT_LAUNCH)
+#undef SPLIT_LAUNCH
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -3849,17 +3874,10 @@ int step_next(const Ctx& c, int t, int rows, RowMap map, float disc, int first, 
     }
     if (use_chain(c, rows, 2, CK_STEP)) {
         ChainArgs a = chain0(c, rows, map, t, c.Kx, 0, 2);
-        ChainProb& d = a.p[0];
-        d.W1 = c.pw + w.w1x; d.b1 = c.pw + w.b1x; d.W2 = c.pw + w.w2d; d.b2 = c.pw + w.b2d;
-        ChainProb& r = a.p[1];
-        r.W1 = c.pw + w.w1x + (size_t)M * c.Kx; r.b1 = c.pw + w.b1x + M; r.W2 = c.pw + w.w2r; r.b2 = c.pw + w.b2r;
-        r.w3v = c.pw + w.w3r; r.b3v = c.pw + w.b3r;
+        step_probs(c, a.p, a.x6 != 0);
+        a.p[1].b3v = c.pw + w.b3r;
         a.W3 = c.pw + w.w3d; a.b3 = c.pw + w.b3d; a.n3 = w.Lr; a.nvalid = w.L; a.nstore = w.Lp;
-        if (a.x6) {
-            const size_t rb1 = (size_t)(M / 32) * (rup(c.Kx, 16) / 16) * 1536;   // bf16 per M rows of x6 W1
-            d.X1 = x6p(c, X6_W1X); r.X1 = x6p(c, X6_W1X) + rb1;
-            d.X2 = x6p(c, X6_W2D); r.X2 = x6p(c, X6_W2R); a.X3 = x6p(c, X6_W3D);
-        }
+        if (a.x6) a.X3 = x6p(c, X6_W3D);
         a.Xo = Xt(c, t + 1); a.out_q0 = w.Ap / 4;
         a.G = c.k.G; a.rlast = c.k.rlast; a.disc = disc; a.first = first; a.last = last;
         if (t == 0 && c.z0c_ready && map.G % 32 == 0) { a.z0c = c.k.z0c; a.z0_G = map.G; a.k1c = z0c_k1c(c); }
@@ -3869,9 +3887,8 @@ int step_next(const Ctx& c, int t, int rows, RowMap map, float disc, int first, 
                 return TDMPC_E_DIMS;
             }
             if (t >= 1) {
-                const size_t rb1 = (size_t)(M / 32) * (rup(c.Kx, 16) / 16) * 1536;
-                d.X1 = (const unsigned short*)(c.pw + w.fw1_x6); r.X1 = d.X1 + rb1;
-                d.b1 = c.pw + w.bfw; r.b1 = c.pw + w.bfw + M;
+                a.p[0].X1 = (const unsigned short*)(c.pw + w.fw1_x6); a.p[1].X1 = a.p[0].X1 + x6_w1_rows_stride(c);
+                a.p[0].b1 = c.pw + w.bfw; a.p[1].b1 = c.pw + w.bfw + M;
             }
             a.outh = 1;
         }
@@ -3884,27 +3901,17 @@ int step_next(const Ctx& c, int t, int rows, RowMap map, float disc, int first, 
         memset(&a, 0, sizeof a);
         a.rows = rows; a.M = M; a.K1 = c.Kx; a.q1 = 0; a.amap = map;
         a.X = Xt(c, t); a.x_ts = (long)c.Kx * 32;
-        ChainProb& d = a.p[0];
-        d.W1 = c.pw + w.w1x; d.b1 = c.pw + w.b1x; d.W2 = c.pw + w.w2d; d.b2 = c.pw + w.b2d;
-        ChainProb& r = a.p[1];
-        r.W1 = c.pw + w.w1x + (size_t)M * c.Kx; r.b1 = c.pw + w.b1x + M; r.W2 = c.pw + w.w2r; r.b2 = c.pw + w.b2r;
-        r.w3v = c.pw + w.w3r;
+        const bool x6 = use_x6(c) != 0;
+        step_probs(c, a.p, x6);
         a.W3 = c.pw + w.w3d; a.n3 = w.Lr;
+        if (x6) a.X3 = x6p(c, X6_W3D);
         a.zpart = c.k.zpart + par * zs; a.rpart = c.k.rpart_s + par * rs; a.prow = c.k.split_rows;
         a.b3d = c.pw + w.b3d; a.b3r = c.pw + w.b3r; a.L = w.L; a.Lp = w.Lp; a.zq0 = w.Ap / 4;
-        const bool x6 = use_x6(c) != 0;
-        if (x6) {
-            d.X1 = x6p(c, X6_W1X); r.X1 = x6p(c, X6_W1X) + (size_t)(M / 32) * (rup(c.Kx, 16) / 16) * 1536;
-            d.X2 = x6p(c, X6_W2D); r.X2 = x6p(c, X6_W2R); a.X3 = x6p(c, X6_W3D);
-        }
         if (c.split_pend) {   // the previous step's finish, folded into this launch's staging
             a.zin = c.k.zpart + (1 - par) * zs; a.rin = c.k.rpart_s + (1 - par) * rs;
             a.Xw = Xt(c, t); a.G = c.k.G; a.disc_in = c.split_disc; a.first_in = c.split_first;
         }
-        const size_t lds = (size_t)split_lds_floats(c.Kx, M) * 4;
-        if (x6) hipLaunchKernelGGL((split_step_kernel<4, 4, 1>), dim3((rows + 15) / 16, SPLIT_S, 2), dim3(512), lds, c.s, a);
-        else hipLaunchKernelGGL((split_step_kernel<4>), dim3((rows + 15) / 16, SPLIT_S, 2), dim3(512), lds, c.s, a);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch_split(c, a, 2, x6))) return rc;
         c.split_pend = 0;
         c.split_par = 1 - par;
         if (defer && !last) {
@@ -3962,9 +3969,9 @@ int policy(const Ctx& c, int t, int rows, RowMap map, const float* eps, long eps
     if (use_chain(c, rows, 1, CK_PI)) {
         ChainArgs a = chain0(c, rows, map, t, w.Lp, w.Ap / 4, 1);
         ChainProb& p = a.p[0];
-        p.W1 = c.pw + w.wp1; p.b1 = c.pw + w.bp1; p.W2 = c.pw + w.wp2; p.b2 = c.pw + w.bp2;
+        pi_prob(c, p, a.x6 != 0);
         a.W3 = c.pw + w.wp3; a.b3 = c.pw + w.bp3; a.n3 = w.Ar; a.nvalid = w.A; a.nstore = w.Ap;
-        if (a.x6) { p.X1 = x6p(c, X6_WP1); p.X2 = x6p(c, X6_WP2); a.X3 = x6p(c, X6_WP3); }
+        if (a.x6) a.X3 = x6p(c, X6_WP3);
         if (fold) { p.X1 = (const unsigned short*)(c.pw + w.fpi_x6); p.b1 = c.pw + w.fpi_b; }
         a.Xo = Xt(c, t); a.out_q0 = 0;
         a.eps = eps; a.eps_G = eps_G; a.eps_env = eps_env; a.eps_off = eps_off; a.A = w.A;
@@ -3978,18 +3985,12 @@ int policy(const Ctx& c, int t, int rows, RowMap map, const float* eps, long eps
         memset(&a, 0, sizeof a);
         a.rows = rows; a.M = M; a.K1 = w.Lp; a.q1 = w.Ap / 4; a.amap = map;
         a.X = Xt(c, t); a.x_ts = (long)c.Kx * 32;
-        ChainProb& p = a.p[0];
-        p.W1 = c.pw + w.wp1; p.b1 = c.pw + w.bp1; p.W2 = c.pw + w.wp2; p.b2 = c.pw + w.bp2;
+        const bool x6 = use_x6(c) != 0;
+        pi_prob(c, a.p[0], x6);
         a.W3 = c.pw + w.wp3; a.n3 = w.Ar;
+        if (x6) a.X3 = x6p(c, X6_WP3);
         a.zpart = c.k.zpart; a.rpart = c.k.rpart_s; a.prow = c.k.split_rows;
-        const size_t lds = (size_t)split_lds_floats(w.Lp, M) * 4;
-        if (use_x6(c)) {
-            p.X1 = x6p(c, X6_WP1); p.X2 = x6p(c, X6_WP2); a.X3 = x6p(c, X6_WP3);
-            hipLaunchKernelGGL((split_step_kernel<4, 4, 1>), dim3((rows + 15) / 16, SPLIT_S, 1), dim3(512), lds, c.s, a);
-        } else {
-            hipLaunchKernelGGL((split_step_kernel<4>), dim3((rows + 15) / 16, SPLIT_S, 1), dim3(512), lds, c.s, a);
-        }
-        HIPCHK(hipGetLastError());
+        if ((rc = launch_split(c, a, 1, x6))) return rc;
         SplitPiArgs f;
         memset(&f, 0, sizeof f);
         f.rows = rows; f.amap = map; f.part = c.k.zpart; f.prow = c.k.split_rows; f.n3 = w.Ar; f.A = w.A;
@@ -4062,16 +4063,19 @@ int policy_from_mu(const Ctx& c, int rows, RowMap map, const float* eps, long ep
 // prep_kernel launch: candidates of CEM iteration `iter` for all H steps (if noise) and, with z0, the
 // latent columns of X_0 for every row; with pm, the policy rows' terminal redraw of that iteration in the same launch
 // (it reads only the cached pi mean and the noise, so it need not wait for the rollout).
-int prep(const Ctx& c, const float* noise, int iter, const float* z0, const PiMuArgs* pm = nullptr) {
+// sample_rows: the first rows of each env's block that get candidates (N; an iCEM iteration's own count), their noise
+// at eps_off of the env's eps_env floats
+int prep_launch(const Ctx& c, const float* noise, int sample_rows, long eps_env, long eps_off, const float* z0,
+                const PiMuArgs* pm) {
     PrepArgs a;
     memset(&a, 0, sizeof a);
     a.X = c.k.X; a.x_stride = c.k.x_stride; a.Kx = c.Kx; a.apq = c.w.Ap / 4; a.lpq = c.w.Lp / 4;
-    a.B = c.B; a.N = c.N; a.T = c.T; a.H = c.H; a.A = c.A;
+    a.B = c.B; a.N = sample_rows; a.T = c.T; a.H = c.H; a.A = c.A;
     a.mean = c.k.mean; a.stdv = c.k.stdv; a.mstride = c.d->max_horizon * c.A;
-    a.eps = noise; a.eps_env = c.eps_env; a.eps_off = c.eps_cem_off + (long)iter * c.eps_iter;
+    a.eps = noise; a.eps_env = eps_env; a.eps_off = eps_off;
     a.z0 = z0;
     a.n_zq = z0 ? (long)c.B * a.lpq * c.T : 0;
-    a.n_sq = noise ? (long)c.B * c.H * a.apq * c.N : 0;
+    a.n_sq = noise ? (long)c.B * c.H * a.apq * sample_rows : 0;
     if (pm) {
         a.pm = *pm;
         a.n_pm = (long)pm->rows * (pm->Ap / 4);
@@ -4082,6 +4086,9 @@ int prep(const Ctx& c, const float* noise, int iter, const float* z0, const PiMu
     hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(256), 0, c.s, a);
     HIPCHK(hipGetLastError());
     return 0;
+}
+int prep(const Ctx& c, const float* noise, int iter, const float* z0, const PiMuArgs* pm = nullptr) {
+    return prep_launch(c, noise, c.N, c.eps_env, c.eps_cem_off + (long)iter * c.eps_iter, z0, pm);
 }
 
 // helper.q for both heads over `rows` rows of X_H mapped by `map`, on the chain kernel: q_p per row into k.qv
@@ -4104,11 +4111,11 @@ int q_chain(const Ctx& c, int rows, RowMap map, const float* X = nullptr, float*
         p.g2 = c.pw + w.g2 + q * M; p.be2 = c.pw + w.be2 + q * M;
         p.w3v = c.pw + w.wq3 + q * M; p.b3v = c.pw + w.bq3 + q;
         if (a.x6) {
-            p.X1 = x6p(c, X6_WQ1X) + (size_t)q * (M / 32) * (rup(c.Kx, 16) / 16) * 1536;
+            p.X1 = x6p(c, X6_WQ1X) + q * x6_w1_rows_stride(c);
             p.X2 = x6p(c, X6_WQ2) + (size_t)q * (M / 32) * (M / 16) * 1536;
         }
         if (fold) {   // the rows' latent columns hold h2_{H-1}: [Wq1a | Wq1z W3], bq1 + Wq1z b3
-            p.X1 = (const unsigned short*)(c.pw + w.fq_x6) + (size_t)q * (M / 32) * (rup(c.Kx, 16) / 16) * 1536;
+            p.X1 = (const unsigned short*)(c.pw + w.fq_x6) + q * x6_w1_rows_stride(c);
             p.b1 = c.pw + w.fq_b + q * M;
         }
     }
@@ -4192,13 +4199,11 @@ int launch_wide_heads(const Ctx& c, const WHJob* jobs, int nj, const float* eps,
     const int g1p = wh_g1p(c), nb3 = wh_nb3p(c), nst = w.nsr / 16;
     // diagnostic timer (tdmpc_profile_begin cfg 4 + CH_Q: the all-Q launch, cfg 4 + CH_PI: the mixed one)
     Profiler& pf = g_prof;
-    const bool prof = pf.armed && pf.cfg == 4 + (allq ? CH_Q : CH_PI) && pf.n + 2 <= pf.cap &&
-                      (pf.rows == 0 || jobs[0].rows == pf.rows);
-    if (prof) {
+    const bool prof = prof_armed() && pf.cfg == 4 + (allq ? CH_Q : CH_PI) && (pf.rows == 0 || jobs[0].rows == pf.rows);
+    if (prof)
         snprintf(pf.kernel, sizeof pf.kernel, "wide_heads_kernel<%d, %d, %d, %d> (%s)", g1p, nb3, g1q, nst,
                  allq ? "Q1 + Q2" : "pi + Q1 + Q2 of the policy rows");
-        HIPCHK(hipEventRecord(pf.ev[pf.n], c.s));
-    }
+    HIPCHK(prof_begin(prof, c.s));
     bool done = false;
 #define WH_LAUNCH(G1P, NB3P, G1Q, NSTQ) \
     if (!done && g1p == G1P && nb3 == NB3P && g1q == G1Q && nst == NSTQ) { \
@@ -4210,11 +4215,7 @@ int launch_wide_heads(const Ctx& c, const WHJob* jobs, int nj, const float* eps,
 #undef WH_LAUNCH
     if (!done) { snprintf(g_err, sizeof g_err, "wide heads: no instance"); return TDMPC_E_DIMS; }
     HIPCHK(hipGetLastError());
-    if (prof) {
-        HIPCHK(hipEventRecord(pf.ev[pf.n + 1], c.s));
-        pf.n += 2;
-        pf.flops += flops;
-    }
+    HIPCHK(prof_end(prof, c.s, flops));
     return 0;
 }
 
@@ -4335,15 +4336,11 @@ int encode(const Ctx& c, const void* obs, int obs_is_u8, int batch, const float*
             if (toy > 0) {
                 const size_t lds = (rup((size_t)cin * (2 * (toy - 1) + ks[i]) * hi, 4) + (size_t)w.nch * cin * ks[i] * ks[i]) * 4;
                 const dim3 grid((ho + toy - 1) / toy, batch);
-                if (px == 4)
-                    hipLaunchKernelGGL(conv_tile_kernel<4>, grid, dim3(256), lds, c.s, in, in_u8, in_bs, cin, hi, out,
-                                       (long)act, w.nch, ho, ks[i], toy, pw + w.cwt[i], pw + w.cb[i]);
-                else if (px == 2)
-                    hipLaunchKernelGGL(conv_tile_kernel<2>, grid, dim3(256), lds, c.s, in, in_u8, in_bs, cin, hi, out,
-                                       (long)act, w.nch, ho, ks[i], toy, pw + w.cwt[i], pw + w.cb[i]);
-                else
-                    hipLaunchKernelGGL(conv_tile_kernel<1>, grid, dim3(256), lds, c.s, in, in_u8, in_bs, cin, hi, out,
-                                       (long)act, w.nch, ho, ks[i], toy, pw + w.cwt[i], pw + w.cb[i]);
+#define CONV_LAUNCH(PX) \
+                if (px == PX) hipLaunchKernelGGL(conv_tile_kernel<PX>, grid, dim3(256), lds, c.s, in, in_u8, in_bs, cin, hi, \
+                                                 out, (long)act, w.nch, ho, ks[i], toy, pw + w.cwt[i], pw + w.cb[i]);
+                CONV_TILE_FOR_EACH(CONV_LAUNCH)
+#undef CONV_LAUNCH
             } else {
                 hipLaunchKernelGGL(conv_relu_kernel, dim3((total + 255) / 256, batch), dim3(256), 0, c.s, in, in_u8,
                                    in_bs, cin, hi, out, (long)act, w.nch, ho, ks[i], pw + w.cw[i], pw + w.cb[i]);
@@ -4379,9 +4376,10 @@ bool plan1_resident(const Ctx& c) {
     if (ok_lds[ks] == lds) return true;
     if (bad_lds[ks] == lds) return false;
     int per_cu = 0;
-    const hipError_t e = ks == 0
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plan1_kernel<4>, P1_NT, lds)
-        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plan1_kernel<6>, P1_NT, lds);
+    hipError_t e = hipErrorInvalidValue;
+#define PLAN1_OCC(KS) if (p1_ks(c.w) == KS) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plan1_kernel<KS>, P1_NT, lds);
+    PLAN1_FOR_EACH(PLAN1_OCC)
+#undef PLAN1_OCC
     const bool ok = e == hipSuccess && (long)per_cu * num_cus() >= P1_NG * P1_WPG;
     (ok ? ok_lds : bad_lds)[ks] = lds;
     return ok;
@@ -4448,8 +4446,10 @@ int plan1_launch(const Ctx& c, const tdmpc_plan_params* prm, const float* noise,
                        P1_NG * 64 + 64);
     HIPCHK(hipGetLastError());
     const size_t lds = p1_lds_bytes(c.H, a.K, w.A, c.T);
-    if (p1_ks(w) == 4) hipLaunchKernelGGL(plan1_kernel<4>, dim3(P1_NG * P1_WPG), dim3(P1_NT), lds, c.s, a);
-    else hipLaunchKernelGGL(plan1_kernel<6>, dim3(P1_NG * P1_WPG), dim3(P1_NT), lds, c.s, a);
+#define PLAN1_LAUNCH(KS) \
+    if (p1_ks(w) == KS) hipLaunchKernelGGL(plan1_kernel<KS>, dim3(P1_NG * P1_WPG), dim3(P1_NT), lds, c.s, a);
+    PLAN1_FOR_EACH(PLAN1_LAUNCH)
+#undef PLAN1_LAUNCH
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -4479,464 +4479,37 @@ int setup_ctx(Ctx& c, const tdmpc_dims* d, const void* packed, void* ws, size_t 
     return init_attrs();
 }
 
-// ---- the fused weight pack (tdmpc_pack_weights): ONE launch writes every region of the packed buffer -- fp32
-// copies, transposes, weight panels, their x6 and x6q bf16 planes -- straight from the reference's tensors (the
-// learner passes views of its flat parameter buffer, so a post-update repack is one kernel, capturable into the
-// update's HIP graph). Each job's padded region is written whole (zeros where the layout pads), so no memset.
-// The x6 / x6q planes are split from the source tensors directly (the same values as from the fp32 panel).
-struct PackSrc {                 // a weight panel's source: rows [0, r0) of p0, then [r0, r0 + r1) of p1
-    const float* p0; const float* p1;
-    int r0, r1, sld, ncols;      // source row length; plain map: panel column k < ncols <- source column k
-    int first;                   // first-layer map: panel [a | 0 | z | 0] <- source [z | a] (L = ncols, A below)
-    int L, A, Ap;
-};
-__host__ __device__ inline float pack_val(const PackSrc& m, int r, int k) {
-    const float* row;
-    if (r < m.r0) row = m.p0 + (size_t)r * m.sld;
-    else if (r < m.r0 + m.r1) row = m.p1 + (size_t)(r - m.r0) * m.sld;
-    else return 0.f;
-    int col;
-    if (m.first) col = k < m.A ? m.L + k : (k >= m.Ap && k < m.Ap + m.L ? k - m.Ap : -1);
-    else col = k < m.ncols ? k : -1;
-    return col < 0 ? 0.f : row[col];
-}
-enum { PJ_COPY, PJ_TRANS, PJ_PANEL, PJ_X6, PJ_X6Q };
-struct PackJob {
-    int kind;
-    int blk0;                    // first workgroup of this job in the launch
-    size_t dst;                  // float offset into the packed buffer
-    long work;                   // work items
-    const float* src; int n, rows, cols;   // COPY: n values then zeros to `work`; TRANS: [rows][cols] -> [cols][rows]
-    PackSrc m; int prow, pk;     // PANEL: [prow][pk] panel; X6 / X6Q: prow rows x pk k of the source map
-};
-static_assert(sizeof(PackJob) <= PACK_JOB_BYTES, "job-table slot");
-constexpr int PACK_WG = 256, PACK_PER = 8;   // threads per workgroup, items per thread
-// elements per item: an x6 / x6q lane's 8 values (16-B stores per plane), a panel's k quad, else one; items per
-// thread: one for those (the split and the gathered reads of 4 - 8 values already give each thread its work), else
-// PACK_PER
-__host__ __device__ constexpr int pack_per_item(int kind) { return kind == PJ_X6 || kind == PJ_X6Q ? 8 : kind == PJ_PANEL ? 4 : 1; }
-__host__ __device__ constexpr int pack_items(int kind) { return pack_per_item(kind) > 1 ? 1 : PACK_PER; }
-
-__global__ void __launch_bounds__(PACK_WG) pack_fused_kernel(PackHdr* hdr, const PackJob* jobs, int nj, float* pw,
-                                                              unsigned long long nonce, long nweights) {
-    if (hdr->nonce != nonce) {
-        // not the table this launch was issued for (the buffer was re-allocated, re-zeroed or re-keyed since): pack
-        // nothing from it, poison every weight region and raise the buffer's sticky status (plans pass it on)
-        for (long i = (long)blockIdx.x * PACK_WG + threadIdx.x; i < nweights; i += (long)gridDim.x * PACK_WG)
-            pw[i] = __builtin_nanf("");
-        if (blockIdx.x == 0 && threadIdx.x == 0)
-            __hip_atomic_fetch_or(&hdr->status, TDMPC_STATUS_PACK_STALE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    // the workgroup's job: last job whose blk0 <= blockIdx.x (binary search over the job table)
-    int lo = 0, hi = nj - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const PackJob& J = jobs[lo];
-    const int epi = pack_per_item(J.kind), ipt = pack_items(J.kind);
-    const long base = (long)(blockIdx.x - J.blk0) * PACK_WG * ipt;
-    for (int u = 0; u < ipt; ++u) {
-        const long i = (base + (long)u * PACK_WG + threadIdx.x) * epi;   // first element of the thread's item
-        if (i >= J.work) break;
-        switch (J.kind) {
-            case PJ_COPY: pw[J.dst + i] = i < J.n ? J.src[i] : 0.f; break;
-            case PJ_TRANS: {
-                const long r = i % J.rows, c = i / J.rows;   // dst[c * rows + r] = src[r * cols + c]
-                pw[J.dst + i] = J.src[r * J.cols + c];
-                break;
-            }
-            case PJ_PANEL: {   // dst index i = pidx(r, k, pk): [r / 32][k / 4][r % 32][k % 4]; the item: one k quad
-                const int rr = (i >> 2) & 31;
-                const long q = i >> 7;
-                const int kq = (int)(q % (J.pk / 4));
-                const int r = (int)(q / (J.pk / 4)) * 32 + rr, k = kq * 4;
-                *(float4*)(pw + J.dst + i) = make_float4(pack_val(J.m, r, k), pack_val(J.m, r, k + 1),
-                                                         pack_val(J.m, r, k + 2), pack_val(J.m, r, k + 3));
-                break;
-            }
-            case PJ_X6: case PJ_X6Q: {   // the item: one lane's 8 values of a block, 16 B per plane
-                const int lane = (i >> 3) & 63;
-                const long blk = i >> 9;
-                int r, k0, k1;   // values j = 0..3 at k0 + j, j = 4..7 at k1 + j - 4
-                if (J.kind == PJ_X6) {   // the x6 layout (Layout::x6): 32-row x 16-k blocks
-                    const int G = (J.pk + 15) / 16;
-                    const int g = (int)(blk % G), nb = (int)(blk / G);
-                    r = 32 * nb + (lane & 31);
-                    k0 = 16 * g + 4 * (lane >> 5);
-                    k1 = k0 + 8;
-                } else {                 // the x6q layout (Layout::x6q): 16-row x 32-k blocks
-                    const int G = (J.pk + 31) / 32;
-                    const int g = (int)(blk % G), nb = (int)(blk / G);
-                    r = 16 * nb + (lane & 15);
-                    k0 = 32 * g + 4 * (lane >> 4);
-                    k1 = k0 + 16;
-                }
-                unsigned short hv[8], mv[8], lv[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int k = (j < 4 ? k0 : k1) + (j & 3);
-                    const float x = k < J.pk && r < J.prow ? pack_val(J.m, r, k) : 0.f;
-                    __bf16 h, m, l;
-                    split3(x, h, m, l);
-                    hv[j] = __builtin_bit_cast(unsigned short, h);
-                    mv[j] = __builtin_bit_cast(unsigned short, m);
-                    lv[j] = __builtin_bit_cast(unsigned short, l);
-                }
-                auto pk8 = [](const unsigned short (&v)[8]) {
-                    return make_uint4(v[0] | (unsigned)v[1] << 16, v[2] | (unsigned)v[3] << 16, v[4] | (unsigned)v[5] << 16,
-                                      v[6] | (unsigned)v[7] << 16);
-                };
-                uint4* d = (uint4*)(pw + J.dst);   // 1 KiB per plane and block, 16 B per lane
-                d[(blk * 3 + 0) * 64 + lane] = pk8(hv);
-                d[(blk * 3 + 1) * 64 + lane] = pk8(mv);
-                d[(blk * 3 + 2) * 64 + lane] = pk8(lv);
-                break;
-            }
-        }
-    }
+// The path an entry point runs for the requested TDMPC_PATH_*, or -1 with the error text set. The retired 64-row
+// blocks (CHAIN64) run as CHAIN_X6; the persistent plan exists for whole plans only, elsewhere it is the auto path.
+int resolve_path(int path, bool whole_plan) {
+    if (path < 0 || path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return -1; }
+    if (path == TDMPC_PATH_CHAIN64) return TDMPC_PATH_CHAIN_X6;
+    return path == TDMPC_PATH_PERSIST && !whole_plan ? TDMPC_PATH_AUTO : path;
 }
 
-// ---- the folded first layer (latent_dim == mlp_dim; Layout::fold): W1z W3 and b1 + W1z b3 for both TOLD.next heads,
-// from the packed fp32 panels (w1x's z columns [2M][Ap .. Ap + L), w3d [Lr][M], b3d, b1x), fp64 sums rounded once to
-// fp32, then split into the x6q planes with the a columns of w1x in front. A step whose input latent columns hold the
-// previous step's h2 = ELU(W2 h1 + b2) computes W1 [a; W3 h2 + b3] + b1 as [W1a | W1z W3] [a; h2] + (b1 + W1z b3).
-struct FoldArgs {
-    const float* W; int Kp, zoff;          // source first layer: fp32 panel [R][Kp], z in columns [zoff, zoff + L)
-    const float* w3d; const float* b3; const float* b;   // W3 panel [Lr][M], b3 [L], the source bias [R]
-    float* fw; float* bf;                  // W_z W3 [R][M] fp32 and b + W_z b3 [R]
-    unsigned short* x6; int kind, pk;      // planes of [W_a | W_z W3] (k < zoff from W, then fw): kind 0 x6q, 1 x6
-    int M, L;
-};
-__global__ void __launch_bounds__(256) fold_gemm_kernel(const FoldArgs a) {
-    // 16 x 16 output tile per workgroup: rows i [0, R), columns j of W3 [0, M) -- tile column M / 16 is the bias
-    // column (j = M: b3)
-    __shared__ double sA[16][17], sB[16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int i0 = blockIdx.y * 16, j0 = blockIdx.x * 16;
-    const int i = i0 + ty, j = j0 + tx;
-    double acc = 0.0;
-    for (int l0 = 0; l0 < a.L; l0 += 16) {
-        const int la = l0 + tx, lb = l0 + ty;
-        sA[ty][tx] = la < a.L ? (double)a.W[pidx(i0 + ty, a.zoff + la, a.Kp)] : 0.0;
-        double b = 0.0;
-        if (lb < a.L) b = j < a.M ? (double)a.w3d[pidx(lb, j, a.M)] : (j == a.M ? (double)a.b3[lb] : 0.0);
-        sB[ty][tx] = b;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acc = fma(sA[ty][k], sB[k][tx], acc);
-        __syncthreads();
-    }
-    if (j < a.M) a.fw[(size_t)i * a.M + j] = (float)acc;
-    else if (j == a.M) a.bf[i] = (float)((double)a.b[i] + acc);
-}
-__global__ void __launch_bounds__(256) fold_split_kernel(const FoldArgs a, long work) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= work) return;
-    const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
-    const long blk = i >> 9;
-    int r, k;
-    if (a.kind == 0) {   // x6q: 16-row x 32-k blocks (the wide kernels)
-        const int G = (a.pk + 31) / 32;
-        const int g = (int)(blk % G), nb = (int)(blk / G);
-        r = 16 * nb + (lane & 15);
-        k = 32 * g + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
-    } else {             // x6: 32-row x 16-k blocks (the chain kernels)
-        const int G = (a.pk + 15) / 16;
-        const int g = (int)(blk % G), nb = (int)(blk / G);
-        r = 32 * nb + (lane & 31);
-        k = 16 * g + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3);
-    }
-    float x = 0.f;
-    if (k < a.zoff) x = a.W[pidx(r, k, a.Kp)];
-    else if (k < a.zoff + a.M && k < a.pk) x = a.fw[(size_t)r * a.M + (k - a.zoff)];
-    __bf16 h, m, l;
-    split3(x, h, m, l);
-    a.x6[(blk * 3 + 0) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, h);
-    a.x6[(blk * 3 + 1) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, m);
-    a.x6[(blk * 3 + 2) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, l);
-}
-int fold_one(const Layout& w, float* pw, hipStream_t s, size_t W, int R, int Kp, int zoff, size_t b, size_t fw,
-             size_t bf, size_t x6, int kind, int pk, bool gemm = true) {
-    FoldArgs f;
-    memset(&f, 0, sizeof f);
-    f.W = pw + W; f.Kp = Kp; f.zoff = zoff; f.w3d = pw + w.w3d; f.b3 = pw + w.b3d; f.b = pw + b;
-    f.fw = pw + fw; f.bf = pw + bf; f.x6 = (unsigned short*)(pw + x6); f.kind = kind; f.pk = pk;
-    f.M = w.M; f.L = w.L;
-    if (gemm) {
-        hipLaunchKernelGGL(fold_gemm_kernel, dim3(w.M / 16 + 1, R / 16), dim3(256), 0, s, f);
-        HIPCHK(hipGetLastError());
-    }
-    const long work = kind == 0 ? (long)(R / 16) * ((pk + 31) / 32) * 512 : (long)((R + 31) / 32) * ((pk + 15) / 16) * 512;
-    hipLaunchKernelGGL(fold_split_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, f, work);
+// z0 [B][L] -> the workspace's padded z0 [B][Lp] and the latent columns of X_0 for all T rows of every env
+int load_z0(const Ctx& c, const float* z0) {
+    const int L = c.w.L;
+    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, c.s, (unsigned*)c.k.z0, (int)((size_t)c.B * c.w.Lp));
     HIPCHK(hipGetLastError());
-    return 0;
-}
-int pack_fold(const Layout& w, float* pw, hipStream_t s) {
-    int rc, r, k;
-    // TOLD.next (both heads, the wide kernel's x6q): [W1a | W1z W3], b1 + W1z b3
-    if ((rc = fold_one(w, pw, s, w.w1x, 2 * w.M, w.Kx, w.Ap, w.b1x, w.fold_w, w.bfw, w.x6qw, 0, w.Kx))) return rc;
-    // (the same product split again into the chain kernels' x6 layout)
-    x6_shape(w, X6_W1X, &r, &k);
-    if ((rc = fold_one(w, pw, s, w.w1x, 2 * w.M, w.Kx, w.Ap, w.b1x, w.fold_w, w.bfw, w.fw1_x6, 1, k, false))) return rc;
-    // pi (chain x6): [Wp1 W3], bp1 + Wp1 b3
-    x6_shape(w, X6_WP1, &r, &k);
-    if ((rc = fold_one(w, pw, s, w.wp1, w.M, w.Lp, 0, w.bp1, w.fold_p, w.fpi_b, w.fpi_x6, 1, k))) return rc;
-    // Q1 | Q2 (chain x6): [Wq1a | Wq1z W3], bq1 + Wq1z b3
-    x6_shape(w, X6_WQ1X, &r, &k);
-    return fold_one(w, pw, s, w.wq1x, 2 * w.M, w.Kx, w.Ap, w.bq1x, w.fold_q, w.fq_b, w.fq_x6, 1, k);
+    HIPCHK(hipMemcpy2DAsync(c.k.z0, c.w.Lp * 4, z0, L * 4, L * 4, c.B, hipMemcpyDeviceToDevice, c.s));
+    return prep(c, nullptr, 0, c.k.z0);
 }
 
-// The job list of a layout and the reference tensors t (state_dict order, tdmpc_num_param_tensors of them).
-// heads_only (the DSSM planner, drnn.inc): t holds the encoder, pi, Q1 and Q2 tensors only, and the TOLD dynamics /
-// reward regions get no job.
-void pack_jobs(const Layout& w, const float* const* t, std::vector<PackJob>& jobs, bool heads_only = false) {
-    const int M = w.M, L = w.L, A = w.A;
-    auto job = [&](int kind, size_t dst, long work) -> PackJob& {
-        PackJob j;
-        memset(&j, 0, sizeof j);
-        j.kind = kind; j.dst = dst; j.work = work;
-        jobs.push_back(j);
-        return jobs.back();
-    };
-    auto cp = [&](size_t dst, const float* src, int n) {   // zero tail to the 64-float slot take() reserved
-        PackJob& j = job(PJ_COPY, dst, (long)rup(n, 64));
-        j.src = src; j.n = n;
-    };
-    auto tr = [&](size_t dst, const float* src, int rows, int cols) {
-        PackJob& j = job(PJ_TRANS, dst, (long)rows * cols);
-        j.src = src; j.rows = rows; j.cols = cols;
-    };
-    auto msrc = [&](const float* p0, const float* p1, int r0, int r1, int sld, int ncols, int first) {
-        PackSrc m;
-        memset(&m, 0, sizeof m);
-        m.p0 = p0; m.p1 = p1 ? p1 : p0; m.r0 = r0; m.r1 = r1; m.sld = sld; m.ncols = ncols; m.first = first;
-        m.L = L; m.A = A; m.Ap = w.Ap;
-        return m;
-    };
-    auto panel = [&](size_t dst, const PackSrc& m, int prow, int pk) {
-        PackJob& j = job(PJ_PANEL, dst, (long)rup(prow, 32) * pk);
-        j.m = m; j.prow = prow; j.pk = pk;
-    };
-    int i = 0;
-    if (w.modality == 0) {
-        tr(w.enc_w1t, t[i++], w.E, w.obs_dim);
-        cp(w.enc_b1, t[i++], w.E);
-        if (w.enc_norm) { cp(w.enc_lng, t[i++], w.E); cp(w.enc_lnb, t[i++], w.E); }
-        tr(w.enc_w2t, t[i++], L, w.E);
-        cp(w.enc_b2, t[i++], L);
-    } else {
-        static const int ks[4] = {7, 5, 3, 3};
-        int cin = w.img_c;
-        for (int c = 0; c < 4; ++c) {
-            const float* cw = t[i++];
-            cp(w.cw[c], cw, w.nch * cin * ks[c] * ks[c]);
-            tr(w.cwt[c], cw, w.nch, cin * ks[c] * ks[c]);
-            cp(w.cb[c], t[i++], w.nch);
-            cin = w.nch;
-        }
-        tr(w.pl_wt, t[i++], L, w.flat);
-        cp(w.pl_b, t[i++], L);
-    }
-    const int KI = L + A;
-    const float* const* dyn = t + i;        // 0.w 0.b 2.w 2.b 4.w 4.b
-    const float* const* rew = dyn + 6;
-    const float* const* pi = heads_only ? dyn : rew + 6;
-    const float* const* q1 = pi + 6;        // 0.w 0.b 1.w 1.b 3.w 3.b 4.w 4.b 6.w 6.b
-    const float* const* q2 = q1 + 10;
-    const PackSrc sW1X = msrc(dyn[0], rew[0], M, M, KI, L, 1), sW2D = msrc(dyn[2], nullptr, M, 0, M, M, 0),
-                  sW2R = msrc(rew[2], nullptr, M, 0, M, M, 0), sW3D = msrc(dyn[4], nullptr, L, 0, M, M, 0),
-                  sWP1 = msrc(pi[0], nullptr, M, 0, L, L, 0), sWP2 = msrc(pi[2], nullptr, M, 0, M, M, 0),
-                  sWP3 = msrc(pi[4], nullptr, A, 0, M, M, 0), sWQ1X = msrc(q1[0], q2[0], M, M, KI, L, 1),
-                  sWQ2 = msrc(q1[4], q2[4], M, M, M, M, 0);
-    if (!heads_only) {
-        panel(w.w1x, sW1X, 2 * M, w.Kx);
-        cp(w.b1x, dyn[1], M); cp(w.b1x + M, rew[1], M);
-        panel(w.w2d, sW2D, M, M); cp(w.b2d, dyn[3], M);
-        panel(w.w3d, sW3D, w.Lr, M); cp(w.b3d, dyn[5], L);
-        panel(w.w2r, sW2R, M, M); cp(w.b2r, rew[3], M);
-        cp(w.w3r, rew[4], M); cp(w.b3r, rew[5], 1);
-    }
-    panel(w.wp1, sWP1, M, w.Lp); cp(w.bp1, pi[1], M);
-    panel(w.wp2, sWP2, M, M); cp(w.bp2, pi[3], M);
-    panel(w.wp3, sWP3, w.Ar, M); cp(w.bp3, pi[5], A);
-    panel(w.wq1x, sWQ1X, 2 * M, w.Kx);
-    panel(w.wq2, sWQ2, 2 * M, M);
-    const float* const* qs[2] = {q1, q2};
-    for (int q = 0; q < 2; ++q) {
-        const float* const* Q = qs[q];
-        // (the 2M-float LN / bias slots hold both heads: each copy's zero tail stops at the next head's start)
-        PackJob* jb;
-        cp(w.bq1x + q * M, Q[1], M); cp(w.g1 + q * M, Q[2], M); cp(w.be1 + q * M, Q[3], M);
-        cp(w.bq2 + q * M, Q[5], M); cp(w.g2 + q * M, Q[6], M); cp(w.be2 + q * M, Q[7], M);
-        cp(w.wq3 + q * M, Q[8], M);
-        jb = &job(PJ_COPY, w.bq3 + q, 1);
-        jb->src = Q[9]; jb->n = 1;
-    }
-    const PackSrc* xs[X6_N] = {&sW1X, &sW2D, &sW2R, &sW3D, &sWP1, &sWP2, &sWP3, &sWQ1X, &sWQ2};
-    for (int x = heads_only ? X6_WP1 : 0; x < X6_N; ++x) {
-        int rows, k;
-        x6_shape(w, x, &rows, &k);
-        PackJob& j = job(PJ_X6, w.x6[x], (long)((rows + 31) / 32) * ((k + 15) / 16) * 512);
-        j.m = *xs[x]; j.prow = rows; j.pk = k;
-    }
-    for (int x = heads_only ? X6_WP1 : 0; x < X6_N; ++x) {
-        int rows, k;
-        x6_shape(w, x, &rows, &k);
-        PackJob& j = job(PJ_X6Q, w.x6q[x], (long)((rows + 15) / 16) * ((k + 31) / 32) * 512);
-        j.m = *xs[x]; j.prow = rows; j.pk = k;
-    }
+// The CemArgs fields every entry point sets alike: the call's geometry (iCEM overrides the per-iteration row counts),
+// the workspace buffers and the pack status.
+CemArgs cem_args0(const Ctx& c) {
+    CemArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.H = c.H; ca.N = c.N; ca.P = c.P; ca.T = ca.Tw = ca.NE = c.T; ca.A = c.A; ca.K = c.d->num_elites; ca.Kx = c.Kx;
+    ca.Hmax = c.d->max_horizon;
+    ca.X = c.k.X; ca.x_stride = c.k.x_stride; ca.value = c.k.value; ca.rlast = c.k.rlast;
+    ca.mean = c.k.mean; ca.stdv = c.k.stdv;
+    ca.pstatus = pack_status(c);
+    return ca;
 }
 
-// The job table lives in the caller's packed buffer (Layout::jobtab), so it lives and dies with that buffer and the
-// HIP graphs the caller captured over it -- nothing device-side is global or leaks. Every pack outside a stream
-// capture uploads header + table (an async copy from a pinned staging buffer kept per packed buffer, whose previous
-// copy's event is waited for before it is rewritten -- long done by then); a pack inside a capture uploads nothing and
-// requires the table last uploaded into that buffer to be this one (pack once before capturing, as the learner does).
-// Staleness is checked on the device, not trusted from the host record: every launch carries the nonce of the table
-// the record says is in the buffer and pack_fused_kernel compares it with the header's (a buffer re-allocated at a
-// recorded address or zeroed again fails loudly: NaN weights + TDMPC_STATUS_PACK_STALE). An uncaptured pack keeps the
-// record's nonce when its table is unchanged (graphs captured over the buffer stay valid) and draws a new one
-// otherwise; once a capture has packed from a buffer, an uncaptured pack with OTHER tensors is refused (it would
-// silently re-point the captured graph) until tdmpc_pack_forget drops the record -- after which such a graph's pack
-// sees a nonce mismatch and fails loudly. Records live until tdmpc_pack_forget; only their pinned staging buffers are
-// recycled (PACK_PINNED of them, least recently used first). One mutex guards it.
-struct PackTable {
-    std::vector<PackJob> host; const float* pw; int device;
-    unsigned long long nonce; bool captured;
-    char* pinned; hipEvent_t done; bool recorded;
-};
-std::vector<PackTable> g_pack_tables;   // most recently used last
-std::mutex g_pack_mu;
-constexpr size_t PACK_PINNED = 64;
-constexpr size_t PACK_UPLOAD_BYTES = (size_t)PACK_HDR_BYTES + (size_t)PACK_MAX_JOBS * sizeof(PackJob);
-
-void pack_table_unpin(PackTable& t) {
-    if (t.recorded) (void)hipEventSynchronize(t.done);
-    if (t.done) (void)hipEventDestroy(t.done);
-    if (t.pinned) (void)hipHostFree(t.pinned);
-    t.pinned = nullptr;
-    t.done = nullptr;
-    t.recorded = false;
-}
-
-// table nonces: never 0 (a zeroed buffer's header) and distinct across processes and buffers with high probability
-unsigned long long pack_next_nonce() {
-    static std::atomic<unsigned long long> ctr{0};
-    static const unsigned long long base =
-        ((unsigned long long)std::chrono::high_resolution_clock::now().time_since_epoch().count() * 0x9E3779B97F4A7C15ull) ^
-        ((unsigned long long)getpid() << 32);
-    for (;;) {
-        unsigned long long z = base + 0x9E3779B97F4A7C15ull * (ctr.fetch_add(1) + 1);   // splitmix64 finaliser
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        if (z) return z;
-    }
-}
-
-int launch_pack(std::vector<PackJob>& jobs, const Layout& w, float* pw, hipStream_t s) {
-    if (jobs.size() > (size_t)PACK_MAX_JOBS) {
-        snprintf(g_err, sizeof g_err, "tdmpc_pack_weights: %zu jobs > %d", jobs.size(), PACK_MAX_JOBS);
-        return TDMPC_E_SIZE;
-    }
-    int blk = 0;
-    for (PackJob& j : jobs) {
-        j.blk0 = blk;
-        const long per_blk = (long)PACK_WG * pack_items(j.kind) * pack_per_item(j.kind);
-        blk += (int)((j.work + per_blk - 1) / per_blk);
-    }
-    const size_t nb = jobs.size() * sizeof(PackJob);
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    PackHdr* hdr = (PackHdr*)(pw + w.jobtab);
-    PackJob* dev = (PackJob*)((char*)hdr + PACK_HDR_BYTES);
-    unsigned long long nonce = 0;
-    {
-        std::lock_guard<std::mutex> lock(g_pack_mu);
-        size_t hit = g_pack_tables.size();
-        for (size_t i = 0; i < g_pack_tables.size(); ++i)
-            if (g_pack_tables[i].pw == pw && g_pack_tables[i].device == device) { hit = i; break; }
-        const bool same = hit < g_pack_tables.size() && g_pack_tables[hit].host.size() == jobs.size() &&
-                          !memcmp(g_pack_tables[hit].host.data(), jobs.data(), nb);
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIPCHK(hipStreamIsCapturing(s, &cs));
-        if (cs != hipStreamCaptureStatusNone) {
-            if (!same) {
-                snprintf(g_err, sizeof g_err, hit == g_pack_tables.size()
-                         ? "tdmpc_pack_weights: no table uploaded into this buffer while capturing (pack once before capture)"
-                         : "tdmpc_pack_weights: new tensors while capturing (pack once before capture)");
-                return TDMPC_E_DIMS;
-            }
-            g_pack_tables[hit].captured = true;
-        } else {
-            if (hit < g_pack_tables.size() && g_pack_tables[hit].captured && !same) {
-                snprintf(g_err, sizeof g_err, "tdmpc_pack_weights: a captured graph packs into this buffer from other "
-                         "tensors; call tdmpc_pack_forget(packed) first (that graph's pack then fails loudly)");
-                return TDMPC_E_DIMS;
-            }
-            if (hit == g_pack_tables.size()) {
-                g_pack_tables.push_back(PackTable{{}, pw, device, 0, false, nullptr, nullptr, false});
-                hit = g_pack_tables.size() - 1;
-            }
-            PackTable& t = g_pack_tables[hit];
-            if (!same || !t.nonce) t.nonce = pack_next_nonce();
-            if (!t.pinned) {
-                size_t npin = 0;
-                for (const PackTable& o : g_pack_tables) npin += o.pinned != nullptr;
-                for (size_t i = 0; npin >= PACK_PINNED && i < g_pack_tables.size(); ++i)
-                    if (g_pack_tables[i].pinned) { pack_table_unpin(g_pack_tables[i]); --npin; }
-                HIPCHK(hipHostMalloc((void**)&t.pinned, PACK_UPLOAD_BYTES, hipHostMallocDefault));
-                HIPCHK(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
-            }
-            if (t.recorded) HIPCHK(hipEventSynchronize(t.done));
-            PackHdr h;
-            memset(&h, 0, sizeof h);
-            h.nonce = t.nonce; h.status = 0; h.njobs = (int)jobs.size();
-            memset(t.pinned, 0, PACK_HDR_BYTES);
-            memcpy(t.pinned, &h, sizeof h);
-            memcpy(t.pinned + PACK_HDR_BYTES, jobs.data(), nb);
-            HIPCHK(hipMemcpyAsync(hdr, t.pinned, PACK_HDR_BYTES + nb, hipMemcpyHostToDevice, s));
-            HIPCHK(hipEventRecord(t.done, s));
-            t.recorded = true;
-            t.host = jobs;
-        }
-        nonce = g_pack_tables[hit].nonce;
-        PackTable t = std::move(g_pack_tables[hit]);   // most recently used last
-        g_pack_tables.erase(g_pack_tables.begin() + hit);
-        g_pack_tables.push_back(std::move(t));
-    }
-    hipLaunchKernelGGL(pack_fused_kernel, dim3((unsigned)blk), dim3(PACK_WG), 0, s, hdr, (const PackJob*)dev,
-                       (int)jobs.size(), pw, nonce, (long)w.jobtab);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Host-only bounds check of one pack job (no HIP call), shared by tdmpc_debug_pack_check and
-// tdmpc_drnn_debug_pack_check: its writes inside the float offsets [lo, hi) of the packed buffer, its reads inside its
-// source tensor, where tensor i of n has the fake base address (i + 1) << 40 and numel[i] floats.
-bool pack_job_in_bounds(const PackJob& J, const int64_t* numel, int n, size_t lo, size_t hi) {
-    auto in_tensor = [&](const float* p, long last) -> bool {   // reads p[0 .. last]
-        const uintptr_t u = (uintptr_t)p;
-        const long i = (long)(u >> 40) - 1;
-        if (i < 0 || i >= n) return false;
-        const long off = (long)((u & (((uintptr_t)1 << 40) - 1)) / 4);
-        return off + last < numel[i];
-    };
-    auto src_ok = [&](const PackSrc& m, int maxk) -> bool {
-        const int maxcol = m.first ? m.L + m.A - 1 : std::min(maxk, m.ncols - 1);
-        if (m.r0 > 0 && !in_tensor(m.p0, (long)(m.r0 - 1) * m.sld + maxcol)) return false;
-        if (m.r1 > 0 && !in_tensor(m.p1, (long)(m.r1 - 1) * m.sld + maxcol)) return false;
-        return true;
-    };
-    const double end = J.kind == PJ_X6 || J.kind == PJ_X6Q ? (double)J.dst + 1.5 * J.work : (double)(J.dst + J.work);
-    if (J.dst < lo || end > (double)hi) return false;
-    if (J.kind == PJ_COPY) return J.n <= J.work && in_tensor(J.src, J.n - 1);
-    if (J.kind == PJ_TRANS) return in_tensor(J.src, (long)J.rows * J.cols - 1);
-    return src_ok(J.m, J.pk - 1);
-}
+#include "pack.inc"
 
 }  // namespace
 
@@ -5186,8 +4759,7 @@ int tdmpc_plan(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* pa
     int rc;
     const int H = prm->horizon, I = prm->iterations, B = prm->batch;
     if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream))) return rc;
-    if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
-    c.path = prm->path == TDMPC_PATH_CHAIN64 ? TDMPC_PATH_CHAIN_X6 : prm->path;   // (64-row blocks retired: path 6)
+    if ((c.path = resolve_path(prm->path, true)) < 0) return TDMPC_E_DIMS;
     const int N = c.N, P = c.P, T = c.T;
     // TDMPC_PATH_PERSIST: the persistent plan where it applies (one env, supported shape), the auto path elsewhere
     if (c.path == TDMPC_PATH_PERSIST && !use_plan1(c)) c.path = TDMPC_PATH_AUTO;
@@ -5233,13 +4805,8 @@ int tdmpc_plan(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* pa
                 return rc;
         }
     }
-    CemArgs ca;
-    memset(&ca, 0, sizeof ca);
-    ca.H = H; ca.N = N; ca.P = P; ca.T = T; ca.A = c.A; ca.K = d->num_elites; ca.Kx = c.Kx;
-    ca.Hmax = d->max_horizon; ca.I = I;
-    ca.Tw = T; ca.NE = T; ca.pi_base = 0;
-    ca.X = c.k.X; ca.x_stride = c.k.x_stride; ca.value = c.k.value; ca.rlast = c.k.rlast;
-    ca.mean = c.k.mean; ca.stdv = c.k.stdv;
+    CemArgs ca = cem_args0(c);
+    ca.I = I;
     ca.eps = noise; ca.eps_env = c.eps_env; ca.eps_cem_off = c.eps_cem_off; ca.eps_iter = c.eps_iter;
     ca.eps_act_off = c.eps_act_off; ca.u = u; ca.prev_mean = prev_mean;
     ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
@@ -5247,7 +4814,7 @@ int tdmpc_plan(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* pa
     ca.std_floor_p = prm->std_floor_dev;
     ca.elite_out = elite_out; ca.score_out = score_out; ca.mean_out = mean_out; ca.std_out = std_out;
     ca.value_out = value_out;
-    ca.pstatus = pack_status(c); ca.status = prm->status;
+    ca.status = prm->status;
     const bool wide_heads = use_wide_heads(c);
     if (wide_heads || c.fold_heads || use_chain(c, B * T, 2, CK_Q)) {   // q1, q2 per row in k.qv; cem_kernel forms the values
         ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H];
@@ -5332,9 +4899,7 @@ int tdmpc_plan_icem(const tdmpc_dims* d, const tdmpc_icem_params* prm, const voi
     const int H = prm->horizon, I = prm->iterations, B = prm->batch, K = d->num_elites;
     if (I <= 0 || I > 16) { snprintf(g_err, sizeof g_err, "iCEM: 1..16 iterations"); return TDMPC_E_DIMS; }
     if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream, K))) return rc;
-    if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
-    c.path = prm->path == TDMPC_PATH_PERSIST ? TDMPC_PATH_AUTO : prm->path == TDMPC_PATH_CHAIN64 ? TDMPC_PATH_CHAIN_X6
-           : prm->path;   // (persist: whole plans only; the retired 64-row path is path 6)
+    if ((c.path = resolve_path(prm->path, false)) < 0) return TDMPC_E_DIMS;
     const int N = d->num_samples, Pmax = d->num_pi, Tw = N + K + Pmax, pi_base = N + K, P0 = prm->n_pi0;
     c.T = Tw;
     if (P0 <= 0 || P0 > Pmax || prm->n_samples[0] != N) { snprintf(g_err, sizeof g_err, "iCEM: bad counts"); return TDMPC_E_DIMS; }
@@ -5352,43 +4917,24 @@ int tdmpc_plan_icem(const tdmpc_dims* d, const tdmpc_icem_params* prm, const voi
     // pi pre-rollout of the P0 policy rows (tdmpc_icem_similarity_mlp.py:193-199); their rollout, reward
     // prefix and z_H are the same in every iteration (same z, same pi actions), so they are computed once
     const RowMap pm0 = {P0, Tw, pi_base};
-    {
-        PrepArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.X = c.k.X; pa.x_stride = c.k.x_stride; pa.Kx = c.Kx; pa.apq = c.w.Ap / 4; pa.lpq = c.w.Lp / 4;
-        pa.B = B; pa.N = N; pa.T = Tw; pa.H = H; pa.A = c.A; pa.z0 = c.k.z0; pa.n_zq = (long)B * pa.lpq * Tw;
-        hipLaunchKernelGGL(prep_kernel, dim3((int)std::min<long>((pa.n_zq + 255) / 256, 2048)), dim3(256), 0, c.s, pa);
-        HIPCHK(hipGetLastError());
-    }
+    if ((rc = prep(c, nullptr, 0, c.k.z0))) return rc;   // z0 into X_0's latent columns, all Tw rows
     for (int t = 0; t < H; ++t) {
         if ((rc = policy(c, t, B * P0, pm0, noise, env, P0, prm->pi_off + (long)t * P0 * A, prm->min_std))) return rc;
         if ((rc = step_next(c, t, B * P0, pm0, prm->discount_pow[t], t == 0, t == H - 1))) return rc;
     }
-    CemArgs ca;
-    memset(&ca, 0, sizeof ca);
-    ca.H = H; ca.A = c.A; ca.K = K; ca.Kx = c.Kx; ca.Hmax = d->max_horizon; ca.I = I;
-    ca.X = c.k.X; ca.x_stride = c.k.x_stride; ca.value = c.k.value; ca.rlast = c.k.rlast;
-    ca.mean = c.k.mean; ca.stdv = c.k.stdv; ca.Tw = Tw; ca.pi_base = pi_base;
+    CemArgs ca = cem_args0(c);   // (c.T = Tw; N, P, T, NE per iteration below)
+    ca.I = I; ca.pi_base = pi_base;
     ca.eps = noise; ca.eps_env = env; ca.eps_act_off = prm->act_off; ca.u = u; ca.prev_mean = prev_mean;
     ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
     ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
     ca.mean_out = mean_out; ca.std_out = std_out; ca.elite_store = elites;
     ca.G = c.k.G; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H]; ca.value_out = value_out;
-    ca.pstatus = pack_status(c); ca.status = prm->status;
+    ca.status = prm->status;
     const size_t cem_lds = cem_lds_bytes(Tw, H, K, c.A);
     for (int i = 0; i < I; ++i) {
         const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i], NE = Ni + Ei;
-        {   // sampled candidates clamp(mean + std * noise) for rows [0, Ni) (sample_mix_action_sequence)
-            PrepArgs pa;
-            memset(&pa, 0, sizeof pa);
-            pa.X = c.k.X; pa.x_stride = c.k.x_stride; pa.Kx = c.Kx; pa.apq = c.w.Ap / 4; pa.lpq = c.w.Lp / 4;
-            pa.B = B; pa.N = Ni; pa.T = Tw; pa.H = H; pa.A = c.A;
-            pa.mean = c.k.mean; pa.stdv = c.k.stdv; pa.mstride = d->max_horizon * c.A;
-            pa.eps = noise; pa.eps_env = env; pa.eps_off = prm->samp_off[i];
-            pa.n_sq = (long)B * H * pa.apq * Ni;
-            hipLaunchKernelGGL(prep_kernel, dim3((int)std::min<long>((pa.n_sq + 255) / 256, 2048)), dim3(256), 0, c.s, pa);
-            HIPCHK(hipGetLastError());
-        }
+        // sampled candidates clamp(mean + std * noise) for rows [0, Ni) (sample_mix_action_sequence)
+        if ((rc = prep_launch(c, noise, Ni, env, prm->samp_off[i], nullptr, nullptr))) return rc;
         if (Ei > 0 || i == I - 1) {
             FillArgs fa;
             memset(&fa, 0, sizeof fa);
@@ -5432,18 +4978,13 @@ int tdmpc_estimate_value(const tdmpc_dims* d, const tdmpc_plan_params* prm, cons
     int rc;
     const int H = prm->horizon, B = prm->batch;
     if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
-    if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
-    c.path = prm->path == TDMPC_PATH_PERSIST ? TDMPC_PATH_AUTO : prm->path == TDMPC_PATH_CHAIN64 ? TDMPC_PATH_CHAIN_X6
-           : prm->path;   // (persist: whole plans only; the retired 64-row path is path 6)
+    if ((c.path = resolve_path(prm->path, false)) < 0) return TDMPC_E_DIMS;
     if (rows != c.T) { snprintf(g_err, sizeof g_err, "rows must equal N+P"); return TDMPC_E_DIMS; }
     const int T = c.T, L = c.w.L;
-    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, c.s, (unsigned*)c.k.z0, (int)((size_t)B * c.w.Lp));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy2DAsync(c.k.z0, c.w.Lp * 4, z0, L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
+    if ((rc = load_z0(c, z0))) return rc;
     hipLaunchKernelGGL(scatter_actions_kernel, dim3(512), dim3(256), 0, c.s, actions, c.k.X, c.k.x_stride, H, T, c.A,
                        c.w.Ap, c.Kx, B, T, 0);
     HIPCHK(hipGetLastError());
-    if ((rc = prep(c, nullptr, 0, c.k.z0))) return rc;
     const RowMap all = {T, T, 0};
     for (int t = 0; t < H; ++t)
         if ((rc = step_next(c, t, B * T, all, prm->discount_pow[t], t == 0, t == H - 1)))
@@ -5464,15 +5005,6 @@ int tdmpc_estimate_value(const tdmpc_dims* d, const tdmpc_plan_params* prm, cons
     return 0;
 }
 
-// z0 [B][L] -> the workspace's padded z0 [B][Lp] and the latent columns of X_0 for all T rows of every env
-static int load_z0(const Ctx& c, const float* z0) {
-    const int L = c.w.L;
-    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, c.s, (unsigned*)c.k.z0, (int)((size_t)c.B * c.w.Lp));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy2DAsync(c.k.z0, c.w.Lp * 4, z0, L * 4, L * 4, c.B, hipMemcpyDeviceToDevice, c.s));
-    return prep(c, nullptr, 0, c.k.z0);
-}
-
 int tdmpc_pi_rollout(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* packed, const float* z0,
                      const float* eps_pi, float* pi_actions, void* workspace, size_t ws_bytes, void* stream) {
     if (!d || !prm || !packed || !z0 || !eps_pi || !pi_actions || !workspace) return TDMPC_E_NULL;
@@ -5480,9 +5012,7 @@ int tdmpc_pi_rollout(const tdmpc_dims* d, const tdmpc_plan_params* prm, const vo
     int rc;
     const int H = prm->horizon, B = prm->batch;
     if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
-    if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
-    c.path = prm->path == TDMPC_PATH_PERSIST ? TDMPC_PATH_AUTO : prm->path == TDMPC_PATH_CHAIN64 ? TDMPC_PATH_CHAIN_X6
-           : prm->path;   // (persist: whole plans only; the retired 64-row path is path 6)
+    if ((c.path = resolve_path(prm->path, false)) < 0) return TDMPC_E_DIMS;
     const int N = c.N, P = c.P, T = c.T;
     const long A = c.A;
     if (P <= 0) { snprintf(g_err, sizeof g_err, "num_pi is 0"); return TDMPC_E_DIMS; }
@@ -5510,9 +5040,7 @@ int tdmpc_cem_iter(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void
     int rc;
     const int H = prm->horizon, B = prm->batch;
     if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
-    if (prm->path < 0 || prm->path > TDMPC_PATH_WIDE) { snprintf(g_err, sizeof g_err, "bad path"); return TDMPC_E_DIMS; }
-    c.path = prm->path == TDMPC_PATH_PERSIST ? TDMPC_PATH_AUTO : prm->path == TDMPC_PATH_CHAIN64 ? TDMPC_PATH_CHAIN_X6
-           : prm->path;   // (persist: whole plans only; the retired 64-row path is path 6)
+    if ((c.path = resolve_path(prm->path, false)) < 0) return TDMPC_E_DIMS;
     const int N = c.N, P = c.P, T = c.T, A = c.A, HA = H * A;
     if (P > 0 && !pi_actions) return TDMPC_E_NULL;
     // the caller's mean/std [B][H][A] -> the workspace's [B][Hmax][A]
@@ -5533,17 +5061,12 @@ int tdmpc_cem_iter(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void
         if ((rc = step_next(c, t, B * T, all, prm->discount_pow[t], t == 0, t == H - 1, 1))) return rc;
     if ((rc = policy(c, H, B * T, all, eps_term, (long)T * A, T, 0, prm->min_std))) return rc;
     if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
-    CemArgs ca;
-    memset(&ca, 0, sizeof ca);
-    ca.H = H; ca.N = N; ca.P = P; ca.T = T; ca.A = A; ca.K = d->num_elites; ca.Kx = c.Kx;
-    ca.Hmax = d->max_horizon; ca.I = 1; ca.iter = 0; ca.final_iter = 1; ca.no_pick = 1;
-    ca.Tw = T; ca.NE = T; ca.pi_base = 0;
-    ca.X = c.k.X; ca.x_stride = c.k.x_stride; ca.value = c.k.value; ca.rlast = c.k.rlast;
-    ca.mean = c.k.mean; ca.stdv = c.k.stdv;
+    CemArgs ca = cem_args0(c);
+    ca.I = 1; ca.iter = 0; ca.final_iter = 1; ca.no_pick = 1;
     ca.temperature = prm->temperature; ca.momentum = prm->momentum; ca.omm = prm->one_minus_momentum;
     ca.std_floor = prm->std_floor; ca.std_floor_p = prm->std_floor_dev;
     ca.elite_out = elite_actions; ca.score_out = score; ca.value_out = value; ca.reward_out = reward_mean;
-    ca.pstatus = pack_status(c); ca.status = prm->status;
+    ca.status = prm->status;
     if (use_chain(c, B * T, 2, CK_Q)) { ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H]; }
     hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds_bytes(T, H, ca.K, A), c.s, ca);
     HIPCHK(hipGetLastError());

@@ -57,6 +57,19 @@ def test_plan_fullsize_configs(name, B):
     task, ov = CONFIGS[name]
     cfg = make_cfg(task, **ov)
     agent = _agent(cfg, 21, B=B)
+    _plan_calls_match_oracle(name, cfg, agent, B)
+    if B == 32:   # the kernels that ran: the wide ones where the bench runs them (latent 512: the wide step kernel
+        # with the streamed x and the folded first layer; helper.q stays on the chain kernel -- its statistics block
+        # does not fit at 534 columns)
+        step_k, q_k = _kernel_of(agent, cfg, 4), _kernel_of(agent, cfg, 6)
+        l512 = name == "humanoid-run-l512"
+        assert step_k.startswith("wide_step_kernel<17, 32" if l512 else "wide_step_kernel"), step_k
+        assert q_k.startswith("chain_kernel" if l512 else "wide_heads_kernel"), q_k
+
+
+def _plan_calls_match_oracle(name, cfg, agent, B):
+    """Cold, warm and (B > 1) mixed-t0 plan() calls of `agent` (synthetic weights of seed 21), every env against the
+    oracle on the same noise: the comparison and tolerances of the module docstring."""
     told = tdmpc_ref.RefTOLD(synthetic_state_dict(cfg, 21), cfg)
     states = [tdmpc_ref.PlanState(0.05) for _ in range(B)]
     diverged = [False] * B        # an env whose elite set swapped on a near tie is not compared while warm
@@ -91,15 +104,8 @@ def test_plan_fullsize_configs(name, B):
             np.testing.assert_allclose(tr["std"][e, -1].cpu().numpy(), rtr["std"][-1].numpy(), atol=2e-5, rtol=0)
             np.testing.assert_allclose([m[e]["external_reward_mean"], m[e]["current_std"]],
                                        [rm["external_reward_mean"], rm["current_std"]], atol=2e-5, rtol=1e-4)
-            pm = agent.planner.prev_mean_view(5, B)[e].cpu().numpy()
+            pm = agent.planner.prev_mean_view(cfg.horizon, B)[e].cpu().numpy()
             np.testing.assert_allclose(pm, states[e].prev_mean.numpy(), atol=2e-5, rtol=0)
-    if B == 32:   # the kernels that ran: the wide ones where the bench runs them (latent 512: the wide step kernel
-        # with the streamed x and the folded first layer; helper.q stays on the chain kernel -- its statistics block
-        # does not fit at 534 columns)
-        step_k, q_k = _kernel_of(agent, cfg, 4), _kernel_of(agent, cfg, 6)
-        l512 = name == "humanoid-run-l512"
-        assert step_k.startswith("wide_step_kernel<17, 32" if l512 else "wide_step_kernel"), step_k
-        assert q_k.startswith("chain_kernel" if l512 else "wide_heads_kernel"), q_k
 
 
 def test_latent512_folded_rollout_accuracy():
@@ -157,6 +163,95 @@ def _kernel_of(agent, cfg, prof_cfg):
         agent.graph = graph
     assert n.value > 0, prof_cfg
     return L.tdmpc_profile_kernel().decode()
+
+
+def _wide_gap_cfg():
+    """The smallest shape in the gap of the wide step kernel's instance table: mlp_dim 512, latent 50 (4 last-layer
+    tiles), action_dim 44 -> Kx = 104, four first-layer 32-k groups, and (4, 4) is no instance (wide_step.inc). One
+    env's T = 96 rows are a single 128-row block."""
+    cfg = make_cfg("dog", latent_dim=50, num_samples=64, num_elites=32, iterations=2, horizon=2)
+    cfg.action_dim = 44
+    return cfg
+
+
+def _estimate_raw(pl, path_id, z0, actions, eps, H):
+    """tdmpc_estimate_value through the raw C ABI with any integer as params->path: (code, value, last reward)."""
+    import ctypes as C
+    prm = pl.params(H, 1, z0.shape[0], False, True, 0.05)
+    prm.path = path_id
+    dev, vp = pl.device, C.c_void_p
+    z0, actions, eps = (t.to(dev, torch.float32).contiguous() for t in (z0, actions, eps))
+    value, rlast = torch.full((z0.shape[0], pl.T), np.nan, device=dev), torch.full((z0.shape[0], pl.T), np.nan, device=dev)
+    rc = pl.L.tdmpc_estimate_value(C.byref(pl.dims), C.byref(prm), vp(pl.packed.data_ptr()), vp(z0.data_ptr()),
+                                   vp(actions.data_ptr()), vp(eps.data_ptr()), pl.T, vp(value.data_ptr()),
+                                   vp(rlast.data_ptr()), None, vp(pl.workspace.data_ptr()), pl.workspace.numel() * 4,
+                                   vp(torch.cuda.current_stream(dev).cuda_stream))
+    return rc, value.cpu(), rlast.cpu()
+
+
+def _estimate_inputs(cfg, pl, H, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(1, cfg.latent_dim, generator=g), torch.rand(1, H, pl.T, cfg.action_dim, generator=g) * 2 - 1,
+            torch.randn(1, pl.T, cfg.action_dim, generator=g))
+
+
+def test_wide_path_without_instance_runs_chain_estimate_value():
+    """path="wide" at a shape the wide step kernel has no instance for takes the chain x6 kernel at every step (it
+    used to fail with "wide step: no instance"): estimate_value's outputs equal path="chain_x6"'s bitwise, and the
+    step launches the profiler names are the chain kernel's."""
+    import ctypes as C
+    from tdmpc_amd import _lib
+    cfg = _wide_gap_cfg()
+    H = cfg.horizon
+    outs = {}
+    for path in ("wide", "chain_x6"):
+        agent = _agent(cfg, 21, path=path)
+        pl = agent.planner
+        pl.pack(agent.model)
+        z0, actions, eps = _estimate_inputs(cfg, pl, H, 3)
+        _lib.check(pl.L.tdmpc_profile_begin(4, -1, 0, 0, 16), "profile_begin")
+        v, r, _ = pl.estimate_value(z0, actions, eps, H)
+        n = C.c_int32()
+        _lib.check(pl.L.tdmpc_profile_end(C.byref(n), None, None), "profile_end")
+        assert n.value == H, n.value
+        step_k = pl.L.tdmpc_profile_kernel().decode()
+        assert step_k == "chain_kernel<CH_STEP, x6>", (path, step_k)
+        outs[path] = (v.cpu(), r.cpu())
+    assert torch.isfinite(outs["wide"][0]).all()
+    assert torch.equal(outs["wide"][0], outs["chain_x6"][0])
+    assert torch.equal(outs["wide"][1], outs["chain_x6"][1])
+
+
+def test_wide_path_without_instance_plan_matches_oracle():
+    """The whole plan() on path="wide" at the same shape (every step falls back to the chain kernel) against the
+    oracle, with test_plan_fullsize_configs' comparison; the device status word stays 0."""
+    cfg = _wide_gap_cfg()
+    agent = _agent(cfg, 21, path="wide")
+    _plan_calls_match_oracle("dog-l50-a44-wide", cfg, agent, 1)
+    assert int(agent.planner.status.item()) == 0
+
+
+def test_path_normalisation_raw_abi():
+    """params->path through the raw C ABI: out-of-range values are refused with "bad path"; the persistent path (whole
+    plans only) runs estimate_value as auto, and the retired path 8 (chain64) as chain_x6, bitwise."""
+    from tdmpc_amd import _lib
+    cfg = make_cfg("cartpole", num_samples=64, num_elites=32, iterations=3, horizon=5)
+    H = cfg.horizon
+    agent = _agent(cfg, 21)
+    pl = agent.planner
+    pl.pack(agent.model)
+    inputs = _estimate_inputs(cfg, pl, H, 5)
+    for bad in (-1, _lib.PATHS["wide"] + 1):
+        rc, _, _ = _estimate_raw(pl, bad, *inputs, H)
+        assert rc == -1, (bad, rc)   # TDMPC_E_DIMS
+        assert "bad path" in pl.L.tdmpc_last_error().decode()
+    assert _lib.PATHS["chain64"] == 8
+    for alias, target in (("persist", "auto"), ("chain64", "chain_x6")):
+        rc_a, v_a, r_a = _estimate_raw(pl, _lib.PATHS[alias], *inputs, H)
+        rc_t, v_t, r_t = _estimate_raw(pl, _lib.PATHS[target], *inputs, H)
+        assert rc_a == 0 and rc_t == 0, (alias, rc_a, rc_t)
+        assert torch.isfinite(v_t).all()
+        assert torch.equal(v_a, v_t) and torch.equal(r_a, r_t), alias
 
 
 @pytest.mark.parametrize("path", ["auto", "chain_x6", "layered"])
