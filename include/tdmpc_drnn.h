@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TDMPC_DRNN_VERSION 1
+#define TDMPC_DRNN_VERSION 2
 
 /* Static shape of one DSSM planner: the planner dims plus the GRU width (cfg.hidden_dim). base.num_pi is
  * int(mixture_coef * num_samples) of the call (regularization_schedule moves it; sizes are monotone in it, so size the
@@ -86,6 +86,57 @@ int tdmpc_drnn_plan(const tdmpc_drnn_dims* dims, const tdmpc_plan_params* params
                     const float* hidden, const float* noise, const double* u, float* prev_mean, float* action,
                     float* metrics, float* z_out, float* elite_out, float* score_out, float* value_out,
                     float* mean_out, float* std_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- iCEM on the DSSM (`TdICemSimDssm`, src/algorithm/tdmpc_icem_similarity_drnn.py), version 2 ---- */
+
+/* Byte sizes of the iCEM DSSM planner: the workspace holds N + K + num_pi rows per env (as tdmpc_icem_sizes_for) plus
+ * the two hidden ping-pong buffers; the packed size is tdmpc_drnn_sizes_for's. noise_floats_per_env is an upper bound
+ * of one env's noise stream at max_horizon / max_iterations with K reused elites (the layout itself is the caller's:
+ * tdmpc_icem_params offsets). */
+int tdmpc_drnn_icem_sizes_for(const tdmpc_drnn_dims* dims, tdmpc_sizes* out);
+
+/* One TdICemSimDssm.plan (:169-272, after the seed-step branch) for params->batch envs: tdmpc_plan_icem's order of
+ * work with the rollout step replaced by drnn_step_kernel from each env's hidden state, then DSSM.next(z0, action,
+ * hidden) with the returned (noised) action (:267).
+ *   hidden     [batch, Hd] in   the GRU state the rollouts start from
+ *   hidden_out [batch, Hd] out  required; may alias `hidden`
+ *   z_out      [batch, L]  out  optional: the encoded observation
+ * and every other argument as tdmpc_plan_icem (state observations, fp32). The policy rows' pre-rollout (their G,
+ * last reward and z_H) is computed once and reused by every iteration. params->path is checked and selects nothing. */
+int tdmpc_drnn_plan_icem(const tdmpc_drnn_dims* dims, const tdmpc_icem_params* params, const void* packed,
+                         const void* obs, const float* hidden, const float* noise, const double* u, float* prev_mean,
+                         float* elites, float* action, float* metrics, float* hidden_out, float* z_out,
+                         float* value_out, float* mean_out, float* std_out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* Power-law (coloured) noise sequences written straight into the per-env noise streams (drnn_colored_noise_kernel).
+ * A job is `n` sequences (r, a), r < n, a < A, of L samples each, for the block [L][rows][A] at `dst` floats into
+ * the env's stream, columns c0 .. c0 + n: sample t of sequence (r, a) goes to
+ *   noise[env * env_stride + dst + (t * rows + c0 + r) * A + a].
+ * Sequence s = r * A + a takes 2F standard normals, F = L / 2 + 1, from
+ *   normals[env * normals_env + src + k * n * A + s],  k < 2F  (k < F: real parts, then the imaginary parts)
+ * multiplies them by its spectrum's factors re[k] / im[k] (colored_noise.spectrum_rows: f^(-beta/2) with the low
+ * cutoff, sqrt(2) on the DC and even-L Nyquist real parts, 0 for their imaginary parts, 1/sigma folded in) and
+ * applies the inverse real DFT as the [2F][L] matrix `dft` (colored_noise.irfft_matrices; rows of 16 floats). */
+#define TDMPC_NOISE_MAX_JOBS 17
+#define TDMPC_NOISE_MAX_SPECTRA 4
+typedef struct tdmpc_noise_job {
+    int32_t spectrum, n, rows, c0;
+    int64_t dst, src;
+} tdmpc_noise_job;
+typedef struct tdmpc_colored_noise_params {
+    int32_t L, A, batch, n_jobs, n_spectra, pad_;
+    int64_t env_stride, normals_env;
+    tdmpc_noise_job jobs[TDMPC_NOISE_MAX_JOBS];
+    float re[TDMPC_NOISE_MAX_SPECTRA][9], im[TDMPC_NOISE_MAX_SPECTRA][9];
+    float dft[18][16];
+} tdmpc_colored_noise_params;
+
+/* Domain: 2 <= L <= 16, A <= 64, 1 <= n_jobs <= 17, 1 <= n_spectra <= 4. Every job must lie inside its env's stream
+ * (batch * env_stride <= noise_floats) and read inside normals (batch * normals_env <= normals_floats); otherwise
+ * TDMPC_E_SIZE / TDMPC_E_DIMS with a message and nothing is launched. */
+int tdmpc_drnn_colored_noise(const tdmpc_colored_noise_params* params, const float* normals, size_t normals_floats,
+                             float* noise, size_t noise_floats, void* stream);
 
 /* Diagnostic kernel timer, as tdmpc_profile_begin / tdmpc_profile_end for drnn_step_kernel: arms a per-thread recorder
  * that brackets every later step launch over exactly `rows` rows (0 = any) by HIP events; _end returns the launch

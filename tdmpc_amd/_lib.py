@@ -30,8 +30,10 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             # include/tdmpc_drnn.h
             "tdmpc_drnn_version", "tdmpc_drnn_sizes_for", "tdmpc_drnn_num_param_tensors", "tdmpc_drnn_pack_weights",
             "tdmpc_drnn_debug_pack_check", "tdmpc_drnn_next", "tdmpc_drnn_estimate_value", "tdmpc_drnn_pi_rollout", "tdmpc_drnn_plan",
-            "tdmpc_drnn_profile_begin", "tdmpc_drnn_profile_end")
-DRNN_VERSION = 1
+            "tdmpc_drnn_profile_begin", "tdmpc_drnn_profile_end",
+            "tdmpc_drnn_icem_sizes_for", "tdmpc_drnn_plan_icem", "tdmpc_drnn_colored_noise")
+DRNN_VERSION = 2
+NOISE_MAX_JOBS, NOISE_MAX_SPECTRA = 17, 4
 
 
 # tdmpc_plan_params.status bits (include/tdmpc_hip.h)
@@ -82,6 +84,17 @@ class IcemParams(C.Structure):
                [(n, C.c_int64) for n in ("reuse_off", "pi_off", "act_off", "env_stride")] + \
                [(n, C.c_float) for n in ("min_std", "temperature", "momentum", "one_minus_momentum", "std_floor",
                                          "init_std")] + [("discount_pow", C.c_float * 17), ("status", C.c_void_p)]
+
+
+class NoiseJob(C.Structure):   # tdmpc_noise_job (include/tdmpc_drnn.h)
+    _fields_ = [(n, C.c_int32) for n in ("spectrum", "n", "rows", "c0")] + [("dst", C.c_int64), ("src", C.c_int64)]
+
+
+class ColoredNoiseParams(C.Structure):   # tdmpc_colored_noise_params
+    _fields_ = [(n, C.c_int32) for n in ("L", "A", "batch", "n_jobs", "n_spectra", "pad_")] + \
+               [("env_stride", C.c_int64), ("normals_env", C.c_int64), ("jobs", NoiseJob * NOISE_MAX_JOBS),
+                ("re", C.c_float * 9 * NOISE_MAX_SPECTRA), ("im", C.c_float * 9 * NOISE_MAX_SPECTRA),
+                ("dft", C.c_float * 16 * 18)]
 
 
 class ReplayDims(C.Structure):
@@ -211,6 +224,10 @@ def lib():
     L.tdmpc_drnn_estimate_value.argtypes = [dd, pp, vp, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     L.tdmpc_drnn_pi_rollout.argtypes = [dd, pp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.tdmpc_drnn_plan.argtypes = [dd, pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.tdmpc_drnn_icem_sizes_for.argtypes = [dd, C.POINTER(Sizes)]
+    L.tdmpc_drnn_plan_icem.argtypes = [dd, C.POINTER(IcemParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, sz, vp]
+    L.tdmpc_drnn_colored_noise.argtypes = [C.POINTER(ColoredNoiseParams), vp, sz, vp, sz, vp]
     L.tdmpc_drnn_profile_begin.argtypes = [i32, i32]
     L.tdmpc_drnn_profile_end.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     for name in EXPORTED:

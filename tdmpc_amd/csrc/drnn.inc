@@ -320,13 +320,14 @@ __global__ void __launch_bounds__(64 * DRNN_NW) drnn_step_kernel(const DrnnArgs 
     }
 }
 
-// z [rows][L], a [rows][A] -> the [a | 0 | z | 0] rows of an X panel (padding written as 0)
-__global__ void drnn_scatter_kernel(const float* z, const float* act, float* X, int rows, int L, int A, int Ap, int Kx) {
+// z [rows][zld], a [rows][A] -> the [a | 0 | z | 0] rows of an X panel (padding written as 0)
+__global__ void drnn_scatter_kernel(const float* z, int zld, const float* act, float* X, int rows, int L, int A, int Ap,
+                                    int Kx) {
     const size_t total = (size_t)rows * Kx;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t m = i / Kx;
         const int c = (int)(i % Kx);
-        const float v = c < A ? act[m * A + c] : (c >= Ap && c < Ap + L ? z[m * L + (c - Ap)] : 0.f);
+        const float v = c < A ? act[m * A + c] : (c >= Ap && c < Ap + L ? z[m * zld + (c - Ap)] : 0.f);
         X[pidx(m, c, Kx)] = v;
     }
 }
@@ -344,6 +345,44 @@ __global__ void drnn_copy_rows_kernel(const float* src, int sld, float* dst, int
     const int total = rows * n;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
         dst[(size_t)(i / n) * dld + i % n] = src[(size_t)(i / n) * sld + i % n];
+}
+
+// Power-law noise sequences straight into the planner's per-env noise streams (tdmpc_drnn_colored_noise; the
+// reference's colorednoise.powerlaw_psd_gaussian per candidate, tdmpc_icem_similarity_drnn.py:135-146). One thread
+// per sequence s = r * A + a of a job (blockIdx.y) of an env (blockIdx.z): its 2F normals lie n * A apart, so the
+// lanes of a wave read consecutive floats for every k, and they write consecutive floats for every sample t
+// (the block is [L][rows][A]). The spectrum factors and the [2F][16] inverse-DFT matrix travel in the kernel
+// arguments; k is uniform, so they are scalar loads. y[] stays in registers (fixed trip count of 16, rows past L are 0).
+struct ColoredJob { int spectrum, n, rows, c0; long dst, src; };
+struct ColoredArgs {
+    int L, A, F;
+    long env_stride, normals_env;
+    const float* normals; float* noise;
+    ColoredJob jobs[17];
+    float re[4][9], im[4][9];
+    float dft[18][16];
+};
+
+__global__ void __launch_bounds__(256) drnn_colored_noise_kernel(const ColoredArgs a) {
+    const ColoredJob& j = a.jobs[blockIdx.y];
+    const int nA = j.n * a.A;
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nA) return;
+    const float* z = a.normals + (size_t)blockIdx.z * a.normals_env + j.src + s;
+    float y[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) y[t] = 0.f;
+    for (int k = 0; k < 2 * a.F; ++k) {
+        const float f = k < a.F ? a.re[j.spectrum][k] : a.im[j.spectrum][k - a.F];
+        const float x = z[(size_t)k * nA] * f;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) y[t] = fmaf(x, a.dft[k][t], y[t]);
+    }
+    float* o = a.noise + (size_t)blockIdx.z * a.env_stride + j.dst + (size_t)j.c0 * a.A + s;
+    const size_t ts = (size_t)j.rows * a.A;
+#pragma unroll
+    for (int t = 0; t < 16; ++t)
+        if (t < a.L) o[t * ts] = y[t];
 }
 
 #else  // ================================================================================================ DRNN_HOST
@@ -394,9 +433,10 @@ bool drnn_check(const tdmpc_drnn_dims* d, Layout* w, DrnnLayout* dl) {
 
 // workspace: the planner's (make_work), then two hidden-state buffers [xrows][Hd] (ping-pong over the steps)
 struct DrnnWork { float* hb[2]; size_t total; };
-void drnn_work(const tdmpc_drnn_dims* d, const Layout& w, char* base, DrnnWork* dw) {
+// (extra: rows per env beyond N + P, as make_work's: the iCEM planner's reused elites)
+void drnn_work(const tdmpc_drnn_dims* d, const Layout& w, char* base, DrnnWork* dw, int extra = 0) {
     Work k;
-    make_work(&d->base, w, nullptr, &k);
+    make_work(&d->base, w, nullptr, &k, extra);
     size_t o = k.total;
     for (int i = 0; i < 2; ++i) {
         dw->hb[i] = base ? (float*)(base + o) : nullptr;
@@ -420,13 +460,13 @@ int drnn_attrs() {
 }
 
 int drnn_setup(DrnnCtx& x, const tdmpc_drnn_dims* d, const void* packed, void* ws, size_t ws_bytes, int batch, int H,
-               int I, hipStream_t s) {
+               int I, hipStream_t s, int extra = 0) {
     Layout w;
     if (!drnn_check(d, &w, &x.dl)) return TDMPC_E_DIMS;
-    drnn_work(d, w, nullptr, &x.dw);
+    drnn_work(d, w, nullptr, &x.dw, extra);
     if (ws_bytes < x.dw.total) { snprintf(g_err, sizeof g_err, "drnn: workspace too small"); return TDMPC_E_SIZE; }
-    drnn_work(d, w, (char*)ws, &x.dw);
-    int rc = setup_ctx(x.c, &d->base, packed, ws, ws_bytes, batch, H, I, s);
+    drnn_work(d, w, (char*)ws, &x.dw, extra);
+    int rc = setup_ctx(x.c, &d->base, packed, ws, ws_bytes, batch, H, I, s, extra);
     if (rc) return rc;
     // one kernel family for every launch size, so a row's arithmetic does not depend on the batch it is planned in
     x.c.path = TDMPC_PATH_CHAIN_X6;
@@ -514,6 +554,16 @@ int drnn_pack_jobs(const Layout& w, const DrnnLayout& dl, const float* const* t,
     x6(dl.x_r2, t[18], nullptr, M, 0, M, M, 0, M);
     cp(dl.b_r2, t[19], M); cp(dl.w_r4, t[20], M); cp(dl.b_r4, t[21], 1);
     return nheads;
+}
+
+// The iCEM planner keeps N + K + num_pi rows per env: the CEM kernel's LDS and row limits at that width.
+bool drnn_icem_dims_ok(const tdmpc_dims& b) {
+    const int Tw = b.num_samples + b.num_elites + b.num_pi;
+    if (b.num_pi <= 0 || Tw > 4096 || cem_lds_bytes(Tw, b.max_horizon, b.num_elites, b.action_dim) > 160 * 1024) {
+        snprintf(g_err, sizeof g_err, "drnn iCEM: %d rows per env (num_pi %d) outside the CEM kernel's range", Tw, b.num_pi);
+        return false;
+    }
+    return true;
 }
 
 }  // namespace
@@ -607,7 +657,7 @@ int tdmpc_drnn_next(const tdmpc_drnn_dims* d, const void* packed, const float* z
     }
     const long total = (long)rows * c.Kx;
     hipLaunchKernelGGL(drnn_scatter_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, c.s,
-                       z, act, c.k.X, rows, c.w.L, c.w.A, c.w.Ap, c.Kx);
+                       z, c.w.L, act, c.k.X, rows, c.w.L, c.w.A, c.w.Ap, c.Kx);
     HIPCHK(hipGetLastError());
     if ((rc = drnn_step(x, 0, rows, RowMap{1 << 30, 0, 0}, h, 0, h_out, nullptr, r_out, 1.f, 1, 1))) return rc;
     hipLaunchKernelGGL(gather_z_kernel, dim3(256), dim3(256), 0, c.s, Xt(c, 1), c.Kx, c.w.Ap, c.w.L, rows, z_out);
@@ -734,6 +784,171 @@ int tdmpc_drnn_plan(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, cons
         hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
         HIPCHK(hipGetLastError());
     }
+    return 0;
+}
+
+int tdmpc_drnn_icem_sizes_for(const tdmpc_drnn_dims* d, tdmpc_sizes* out) {
+    if (!d || !out) return TDMPC_E_NULL;
+    Layout w;
+    DrnnLayout dl;
+    if (!drnn_check(d, &w, &dl)) return TDMPC_E_DIMS;
+    const tdmpc_dims& b = d->base;
+    if (!drnn_icem_dims_ok(b)) return TDMPC_E_DIMS;
+    DrnnWork dw, dw0;
+    drnn_work(d, w, nullptr, &dw, b.num_elites);
+    // (never below tdmpc_drnn_sizes_for's, whose layout may carry a region this one leaves out: one workspace then
+    // serves tdmpc_drnn_next and the other entry points on the same dims too)
+    drnn_work(d, w, nullptr, &dw0);
+    out->packed_weight_bytes = rup(dl.total * 4, 256);
+    out->workspace_bytes = std::max(dw.total, dw0.total);
+    const size_t A = w.A, H = b.max_horizon, N = b.num_samples, P = b.num_pi, K = b.num_elites;
+    out->noise_floats_per_env = H * P * A + b.max_iterations * (H * N * A + (N + K + P) * A) + H * K * A + A;
+    return 0;
+}
+
+int tdmpc_drnn_plan_icem(const tdmpc_drnn_dims* d, const tdmpc_icem_params* prm, const void* packed, const void* obs,
+                         const float* hidden, const float* noise, const double* u, float* prev_mean, float* elites,
+                         float* action, float* metrics, float* hidden_out, float* z_out, float* value_out,
+                         float* mean_out, float* std_out, void* workspace, size_t ws_bytes, void* stream) {
+    if (!d || !prm || !packed || !obs || !hidden || !noise || !u || !prev_mean || !elites || !action || !metrics ||
+        !hidden_out || !workspace)
+        return TDMPC_E_NULL;
+    DrnnCtx x;
+    int rc;
+    const int H = prm->horizon, I = prm->iterations, B = prm->batch, K = d->base.num_elites;
+    if (I <= 0 || I > 16) { snprintf(g_err, sizeof g_err, "drnn iCEM: 1..16 iterations"); return TDMPC_E_DIMS; }
+    if (!drnn_icem_dims_ok(d->base)) return TDMPC_E_DIMS;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream, K))) return rc;
+    if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
+    Ctx& c = x.c;
+    const int N = d->base.num_samples, Pmax = d->base.num_pi, Tw = N + K + Pmax, pi_base = N + K, P0 = prm->n_pi0;
+    c.T = Tw;
+    if (P0 <= 0 || P0 > Pmax || prm->n_samples[0] != N) {
+        snprintf(g_err, sizeof g_err, "drnn iCEM: bad counts");
+        return TDMPC_E_DIMS;
+    }
+    for (int i = 0; i < I; ++i) {
+        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i];
+        if (Ni <= 0 || Ni > N || Pi <= 0 || Pi > P0 || Ei < 0 || Ei > K || Ni + Ei + Pi < K ||
+            (Ei > 0 && i == 0 && !prm->has_elites) ||
+            (i == 0 && Ei > 0 && prm->elite_horizon != H && prm->elite_horizon != H - 1)) {
+            snprintf(g_err, sizeof g_err, "drnn iCEM: bad counts at iteration %d", i);
+            return TDMPC_E_DIMS;
+        }
+    }
+    const long A = c.A, env = prm->env_stride;
+    // z0 = h(obs); mean = 0 (warm: mean[:-1] = prev[1:], mean[-1] = prev[-1]), std = init_std (0.5)
+    if ((rc = encode(c, obs, 0, B, prev_mean, prm->warm_start, 1, prm->init_std))) return rc;
+    if (z_out) {
+        hipLaunchKernelGGL(drnn_copy_rows_kernel, dim3(B), dim3(256), 0, c.s, c.k.z0, c.w.Lp, z_out, c.w.L, c.w.L, B);
+        HIPCHK(hipGetLastError());
+    }
+    // The policy pre-rollout of the P0 policy rows (tdmpc_icem_similarity_drnn.py:197-202), hidden carried from the
+    // env's state: their G, last reward and z_H are the same in every iteration, so they are computed once
+    const RowMap pm0 = {P0, Tw, pi_base};
+    if ((rc = prep(c, nullptr, 0, c.k.z0))) return rc;   // z0 into X_0's latent columns, all Tw rows
+    for (int t = 0; t < H; ++t) {
+        if ((rc = policy(c, t, B * P0, pm0, noise, env, P0, prm->pi_off + (long)t * P0 * A, prm->min_std))) return rc;
+        if ((rc = drnn_step(x, t, B * P0, pm0, t == 0 ? hidden : nullptr, P0, nullptr, c.k.G, c.k.rlast,
+                            prm->discount_pow[t], t == 0, t == H - 1)))
+            return rc;
+    }
+    CemArgs ca = cem_args0(c);   // (c.T = Tw; N, P, T, NE per iteration below)
+    ca.I = I; ca.pi_base = pi_base;
+    ca.eps = noise; ca.eps_env = env; ca.eps_act_off = prm->act_off; ca.u = u; ca.prev_mean = prev_mean;
+    ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
+    ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
+    ca.mean_out = mean_out; ca.std_out = std_out; ca.elite_store = elites;
+    ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H]; ca.value_out = value_out;
+    ca.status = prm->status;
+    const size_t cem_lds = cem_lds_bytes(Tw, H, K, c.A);
+    for (int i = 0; i < I; ++i) {
+        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i], NE = Ni + Ei;
+        // sampled candidates clamp(mean + std * noise) for rows [0, Ni) (sample_action_sequence)
+        if ((rc = prep_launch(c, noise, Ni, env, prm->samp_off[i], nullptr, nullptr))) return rc;
+        if (Ei > 0 || i == I - 1) {
+            FillArgs fa;
+            memset(&fa, 0, sizeof fa);
+            fa.X = c.k.X; fa.x_stride = c.k.x_stride; fa.Kx = c.Kx; fa.apq = c.w.Ap / 4; fa.Tw = Tw;
+            fa.B = B; fa.H = H; fa.A = c.A; fa.Hmax = d->base.max_horizon; fa.K = K;
+            fa.n0 = Ni; fa.E = Ei; fa.mode = i == 0 ? 1 : 2; fa.eH = prm->elite_horizon; fa.mean_row = i == I - 1;
+            fa.mean = c.k.mean; fa.stdv = c.k.stdv; fa.elites = elites;
+            fa.eps = noise; fa.eps_env = env; fa.reuse_off = prm->reuse_off;
+            const long tot = (long)B * H * fa.apq * (Ei + fa.mean_row);
+            hipLaunchKernelGGL(icem_fill_kernel, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, c.s, fa);
+            HIPCHK(hipGetLastError());
+        }
+        // rollout of the sampled + reused rows from the env's hidden state (the policy rows' is cached)
+        const RowMap blk = {NE, Tw, 0};
+        for (int t = 0; t < H; ++t)
+            if ((rc = drnn_step(x, t, B * NE, blk, t == 0 ? hidden : nullptr, NE, nullptr, c.k.G, c.k.rlast,
+                                prm->discount_pow[t], t == 0, t == H - 1)))
+                return rc;
+        // terminal value of all T_i = NE + Pi candidates: pi(z_H) with this iteration's noise, Q
+        const RowMap pmi = {Pi, Tw, pi_base};
+        if ((rc = policy(c, H, B * NE, blk, noise, env, NE, prm->term_off[i], prm->min_std))) return rc;
+        if ((rc = policy(c, H, B * Pi, pmi, noise, env, Pi, prm->term_off[i] + (long)NE * A, prm->min_std))) return rc;
+        if ((rc = terminal_q_rows(c, B * NE, blk, prm->discount_pow[H], true))) return rc;
+        if ((rc = terminal_q_rows(c, B * Pi, pmi, prm->discount_pow[H], true))) return rc;
+        ca.N = Ni; ca.P = Pi; ca.T = NE + Pi; ca.NE = NE;
+        ca.final_iter = i == I - 1;
+        ca.iter = i;
+        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
+        HIPCHK(hipGetLastError());
+    }
+    // :267: the GRU state after DSSM.next(z0, action, hidden) with the returned action: [action | z0] into rows
+    // 0..B-1 of X_0 (the plan is past its last read of it), one step launch over B rows
+    const long total = (long)B * c.Kx;
+    hipLaunchKernelGGL(drnn_scatter_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, c.s,
+                       c.k.z0, c.w.Lp, action, c.k.X, B, c.w.L, c.w.A, c.w.Ap, c.Kx);
+    HIPCHK(hipGetLastError());
+    return drnn_step(x, 0, B, RowMap{1 << 30, 0, 0}, hidden, 0, hidden_out, nullptr, nullptr, 1.f, 1, 0);
+}
+
+int tdmpc_drnn_colored_noise(const tdmpc_colored_noise_params* p, const float* normals, size_t normals_floats,
+                             float* noise, size_t noise_floats, void* stream) {
+    if (!p || !normals || !noise) return TDMPC_E_NULL;
+    if (p->L < 2 || p->L > 16 || p->A <= 0 || p->A > 64 || p->batch <= 0 || p->batch > 65535 || p->n_jobs <= 0 ||
+        p->n_jobs > TDMPC_NOISE_MAX_JOBS || p->n_spectra <= 0 || p->n_spectra > TDMPC_NOISE_MAX_SPECTRA) {
+        snprintf(g_err, sizeof g_err, "coloured noise: L %d (2..16), A %d (1..64), batch %d, %d jobs (1..%d), %d spectra (1..%d)",
+                 p->L, p->A, p->batch, p->n_jobs, TDMPC_NOISE_MAX_JOBS, p->n_spectra, TDMPC_NOISE_MAX_SPECTRA);
+        return TDMPC_E_DIMS;
+    }
+    const long L = p->L, A = p->A, F = L / 2 + 1;
+    if (p->env_stride < 0 || p->normals_env < 0 || (size_t)p->batch * (size_t)p->env_stride > noise_floats ||
+        (size_t)p->batch * (size_t)p->normals_env > normals_floats) {
+        snprintf(g_err, sizeof g_err, "coloured noise: %d env streams of %ld / %ld floats exceed the buffers", p->batch,
+                 (long)p->env_stride, (long)p->normals_env);
+        return TDMPC_E_SIZE;
+    }
+    ColoredArgs a;
+    memset(&a, 0, sizeof a);
+    long max_seq = 0;
+    for (int j = 0; j < p->n_jobs; ++j) {
+        const tdmpc_noise_job& J = p->jobs[j];
+        if (J.spectrum < 0 || J.spectrum >= p->n_spectra || J.n < 0 || J.n > (1 << 20) || J.rows < 0 ||
+            J.rows > (1 << 20) || J.c0 < 0 || (long)J.c0 + J.n > J.rows || J.dst < 0 || J.src < 0) {
+            snprintf(g_err, sizeof g_err, "coloured noise: bad job %d", j);
+            return TDMPC_E_DIMS;
+        }
+        // last float written: dst + ((L - 1) rows + c0 + n) A - 1; last read: src + 2F n A - 1
+        if (J.dst + L * J.rows * A > p->env_stride || J.src + 2 * F * J.n * A > p->normals_env) {
+            snprintf(g_err, sizeof g_err, "coloured noise: job %d leaves its env's stream", j);
+            return TDMPC_E_SIZE;
+        }
+        a.jobs[j] = ColoredJob{J.spectrum, J.n, J.rows, J.c0, (long)J.dst, (long)J.src};
+        max_seq = std::max(max_seq, (long)J.n * A);
+    }
+    if (!max_seq) return 0;
+    a.L = (int)L; a.A = (int)A; a.F = (int)F; a.env_stride = p->env_stride; a.normals_env = p->normals_env;
+    a.normals = normals; a.noise = noise;
+    memcpy(a.re, p->re, sizeof a.re);
+    memcpy(a.im, p->im, sizeof a.im);
+    for (int k = 0; k < 2 * F; ++k)
+        for (int t = 0; t < L; ++t) a.dft[k][t] = p->dft[k][t];   // (rows past 2F and columns past L stay 0)
+    hipLaunchKernelGGL(drnn_colored_noise_kernel, dim3((unsigned)((max_seq + 255) / 256), p->n_jobs, p->batch), dim3(256),
+                       0, (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

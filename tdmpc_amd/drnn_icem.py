@@ -1,0 +1,412 @@
+"""`TdIcemDrnn`: the reference's recurrent-latent iCEM agent's planning API on MI355X.
+
+Reference: `TdICemSimDssm` in src/algorithm/tdmpc_icem_similarity_drnn.py:81-272 (built by train_icem_drnn.py,
+train_icem_dyna_episode_drnn.py and train_multi_experiments.py). Same constructor argument, the same model
+(`tdmpc_amd.dssm.DSSM`), checkpoint `load / save / state_dict`, planner state (`plan_horizon`, `mixture_coef`, `std`,
+`_prev_mean`, `_elite_actions`) and `plan(obs, hidden, eval_mode=False, step=None, t0=True) -> (action [A],
+hidden [1, Hd], metrics)`. The whole plan is one `tdmpc_drnn_plan_icem` call (include/tdmpc_drnn.h): the iCEM order
+of work of `TdICEM` with the rollout step on drnn_step_kernel from the env's GRU state, and at the end the GRU state
+after `DSSM.next(z0, action, hidden)` with the returned action (:267).
+
+Where this agent's file differs from the MLP one (tdmpc_icem_similarity_mlp.py) and this class follows it (:204-234):
+reused elites enter only when `not t0`, in every iteration (E_i = 0 for the whole call at an episode start); all N_i
+samples of an iteration come from `sample_action_sequence` -- coloured with cfg.noise_beta over plan_horizon samples
+when it is > 0, white otherwise -- not from white / pink / brown thirds; `extend_horizon` can only be set on a t0
+call and reuse happens only on a non-t0 call, so the elite horizon at reuse always equals the plan horizon.
+
+Randomness: `rng="reference"` consumes torch's device generator and numpy's global generator in the reference's
+order (the coloured sequences through tdmpc_amd.colored_noise, as `TdICEM`); `rng="device"` draws the call's streams
+with one normal_, the spectrum normals with another and turns them into every coloured block of every env with one
+`tdmpc_drnn_colored_noise` launch; `plan(..., noise=IcemNoise-like)` takes explicit draws (parity tests).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from copy import deepcopy
+
+import numpy as np
+import torch
+
+from . import _lib
+from .colored_noise import irfft_matrices, powerlaw_psd_gaussian, spectrum_rows
+from .config import linear_schedule
+from .drnn import DrnnPlanner
+from .dssm import DSSM, check_dssm_cfg
+from .tdmpc import _discount_pows
+
+
+def colored_noise_params(L, A, batch, env_stride, normals_env, jobs, betas):
+    """tdmpc_colored_noise_params for sequences of L samples: jobs = [(spectrum, n, rows, c0, dst, src)], betas = the
+    spectra's exponents. Factor rows and the inverse-DFT matrix are computed in float64 and passed as float32."""
+    if not 2 <= L <= 16:
+        raise ValueError(f"coloured noise needs 2..16 samples per sequence, not {L}")
+    if len(jobs) > _lib.NOISE_MAX_JOBS or len(betas) > _lib.NOISE_MAX_SPECTRA:
+        raise ValueError(f"{len(jobs)} jobs / {len(betas)} spectra (at most {_lib.NOISE_MAX_JOBS} / "
+                         f"{_lib.NOISE_MAX_SPECTRA})")
+    p = _lib.ColoredNoiseParams()
+    p.L, p.A, p.batch, p.n_jobs, p.n_spectra = L, A, batch, len(jobs), len(betas)
+    p.env_stride, p.normals_env = env_stride, normals_env
+    for j, (sp, n, rows, c0, dst, src) in enumerate(jobs):
+        J = p.jobs[j]
+        J.spectrum, J.n, J.rows, J.c0, J.dst, J.src = sp, n, rows, c0, dst, src
+    F = L // 2 + 1
+    for s, beta in enumerate(betas):
+        re, im, inv = spectrum_rows(beta, L)
+        for k in range(F):
+            p.re[s][k] = float(re[k] * inv)
+            p.im[s][k] = float(im[k] * inv)
+    Cr, Ci = irfft_matrices(L)
+    for k, row in enumerate(np.concatenate([Cr, Ci])):
+        for t in range(L):
+            p.dft[k][t] = float(row[t])
+    return p
+
+
+def colored_noise(L_lib, params, normals, noise, stream=None):
+    """One tdmpc_drnn_colored_noise launch: normals (flat float32 device tensor) -> blocks of `noise` (flat)."""
+    if stream is None:
+        stream = torch.cuda.current_stream(noise.device).cuda_stream
+    rc = L_lib.tdmpc_drnn_colored_noise(C.byref(params), C.c_void_p(normals.data_ptr()), normals.numel(),
+                                        C.c_void_p(noise.data_ptr()), noise.numel(), C.c_void_p(stream))
+    _lib.check(rc, "tdmpc_drnn_colored_noise")
+
+
+class IcemDrnnPlanner(DrnnPlanner):
+    """DrnnPlanner with the iCEM workspace (N + K + num_pi rows per env) and noise stream bound; `ddims.base.num_pi`
+    stays at the schedule's largest value (the calls pass their own counts in tdmpc_icem_params)."""
+
+    def _query_sizes(self):
+        sz = _lib.Sizes()
+        _lib.check(self.L.tdmpc_drnn_icem_sizes_for(C.byref(self.ddims), C.byref(sz)), "tdmpc_drnn_icem_sizes_for")
+        return sz
+
+
+class TdIcemDrnn:
+    """Drop-in for the reference `TdICemSimDssm` planning interface (tdmpc_icem_similarity_drnn.py:81-272)."""
+
+    MAX_GRAPHS = 8   # captured plans kept per agent
+    METRICS0 = {"external_reward_mean": 0.0, "current_std": 0.0}
+
+    def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", graph: bool = True):
+        check_dssm_cfg(cfg)
+        if rng not in ("reference", "device"):
+            raise ValueError("rng: 'reference' or 'device'")
+        if not 1 <= int(cfg.iterations) <= 16:
+            raise ValueError("iCEM: 1..16 iterations")
+        self.cfg = cfg
+        self.rng = rng
+        self.graph = graph
+        self.device = torch.device(cfg.device)
+        self.std = linear_schedule(cfg.std_schedule, 0)                       # :87
+        self.mixture_coef = linear_schedule(cfg.regularization_schedule, 0)   # :88
+        self.model = DSSM(cfg).to(self.device)                                # :89
+        self.model_target = deepcopy(self.model)
+        self.model.eval()
+        self.model_target.eval()
+        self.plan_horizon = 1                                                 # :98
+        self.max_batch = max_batch
+        pl = self.planner = IcemDrnnPlanner(cfg, max_batch=max_batch, device=self.device)
+        dev = self.device
+        A, K, N, H = cfg.action_dim, cfg.num_elites, cfg.num_samples, cfg.horizon
+        self.P_max = pl.pmax
+        self.E_max = int(cfg.fraction_elites_reused * K)
+        self.Tw = N + K + self.P_max
+        self.elites = torch.zeros(max_batch, H, K, A, dtype=torch.float32, device=dev)
+        self.hidden_out = torch.zeros(max_batch, pl.hidden_dim, dtype=torch.float32, device=dev)
+        # spectrum normals of one call (rng 'device') and the host-drawn coloured blocks (rng 'reference'), per env
+        self._col_max = cfg.iterations * H * N * A + H * self.E_max * A
+        F_max = H // 2 + 1
+        self._normals = torch.zeros(max_batch * 2 * F_max * (cfg.iterations * N + self.E_max) * A,
+                                    dtype=torch.float32, device=dev)
+        self._stage = torch.empty(max_batch * self._col_max, dtype=torch.float32, device=dev)
+        self._pinned = torch.empty(max_batch * self._col_max, dtype=torch.float32, pin_memory=dev.type == "cuda")
+        self._h2d_done = None
+        self._noise_params = {}
+        self._has_prev = False
+        self._has_elites = False
+
+    # ------------------------------------------------------------------ reference state
+    @property
+    def _prev_mean(self):
+        if not self._has_prev:
+            raise AttributeError("_prev_mean")
+        return self.planner.prev_mean_view(self.plan_horizon, 1)[0]
+
+    @property
+    def _elite_actions(self):
+        if not self._has_elites:
+            raise AttributeError("_elite_actions")
+        return self.elites[0, :self.plan_horizon]
+
+    def state_dict(self):
+        return {"model": self.model.state_dict(), "model_target": self.model_target.state_dict()}
+
+    def save(self, fp):
+        torch.save(self.state_dict(), fp)
+
+    def load(self, fp):
+        """A reference checkpoint ({'model': sd, 'model_target': sd}): weights_only, strict keys."""
+        d = torch.load(fp, map_location=self.device, weights_only=True)
+        self.model.load_state_dict(d["model"])
+        self.model_target.load_state_dict(d["model_target"])
+
+    # ------------------------------------------------------------------ counts and layout
+    def counts(self, mixture, has_elites, t0):
+        """(N_i, P_i, E_i) per iteration (:205-215): reused elites only inside an episode."""
+        cfg, out, n = self.cfg, [], self.cfg.num_samples
+        for i in range(cfg.iterations):
+            if i > 0:
+                n = max(2 * cfg.num_elites, int(n / cfg.factor_decrease_num))
+            p = int(mixture * n)
+            e = self.E_max if (cfg.fraction_elites_reused > 0 and not t0 and (has_elites or i > 0)) else 0
+            out.append((n, p, e))
+        return out
+
+    def layout(self, H, cts, reuse):
+        """Per-env noise stream offsets (floats): the pre-rollout's draws, per iteration [samples | at i = 0 with
+        reuse the fresh elite tail | terminal policy noise], the action noise."""
+        A = self.cfg.action_dim
+        off = {"pi": 0, "samp": [], "term": [], "reuse": 0}
+        o = H * cts[0][1] * A
+        for i, (n, p, e) in enumerate(cts):
+            off["samp"].append(o)
+            o += H * n * A
+            if i == 0 and reuse:
+                off["reuse"] = o
+                o += H * e * A
+            off["term"].append(o)
+            o += (n + e + p) * A
+        off["act"] = o
+        off["total"] = o + A
+        return off
+
+    def _colored_blocks(self, H, cts, off, reuse):
+        """The coloured blocks of one env's stream in draw order: (n, stream offset)."""
+        out = []
+        for i, (n, p, e) in enumerate(cts):
+            out.append((n, off["samp"][i]))
+            if i == 0 and reuse:
+                out.append((e, off["reuse"]))
+        return out
+
+    # ------------------------------------------------------------------ draws
+    def _draw_device(self, B, H, cts, off, reuse):
+        """rng 'device': the B streams white in one draw; with noise_beta > 0 the spectrum normals in a second draw and
+        one tdmpc_drnn_colored_noise launch over every sample block and reuse tail of every env; the picks' uniforms."""
+        pl, cfg = self.planner, self.cfg
+        S = off["total"]
+        pl.noise_flat[:B * S].normal_()
+        if cfg.noise_beta > 0:
+            key = (H, tuple(cts), reuse, B)
+            ent = self._noise_params.get(key)
+            if ent is None:
+                A, F = cfg.action_dim, H // 2 + 1
+                jobs, src = [], 0
+                for n, dst in self._colored_blocks(H, cts, off, reuse):
+                    jobs.append((0, n, n, 0, dst, src))
+                    src += 2 * F * n * A
+                ent = (colored_noise_params(H, A, B, S, src, jobs, [cfg.noise_beta]), src)
+                if len(self._noise_params) > 16:
+                    self._noise_params.clear()
+                self._noise_params[key] = ent
+            prm, per_env = ent
+            z = self._normals[:B * per_env]
+            z.normal_()
+            colored_noise(pl.L, prm, z, pl.noise_flat[:B * S])
+        pl.u[:B].uniform_()
+
+    def _draw_reference(self, e, H, cts, off, reuse, eval_mode):
+        """Env e's stream in the reference's draw order on torch's (device) and numpy's global generators. The two
+        generators are independent, so numpy's draws (the coloured blocks, then the pick's uniform) run first on the
+        host and travel in one pinned copy; torch's follow in order."""
+        cfg, pl = self.cfg, self.planner
+        A, S, dev = cfg.action_dim, off["total"], self.device
+        buf = pl.noise_flat[e * S:(e + 1) * S]
+        blocks = self._colored_blocks(H, cts, off, reuse)
+        colored = cfg.noise_beta > 0
+        if colored:
+            host = [powerlaw_psd_gaussian(cfg.noise_beta, (n, A, H)).astype(np.float32).transpose(2, 0, 1).reshape(-1)
+                    for n, _ in blocks]
+            host = np.concatenate(host) if host else np.zeros(0, np.float32)
+        u = float(np.random.random_sample())
+        if colored and host.size:
+            if self._h2d_done is not None:
+                self._h2d_done.synchronize()   # the previous copy has left the pinned buffer
+            lo = e * self._col_max
+            stage = self._pinned[lo:lo + host.size]
+            stage.numpy()[:] = host
+            dst = self._stage[lo:lo + host.size]
+            dst.copy_(stage, non_blocking=True)
+            self._h2d_done = torch.cuda.Event()
+            self._h2d_done.record()
+            o = 0
+            for n, so in blocks:
+                buf[so:so + H * n * A].copy_(dst[o:o + H * n * A])
+                o += H * n * A
+        P0 = cts[0][1]
+        for t in range(H):
+            buf[t * P0 * A:(t + 1) * P0 * A].view(P0, A).normal_()
+        for i, (n, p, ne) in enumerate(cts):
+            if not colored:
+                buf[off["samp"][i]:off["samp"][i] + H * n * A].copy_(torch.randn(H, n, A, device=dev).view(-1))
+                if i == 0 and reuse:
+                    buf[off["reuse"]:off["reuse"] + H * ne * A].copy_(torch.randn(H, ne, A, device=dev).view(-1))
+            buf[off["term"][i]:off["term"][i] + (n + ne + p) * A].view(n + ne + p, A).normal_()
+        if not eval_mode:
+            buf[off["act"]:off["act"] + A].copy_(torch.randn(A, device=dev))
+        return u
+
+    def _load(self, e, H, cts, off, reuse, nz):
+        """Explicit draws (eps_pi [H, P0, A], samp[i] [H, N_i, A], reuse [H, E, A], term[i] [T_i, A], u, eps_act [A])
+        into env e's stream."""
+        A, S, dev = self.cfg.action_dim, off["total"], self.device
+        buf = self.planner.noise_flat[e * S:(e + 1) * S]
+        P0 = cts[0][1]
+        buf[:H * P0 * A].copy_(nz.eps_pi.reshape(-1).to(dev, torch.float32))
+        for i, (n, p, ne) in enumerate(cts):
+            buf[off["samp"][i]:off["samp"][i] + H * n * A].copy_(nz.samp[i].reshape(-1).to(dev, torch.float32))
+            if i == 0 and reuse:
+                buf[off["reuse"]:off["reuse"] + H * ne * A].copy_(nz.reuse.reshape(-1).to(dev, torch.float32))
+            buf[off["term"][i]:off["term"][i] + (n + ne + p) * A].copy_(nz.term[i].reshape(-1).to(dev, torch.float32))
+        if nz.eps_act is not None:
+            buf[off["act"]:off["act"] + A].copy_(nz.eps_act.to(dev, torch.float32))
+        return float(nz.u)
+
+    # ------------------------------------------------------------------ plan
+    @torch.no_grad()
+    def plan(self, obs, hidden, eval_mode=False, step=None, t0=True, noise=None, trace=None):
+        """:169-272 -> (action [A], hidden [1, Hd], metrics); at seed steps (uniform action, None, zero metrics)."""
+        cfg = self.cfg
+        if step < cfg.seed_steps and not eval_mode:
+            return (torch.empty(cfg.action_dim, dtype=torch.float32, device=self.device).uniform_(-1, 1), None,
+                    dict(self.METRICS0))
+        obs = torch.as_tensor(np.asarray(obs), dtype=torch.float32).view(1, -1)
+        hidden = torch.as_tensor(hidden, dtype=torch.float32).reshape(1, -1)
+        a, h, m = self._plan_envs(obs, hidden, eval_mode, step, t0, None if noise is None else [noise], trace)
+        return a[0], h, m[0]
+
+    @torch.no_grad()
+    def plan_batch(self, obs, hidden, eval_mode=False, step=None, t0=True, noise=None, trace=None):
+        """B environments at the same step / t0: obs [B, obs_dim], hidden [B, Hd] -> (actions [B, A], hidden [B, Hd],
+        metrics list). Equivalent to B reference agents sharing weights, the draws taken env by env."""
+        cfg = self.cfg
+        obs = torch.as_tensor(np.asarray(obs) if not torch.is_tensor(obs) else obs, dtype=torch.float32)
+        B = obs.shape[0]
+        if step < cfg.seed_steps and not eval_mode:
+            a = torch.empty(B, cfg.action_dim, dtype=torch.float32, device=self.device)
+            for e in range(B):
+                a[e].uniform_(-1, 1)
+            return a, None, [dict(self.METRICS0) for _ in range(B)]
+        hidden = torch.as_tensor(hidden, dtype=torch.float32).reshape(B, -1)
+        return self._plan_envs(obs.view(B, -1), hidden, eval_mode, step, bool(t0), noise, trace)
+
+    def _params(self, B, H, cts, off, reuse, warm, eval_mode):
+        cfg, pl = self.cfg, self.planner
+        p = _lib.IcemParams()
+        p.horizon, p.iterations, p.batch = H, cfg.iterations, B
+        p.warm_start, p.eval_mode, p.has_elites = int(warm), int(eval_mode), int(reuse)
+        p.elite_horizon = H   # (reuse happens inside an episode only, where the horizon does not move)
+        p.n_pi0 = cts[0][1]
+        p.path = _lib.PATHS["chain_x6"]
+        for i, (n, pp, e) in enumerate(cts):
+            p.n_samples[i], p.n_pi[i], p.n_elite[i] = n, pp, e
+            p.samp_off[i], p.term_off[i] = off["samp"][i], off["term"][i]
+        p.reuse_off, p.pi_off, p.act_off, p.env_stride = off["reuse"], 0, off["act"], off["total"]
+        p.min_std, p.temperature, p.momentum = cfg.min_std, cfg.temperature, cfg.momentum
+        p.one_minus_momentum = float(1 - cfg.momentum)
+        p.std_floor, p.init_std = float(self.std), 0.5
+        for t, v in enumerate(_discount_pows(cfg.discount, H)):
+            p.discount_pow[t] = v
+        p.status = pl.status.data_ptr()
+        return p
+
+    def _launch(self, p, outs):
+        pl = self.planner
+        vp = C.c_void_p
+        g = outs.get
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = pl.L.tdmpc_drnn_plan_icem(
+            C.byref(pl.ddims), C.byref(p), vp(pl.packed.data_ptr()), vp(pl.obs_buf.data_ptr()),
+            vp(pl.hidden_buf.data_ptr()), vp(pl.noise_flat.data_ptr()), vp(pl.u.data_ptr()),
+            vp(pl.prev_mean_flat.data_ptr()), vp(self.elites.data_ptr()), vp(pl.action.data_ptr()),
+            vp(pl.metrics.data_ptr()), vp(self.hidden_out.data_ptr()), vp(pl.z_in.data_ptr()),
+            vp(_lib.ptr(g("value"))), vp(_lib.ptr(g("mean"))), vp(_lib.ptr(g("std"))),
+            vp(pl.workspace.data_ptr()), pl.workspace.numel() * 4, vp(stream))
+        _lib.check(rc, "tdmpc_drnn_plan_icem")
+
+    def _plan_envs(self, obs, hidden, eval_mode, step, t0, noise, trace):
+        cfg, pl = self.cfg, self.planner
+        B = obs.shape[0]
+        if B > pl.max_batch:
+            raise ValueError(f"batch {B} > max_batch {pl.max_batch}")
+        if hidden.shape != (B, pl.hidden_dim):
+            raise ValueError(f"hidden must be [{B}, {pl.hidden_dim}], not {tuple(hidden.shape)}")
+        horizon = int(min(cfg.horizon, linear_schedule(cfg.horizon_schedule, step)))   # :179-182
+        if horizon != self.plan_horizon and t0:
+            self.plan_horizon = horizon
+        H = self.plan_horizon
+        self.mixture_coef = linear_schedule(cfg.regularization_schedule, step)
+        cts = self.counts(self.mixture_coef, self._has_elites, t0)
+        if any(p <= 0 for _, p, _ in cts):
+            raise AssertionError("num_pi_trajs > 0")   # the reference asserts this (:193, :209)
+        if cts[0][1] > self.P_max:
+            raise ValueError("mixture_coef above the schedule's maximum")
+        if any(e > 0 for _, _, e in cts[1:]) and not cfg.keep_previous_elites:
+            # the reference would re-use the first iteration's `reused_actions` (a stale loop variable), or none
+            raise NotImplementedError("fraction_elites_reused > 0 needs keep_previous_elites")
+        if cts[0][2] > 0 and not cfg.shift_elites_over_time:
+            raise NotImplementedError("fraction_elites_reused > 0 needs shift_elites_over_time once elites exist "
+                                      "(the reference's `reused_actions` is unbound there)")
+        if cfg.noise_beta > 0 and H < 2:
+            raise ValueError("coloured noise (noise_beta > 0) has no spectrum for a plan horizon of 1: the generator "
+                             "raises at one sample; use noise_beta = 0 or a horizon_schedule starting at 2")
+        reuse = cts[0][2] > 0
+        warm = (not t0) and self._has_prev
+        off = self.layout(H, cts, reuse)
+        if B * off["total"] > pl.noise_flat.numel():
+            raise ValueError("noise stream exceeds the planner's buffer")
+        pl.pack(self.model)
+        pl.hidden_buf[:B].copy_(hidden.to(self.device))
+        pl.obs_buf[:B].copy_(obs.to(self.device))
+        if noise is not None:
+            us = [self._load(e, H, cts, off, reuse, nz) for e, nz in enumerate(noise)]
+            pl.u[:B].copy_(torch.tensor(us, dtype=torch.float64))
+        elif self.rng == "reference":
+            us = [self._draw_reference(e, H, cts, off, reuse, eval_mode) for e in range(B)]
+            pl.u[:B].copy_(torch.tensor(us, dtype=torch.float64))
+        p = self._params(B, H, cts, off, reuse, warm, eval_mode)
+        outs = {}
+        if trace is not None:
+            I, A, dev = cfg.iterations, cfg.action_dim, self.device
+            outs = dict(value=torch.zeros(B, I, self.Tw, device=dev), mean=torch.zeros(B, I, H, A, device=dev),
+                        std=torch.zeros(B, I, H, A, device=dev))
+        device_rng = noise is None and self.rng == "device"
+
+        def device_work():
+            if device_rng:
+                self._draw_device(B, H, cts, off, reuse)
+            self._launch(p, outs)
+
+        if self.graph and noise is None and trace is None:
+            key = (H, B, tuple(cts), reuse, warm, bool(eval_mode), float(self.std), self.rng)
+            ent = pl._graphs.get(key)
+            if ent is None:
+                while len(pl._graphs) >= self.MAX_GRAPHS:
+                    pl._graphs.pop(next(iter(pl._graphs)))
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    device_work()
+                ent = pl._graphs[key] = (g, p)   # (p holds nothing the graph reads after capture; kept for inspection)
+            ent[0].replay()
+        else:
+            device_work()
+        if trace is not None:
+            trace.update(value=[outs["value"][:, i, :n + e + pp] for i, (n, pp, e) in enumerate(cts)],
+                         mean=outs["mean"], std=outs["std"], counts=cts, z_in=pl.z_in[:B].clone())
+        self._has_prev = True
+        self._has_elites = True
+        ms = pl._ms_dev[:4 + 2 * B].cpu()
+        pl.raise_status(int(ms[:1].view(torch.int32)[0]))
+        m = ms[4:4 + 2 * B].view(B, 2).double().tolist()
+        return (pl.action[:B].clone(), self.hidden_out[:B].clone(),
+                [{"external_reward_mean": float(r), "current_std": float(s)} for r, s in m])
