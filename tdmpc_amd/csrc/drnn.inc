@@ -1,7 +1,10 @@
 // drnn.inc -- the recurrent-latent (DSSM) rollout step for gfx950 and its C ABI (include/tdmpc_drnn.h).
 // Included twice from tdmpc_kernels.hip: once beside plan1.inc / wide_step.inc for the device code (it shares the x6
 // helpers and the row-block idiom of chain_kernel), once at the end of the file (DRNN_HOST) for the host side, which
-// shares Ctx, the pack table and the profiler.
+// shares Ctx, the pack table and the profiler. The planning algorithms' launch sequences are not here: the CEM plan,
+// the iCEM plan, estimate_value and the policy pre-rollout are tdmpc_kernels.hip's drivers (cem_run, icem_run,
+// estimate_value_run, pi_rollout_run), which this file instantiates with its own step (DrnnStep); its entry points
+// keep the setup, the z_out copy and the final DSSM.next for hidden_out.
 //
 // Reference: DSSM.next (src/algorithm/tdmpc_similarity_drnn.py:57-60) = DGruDyna (models/gru_dyna.py:25-29: a
 // NormGRUCell over [z, a], then prior_mlp = Linear - BatchNorm1d - ELU - Linear on the new hidden) and the reward MLP
@@ -505,6 +508,24 @@ int drnn_step(const DrnnCtx& x, int t, int rows, RowMap map, const float* hin, i
     return 0;
 }
 
+// The step functor of tdmpc_kernels.hip's drivers: a rollout's rows start from their env's hidden state (row m of a
+// map with G rows per env from hidden[m / G]) and carry their own through the ping-pong buffers after that.
+struct DrnnStep {
+    const DrnnCtx& x; const float* hidden;
+    int operator()(int t, int rows, RowMap map, float disc, int first, int last, int) const {
+        return drnn_step(x, t, rows, map, t == 0 ? hidden : nullptr, map.G, nullptr, x.c.k.G, x.c.k.rlast, disc, first,
+                         last);
+    }
+};
+
+// the encoder's z0 [B][Lp] -> the caller's z_out [B][L] (optional)
+int drnn_z_out(const Ctx& c, float* z_out) {
+    if (!z_out) return 0;
+    hipLaunchKernelGGL(drnn_copy_rows_kernel, dim3(c.B), dim3(256), 0, c.s, c.k.z0, c.w.Lp, z_out, c.w.L, c.w.L, c.B);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // The job list of tdmpc_drnn_pack_weights from the DRNN_NT tensors t: the shared heads' jobs (pack_jobs, heads only),
 // then the DSSM regions' (DrnnLayout). Returns the number of head jobs in front.
 int drnn_pack_jobs(const Layout& w, const DrnnLayout& dl, const float* const* t, std::vector<PackJob>& jobs) {
@@ -673,29 +694,10 @@ int tdmpc_drnn_estimate_value(const tdmpc_drnn_dims* d, const tdmpc_plan_params*
         return TDMPC_E_NULL;
     DrnnCtx x;
     int rc;
-    const int H = prm->horizon, B = prm->batch;
-    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, prm->batch, prm->horizon, 1, (hipStream_t)stream))) return rc;
     if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
-    Ctx& c = x.c;
-    if (rows != c.T) { snprintf(g_err, sizeof g_err, "rows must equal N+P"); return TDMPC_E_DIMS; }
-    const int T = c.T;
-    if ((rc = load_z0(c, z0))) return rc;
-    hipLaunchKernelGGL(scatter_actions_kernel, dim3(512), dim3(256), 0, c.s, actions, c.k.X, c.k.x_stride, H, T, c.A,
-                       c.w.Ap, c.Kx, B, T, 0);
-    HIPCHK(hipGetLastError());
-    const RowMap all = {T, T, 0};
-    for (int t = 0; t < H; ++t)
-        if ((rc = drnn_step(x, t, B * T, all, t == 0 ? h0 : nullptr, T, nullptr, c.k.G, c.k.rlast, prm->discount_pow[t],
-                            t == 0, t == H - 1)))
-            return rc;
-    if ((rc = policy(c, H, B * T, all, eps_term, (long)T * c.A, T, 0, prm->min_std))) return rc;
-    if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
-    hipLaunchKernelGGL(qvalue_kernel, dim3((B * T + 255) / 256), dim3(256), 0, c.s, c.k.G, c.k.qv, c.k.xrows,
-                       prm->discount_pow[H], c.k.value, B * T);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(drnn_copy2_kernel, dim3(64), dim3(256), 0, c.s, c.k.value, value, c.k.rlast, reward_last, B * T);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (rows != x.c.T) { snprintf(g_err, sizeof g_err, "rows must equal N+P"); return TDMPC_E_DIMS; }
+    return estimate_value_run(x.c, DrnnStep{x, h0}, prm, z0, actions, eps_term, value, reward_last, nullptr);
 }
 
 int tdmpc_drnn_pi_rollout(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, const void* packed, const float* z0,
@@ -704,25 +706,9 @@ int tdmpc_drnn_pi_rollout(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm
     if (!d || !prm || !packed || !z0 || !h0 || !eps_pi || !pi_actions || !workspace) return TDMPC_E_NULL;
     DrnnCtx x;
     int rc;
-    const int H = prm->horizon, B = prm->batch;
-    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, prm->batch, prm->horizon, 1, (hipStream_t)stream))) return rc;
     if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
-    Ctx& c = x.c;
-    const int N = c.N, P = c.P, T = c.T;
-    const long A = c.A;
-    if (P <= 0) { snprintf(g_err, sizeof g_err, "num_pi is 0"); return TDMPC_E_DIMS; }
-    if ((rc = load_z0(c, z0))) return rc;
-    const RowMap pm = {P, T, N};
-    for (int t = 0; t < H; ++t) {
-        if ((rc = policy(c, t, B * P, pm, eps_pi, (long)H * P * A, P, (long)t * P * A, prm->min_std))) return rc;
-        if (t < H - 1 && (rc = drnn_step(x, t, B * P, pm, t == 0 ? h0 : nullptr, P, nullptr, nullptr, nullptr, 1.f,
-                                          t == 0, 0)))
-            return rc;
-    }
-    hipLaunchKernelGGL(gather_actions_kernel, dim3(512), dim3(256), 0, c.s, c.k.X, c.k.x_stride, H, P, c.A, c.Kx, B, T,
-                       N, pi_actions);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return pi_rollout_run(x.c, DrnnStep{x, h0}, prm, z0, eps_pi, pi_actions);
 }
 
 int tdmpc_drnn_plan(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, const void* packed, const void* obs,
@@ -733,58 +719,18 @@ int tdmpc_drnn_plan(const tdmpc_drnn_dims* d, const tdmpc_plan_params* prm, cons
         return TDMPC_E_NULL;
     DrnnCtx x;
     int rc;
-    const int H = prm->horizon, I = prm->iterations, B = prm->batch;
-    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream))) return rc;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, prm->batch, prm->horizon, prm->iterations,
+                         (hipStream_t)stream)))
+        return rc;
     if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
     Ctx& c = x.c;
-    const int N = c.N, P = c.P, T = c.T;
     // z0 = h(obs) and mean = 0 (warm: prev_mean shifted), std = 2
-    if ((rc = encode(c, obs, 0, B, prev_mean, prm->warm_start, 0, 2.f, prm->warm_flags))) return rc;
-    if (z_out) {
-        hipLaunchKernelGGL(drnn_copy_rows_kernel, dim3(B), dim3(256), 0, c.s, c.k.z0, c.w.Lp, z_out, c.w.L, c.w.L, B);
-        HIPCHK(hipGetLastError());
-    }
-    if ((rc = prep(c, noise, 0, c.k.z0))) return rc;
-    // The policy pre-rollout (tdmpc_similarity_drnn.py:203-209) fused with CEM iteration 0, as tdmpc_plan: at each
-    // step the policy rows get pi(z_t), then one step launch advances all T rows of every env from the env's hidden.
-    // The policy rows' rollout is the same in every iteration, so later iterations roll out the N sampled rows only.
-    const RowMap all = {T, T, 0}, pm = {P, T, N}, rm = {N, T, 0};
-    if (P > 0) {
-        for (int t = 0; t < H; ++t) {
-            if ((rc = policy(c, t, B * P, pm, noise, c.eps_env, P, (long)t * P * c.A, prm->min_std))) return rc;
-            if ((rc = drnn_step(x, t, B * T, all, t == 0 ? hidden : nullptr, T, nullptr, c.k.G, c.k.rlast,
-                                prm->discount_pow[t], t == 0, t == H - 1)))
-                return rc;
-        }
-    }
-    CemArgs ca = cem_args0(c);
-    ca.I = I;
-    ca.eps = noise; ca.eps_env = c.eps_env; ca.eps_cem_off = c.eps_cem_off; ca.eps_iter = c.eps_iter;
-    ca.eps_act_off = c.eps_act_off; ca.u = u; ca.prev_mean = prev_mean;
-    ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
-    ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
-    ca.std_floor_p = prm->std_floor_dev;
-    ca.elite_out = elite_out; ca.score_out = score_out; ca.mean_out = mean_out; ca.std_out = std_out;
-    ca.value_out = value_out;
-    ca.status = prm->status;
-    ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H];   // (chain Q: q1, q2 per row)
-    const size_t cem_lds = cem_lds_bytes(T, H, ca.K, c.A);
-    for (int i = 0; i < I; ++i) {
-        const long toff = c.eps_cem_off + (long)i * c.eps_iter + c.eps_term_off;
-        if (i > 0 && (rc = prep(c, noise, i, nullptr))) return rc;
-        if (i > 0 || P == 0)
-            for (int t = 0; t < H; ++t)
-                if ((rc = drnn_step(x, t, B * N, rm, t == 0 ? hidden : nullptr, N, nullptr, c.k.G, c.k.rlast,
-                                    prm->discount_pow[t], t == 0, t == H - 1)))
-                    return rc;
-        if ((rc = policy(c, H, B * T, all, noise, c.eps_env, T, toff, prm->min_std))) return rc;
-        if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
-        ca.final_iter = i == I - 1;
-        ca.iter = i;
-        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
+    if ((rc = encode(c, obs, 0, c.B, prev_mean, prm->warm_start, 0, 2.f, prm->warm_flags))) return rc;
+    if ((rc = drnn_z_out(c, z_out))) return rc;
+    // tdmpc_similarity_drnn.py:203-262 is tdmpc_plan's sequence with DSSM.next for the step, every row starting from
+    // its env's hidden. None of the TOLD fast forms: they are other launch sequences with other rounding.
+    return cem_run(c, DrnnStep{x, hidden}, PlanFast{}, prm, noise, u, prev_mean, action, metrics, elite_out, score_out,
+                   value_out, mean_out, std_out);
 }
 
 int tdmpc_drnn_icem_sizes_for(const tdmpc_drnn_dims* d, tdmpc_sizes* out) {
@@ -815,94 +761,25 @@ int tdmpc_drnn_plan_icem(const tdmpc_drnn_dims* d, const tdmpc_icem_params* prm,
         return TDMPC_E_NULL;
     DrnnCtx x;
     int rc;
-    const int H = prm->horizon, I = prm->iterations, B = prm->batch, K = d->base.num_elites;
-    if (I <= 0 || I > 16) { snprintf(g_err, sizeof g_err, "drnn iCEM: 1..16 iterations"); return TDMPC_E_DIMS; }
-    if (!drnn_icem_dims_ok(d->base)) return TDMPC_E_DIMS;
-    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream, K))) return rc;
+    if (!icem_counts_ok(prm, &d->base, "drnn iCEM") || !drnn_icem_dims_ok(d->base)) return TDMPC_E_DIMS;
+    if ((rc = drnn_setup(x, d, packed, workspace, ws_bytes, prm->batch, prm->horizon, prm->iterations,
+                         (hipStream_t)stream, d->base.num_elites)))
+        return rc;
     if (resolve_path(prm->path, true) < 0) return TDMPC_E_DIMS;   // (checked as in the TOLD entry points; the path itself is fixed)
     Ctx& c = x.c;
-    const int N = d->base.num_samples, Pmax = d->base.num_pi, Tw = N + K + Pmax, pi_base = N + K, P0 = prm->n_pi0;
-    c.T = Tw;
-    if (P0 <= 0 || P0 > Pmax || prm->n_samples[0] != N) {
-        snprintf(g_err, sizeof g_err, "drnn iCEM: bad counts");
-        return TDMPC_E_DIMS;
-    }
-    for (int i = 0; i < I; ++i) {
-        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i];
-        if (Ni <= 0 || Ni > N || Pi <= 0 || Pi > P0 || Ei < 0 || Ei > K || Ni + Ei + Pi < K ||
-            (Ei > 0 && i == 0 && !prm->has_elites) ||
-            (i == 0 && Ei > 0 && prm->elite_horizon != H && prm->elite_horizon != H - 1)) {
-            snprintf(g_err, sizeof g_err, "drnn iCEM: bad counts at iteration %d", i);
-            return TDMPC_E_DIMS;
-        }
-    }
-    const long A = c.A, env = prm->env_stride;
     // z0 = h(obs); mean = 0 (warm: mean[:-1] = prev[1:], mean[-1] = prev[-1]), std = init_std (0.5)
-    if ((rc = encode(c, obs, 0, B, prev_mean, prm->warm_start, 1, prm->init_std))) return rc;
-    if (z_out) {
-        hipLaunchKernelGGL(drnn_copy_rows_kernel, dim3(B), dim3(256), 0, c.s, c.k.z0, c.w.Lp, z_out, c.w.L, c.w.L, B);
-        HIPCHK(hipGetLastError());
-    }
-    // The policy pre-rollout of the P0 policy rows (tdmpc_icem_similarity_drnn.py:197-202), hidden carried from the
-    // env's state: their G, last reward and z_H are the same in every iteration, so they are computed once
-    const RowMap pm0 = {P0, Tw, pi_base};
-    if ((rc = prep(c, nullptr, 0, c.k.z0))) return rc;   // z0 into X_0's latent columns, all Tw rows
-    for (int t = 0; t < H; ++t) {
-        if ((rc = policy(c, t, B * P0, pm0, noise, env, P0, prm->pi_off + (long)t * P0 * A, prm->min_std))) return rc;
-        if ((rc = drnn_step(x, t, B * P0, pm0, t == 0 ? hidden : nullptr, P0, nullptr, c.k.G, c.k.rlast,
-                            prm->discount_pow[t], t == 0, t == H - 1)))
-            return rc;
-    }
-    CemArgs ca = cem_args0(c);   // (c.T = Tw; N, P, T, NE per iteration below)
-    ca.I = I; ca.pi_base = pi_base;
-    ca.eps = noise; ca.eps_env = env; ca.eps_act_off = prm->act_off; ca.u = u; ca.prev_mean = prev_mean;
-    ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
-    ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
-    ca.mean_out = mean_out; ca.std_out = std_out; ca.elite_store = elites;
-    ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H]; ca.value_out = value_out;
-    ca.status = prm->status;
-    const size_t cem_lds = cem_lds_bytes(Tw, H, K, c.A);
-    for (int i = 0; i < I; ++i) {
-        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i], NE = Ni + Ei;
-        // sampled candidates clamp(mean + std * noise) for rows [0, Ni) (sample_action_sequence)
-        if ((rc = prep_launch(c, noise, Ni, env, prm->samp_off[i], nullptr, nullptr))) return rc;
-        if (Ei > 0 || i == I - 1) {
-            FillArgs fa;
-            memset(&fa, 0, sizeof fa);
-            fa.X = c.k.X; fa.x_stride = c.k.x_stride; fa.Kx = c.Kx; fa.apq = c.w.Ap / 4; fa.Tw = Tw;
-            fa.B = B; fa.H = H; fa.A = c.A; fa.Hmax = d->base.max_horizon; fa.K = K;
-            fa.n0 = Ni; fa.E = Ei; fa.mode = i == 0 ? 1 : 2; fa.eH = prm->elite_horizon; fa.mean_row = i == I - 1;
-            fa.mean = c.k.mean; fa.stdv = c.k.stdv; fa.elites = elites;
-            fa.eps = noise; fa.eps_env = env; fa.reuse_off = prm->reuse_off;
-            const long tot = (long)B * H * fa.apq * (Ei + fa.mean_row);
-            hipLaunchKernelGGL(icem_fill_kernel, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, c.s, fa);
-            HIPCHK(hipGetLastError());
-        }
-        // rollout of the sampled + reused rows from the env's hidden state (the policy rows' is cached)
-        const RowMap blk = {NE, Tw, 0};
-        for (int t = 0; t < H; ++t)
-            if ((rc = drnn_step(x, t, B * NE, blk, t == 0 ? hidden : nullptr, NE, nullptr, c.k.G, c.k.rlast,
-                                prm->discount_pow[t], t == 0, t == H - 1)))
-                return rc;
-        // terminal value of all T_i = NE + Pi candidates: pi(z_H) with this iteration's noise, Q
-        const RowMap pmi = {Pi, Tw, pi_base};
-        if ((rc = policy(c, H, B * NE, blk, noise, env, NE, prm->term_off[i], prm->min_std))) return rc;
-        if ((rc = policy(c, H, B * Pi, pmi, noise, env, Pi, prm->term_off[i] + (long)NE * A, prm->min_std))) return rc;
-        if ((rc = terminal_q_rows(c, B * NE, blk, prm->discount_pow[H], true))) return rc;
-        if ((rc = terminal_q_rows(c, B * Pi, pmi, prm->discount_pow[H], true))) return rc;
-        ca.N = Ni; ca.P = Pi; ca.T = NE + Pi; ca.NE = NE;
-        ca.final_iter = i == I - 1;
-        ca.iter = i;
-        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
-        HIPCHK(hipGetLastError());
-    }
+    if ((rc = encode(c, obs, 0, c.B, prev_mean, prm->warm_start, 1, prm->init_std))) return rc;
+    if ((rc = drnn_z_out(c, z_out))) return rc;
+    if ((rc = icem_run(c, DrnnStep{x, hidden}, prm, noise, u, prev_mean, elites, action, metrics, value_out, mean_out,
+                       std_out)))
+        return rc;
     // :267: the GRU state after DSSM.next(z0, action, hidden) with the returned action: [action | z0] into rows
     // 0..B-1 of X_0 (the plan is past its last read of it), one step launch over B rows
-    const long total = (long)B * c.Kx;
+    const long total = (long)c.B * c.Kx;
     hipLaunchKernelGGL(drnn_scatter_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, c.s,
-                       c.k.z0, c.w.Lp, action, c.k.X, B, c.w.L, c.w.A, c.w.Ap, c.Kx);
+                       c.k.z0, c.w.Lp, action, c.k.X, c.B, c.w.L, c.w.A, c.w.Ap, c.Kx);
     HIPCHK(hipGetLastError());
-    return drnn_step(x, 0, B, RowMap{1 << 30, 0, 0}, hidden, 0, hidden_out, nullptr, nullptr, 1.f, 1, 0);
+    return drnn_step(x, 0, c.B, RowMap{1 << 30, 0, 0}, hidden, 0, hidden_out, nullptr, nullptr, 1.f, 1, 0);
 }
 
 int tdmpc_drnn_colored_noise(const tdmpc_colored_noise_params* p, const float* normals, size_t normals_floats,

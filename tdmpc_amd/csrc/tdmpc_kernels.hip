@@ -4496,17 +4496,283 @@ int load_z0(const Ctx& c, const float* z0) {
     return prep(c, nullptr, 0, c.k.z0);
 }
 
-// The CemArgs fields every entry point sets alike: the call's geometry (iCEM overrides the per-iteration row counts),
-// the workspace buffers and the pack status.
-CemArgs cem_args0(const Ctx& c) {
+// The CemArgs fields every caller of cem_kernel sets alike: the call's geometry (iCEM overrides the per-iteration row
+// counts), the workspace buffers, the pack status, and what the params struct (plan or iCEM) and the caller's pointers
+// carry under the same names. (tdmpc_cem_iter passes no eps ... metrics: with no_pick the kernel never reads them.)
+template <class Prm>
+CemArgs cem_args(const Ctx& c, const Prm* prm, const float* eps, const double* u, float* prev_mean, float* action,
+                 float* metrics, float* value_out, float* mean_out, float* std_out) {
     CemArgs ca;
     memset(&ca, 0, sizeof ca);
     ca.H = c.H; ca.N = c.N; ca.P = c.P; ca.T = ca.Tw = ca.NE = c.T; ca.A = c.A; ca.K = c.d->num_elites; ca.Kx = c.Kx;
-    ca.Hmax = c.d->max_horizon;
+    ca.Hmax = c.d->max_horizon; ca.mean = c.k.mean; ca.stdv = c.k.stdv; ca.pstatus = pack_status(c);
     ca.X = c.k.X; ca.x_stride = c.k.x_stride; ca.value = c.k.value; ca.rlast = c.k.rlast;
-    ca.mean = c.k.mean; ca.stdv = c.k.stdv;
-    ca.pstatus = pack_status(c);
+    ca.eps = eps; ca.u = u; ca.prev_mean = prev_mean;
+    ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
+    ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
+    ca.value_out = value_out; ca.mean_out = mean_out; ca.std_out = std_out; ca.status = prm->status;
     return ca;
+}
+// q1, q2 per row in k.qv (the chain / wide Q heads): cem_kernel forms the values from them and G
+void cem_args_qv(CemArgs& ca, const Ctx& c, float discH) {
+    ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = discH;
+}
+
+// ------------------------------------------------------------------------------------------------ drivers
+// Each planning algorithm's launch sequence, written once for both world models. `step` is the dynamics step of a
+// rollout, called as step(t, rows, map, disc, first, last, defer): ToldStep (TOLD.next, step_next) below, DrnnStep
+// (DSSM.next from the env's GRU state) in drnn.inc's host half. The drivers start after the entry point's encode (or
+// at load_z0), so what only one model's entry points do -- path resolution, the persistent plan, the DSSM z_out /
+// hidden_out -- stays with the entry points.
+struct ToldStep {
+    const Ctx& c;
+    int operator()(int t, int rows, RowMap map, float disc, int first, int last, int defer) const {
+        return step_next(c, t, rows, map, disc, first, last, defer);
+    }
+};
+
+// tdmpc_plan's TOLD-only fast forms, chosen by the caller (all off: the plain sequence, which is the DSSM plan's)
+struct PlanFast {
+    bool z0c;         // per-env first-layer z0 shares for the step at t = 0 (z0c_eligible)
+    bool fold;        // folded first layers where the shape allows (fold_on; Ctx::fold_ok / fold_heads / fold_policy)
+    bool wide_heads;  // terminal pi / Q on the wide heads kernel (use_wide_heads)
+    bool pi_cache;    // the policy rows' terminal pi mean cached by iteration 0 (pi_cache_on)
+};
+
+// The CEM plan (tdmpc.py:113-160) after encode.
+template <class Step>
+int cem_run(Ctx& c, const Step& step, const PlanFast& f, const tdmpc_plan_params* prm, const float* noise,
+            const double* u, float* prev_mean, float* action, float* metrics, float* elite_out, float* score_out,
+            float* value_out, float* mean_out, float* std_out) {
+    int rc;
+    const int H = c.H, I = prm->iterations, B = c.B, N = c.N, P = c.P, T = c.T;
+    if ((rc = prep(c, noise, 0, c.k.z0))) return rc;
+    if (f.z0c) {
+        if ((rc = z0c_launch(c))) return rc;
+        c.z0c_ready = 1;
+    }
+    if (f.fold) {   // latent 512: the sampled rows' rollout on the wide kernel at every t, through the folded first layer
+        const RowMap rm0 = {N, T, 0};
+        c.fold_ok = c.w.fold && H > 1 && use_wide(c, B * N, rm0, c.z0c_ready != 0) && use_wide(c, B * N, rm0, false);
+        // the terminal pi / Q of the sampled rows on the chain x6 kernels with folded first layers (the wide heads
+        // carry no folded form): then the last step stores h2 too and z_H is never formed
+        c.fold_heads = c.fold_ok && !f.wide_heads && use_x6(c) && use_chain(c, B * N, 1, CK_PI) &&
+                       use_chain(c, B * N, 2, CK_Q) && (P == 0 || use_chain(c, B * P, 2, CK_Q));
+        // the policy rows' pre-rollout (iteration 0's pi + TOLD.next on the chain kernels) through the folded layers
+        // too: needs the 32-row x6 chain kernel for their steps (its h2 epilogue)
+        if (c.fold_heads && P > 0 && use_chain(c, B * P, 2, CK_STEP) && use_chain(c, B * P, 1, CK_PI)) {
+            const ChainArgs probe = chain0(c, B * P, RowMap{P, T, N}, 0, c.Kx, 0, 2);
+            c.fold_policy = probe.rb == 32 && probe.x6;
+        }
+    }
+
+    // pi pre-rollout (tdmpc.py:113-118) fused with CEM iteration 0: at each step t the policy rows get
+    // pi(z_t) first, then ONE dynamics launch advances all T rows of every env (rollout rows with the
+    // sampled candidates, pi rows with their pi actions). The pi rows' rollout, reward prefix and z_H are
+    // identical in every CEM iteration (same z0, same pi actions), so later iterations only roll out the N
+    // sampled rows and reuse rows N..T-1 of X_t, G and rlast.
+    const RowMap all = {T, T, 0}, pm = {P, T, N}, rm = {N, T, 0};
+    if (P > 0) {
+        for (int t = 0; t < H; ++t) {
+            if ((rc = policy(c, t, B * P, pm, noise, c.eps_env, P, (long)t * P * c.A, prm->min_std, nullptr,
+                             c.fold_policy && t >= 1)))
+                return rc;
+            if ((rc = step(t, B * T, all, prm->discount_pow[t], t == 0, t == H - 1, 0))) return rc;
+        }
+    }
+    CemArgs ca = cem_args(c, prm, noise, u, prev_mean, action, metrics, value_out, mean_out, std_out);
+    ca.I = I; ca.std_floor_p = prm->std_floor_dev; ca.elite_out = elite_out; ca.score_out = score_out;
+    ca.eps_env = c.eps_env; ca.eps_cem_off = c.eps_cem_off; ca.eps_iter = c.eps_iter; ca.eps_act_off = c.eps_act_off;
+    if (f.wide_heads || c.fold_heads || use_chain(c, B * T, 2, CK_Q)) cem_args_qv(ca, c, prm->discount_pow[H]);
+    const size_t cem_lds = cem_lds_bytes(T, H, ca.K, c.A);
+
+    // The pi rows' terminal mean tanh(pi(z_H)) is the same in every iteration: the first iteration's pi launch over
+    // all T rows caches it (chain path), later ones run pi over the N sampled rows only and redraw the pi rows'
+    // TruncatedNormal sample from the cache (TDMPC_PI_CACHE=0: pi over all T rows every iteration).
+    const bool pi_cache = f.pi_cache && P > 0 && use_chain(c, B * T, 1, CK_PI);
+    for (int i = 0; i < I; ++i) {
+        const long toff = c.eps_cem_off + (long)i * c.eps_iter + c.eps_term_off;
+        if (i > 0) {
+            // wide heads: the policy rows' terminal redraw (pi_from_mu) rides in this iteration's prep launch
+            const PiMuArgs pmu = pimu_args(c, B * P, pm, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std);
+            if ((rc = prep(c, noise, i, nullptr, f.wide_heads && P > 0 ? &pmu : nullptr))) return rc;
+        }
+        if (i > 0 || P == 0)
+            for (int t = 0; t < H; ++t)
+                if ((rc = step(t, B * N, rm, prm->discount_pow[t], t == 0, t == H - 1, 1))) return rc;
+        if (f.wide_heads) {
+            if (P > 0) {
+                if (i == 0) rc = policy(c, H, B * P, pm, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std, c.k.pimu);
+                if (rc || (rc = flush_split(c))) return rc;
+            }
+            if ((rc = terminal_wide(c, noise, toff, prm->min_std))) return rc;
+        } else if (c.fold_heads) {
+            // the sampled rows' X_H holds h2_{H-1} (folded first layers), the policy rows' holds z_H: one launch each
+            if ((rc = policy(c, H, B * N, rm, noise, c.eps_env, N, toff, prm->min_std, nullptr, true))) return rc;
+            if (P > 0) {
+                if (i == 0 || !pi_cache)
+                    rc = policy(c, H, B * P, pm, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std,
+                                pi_cache ? c.k.pimu : nullptr, c.fold_policy != 0);
+                else
+                    rc = policy_from_mu(c, B * P, pm, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std);
+                if (rc) return rc;
+            }
+            if ((rc = q_chain(c, B * N, rm, nullptr, nullptr, 0, true))) return rc;
+            if (P > 0 && (rc = q_chain(c, B * P, pm, nullptr, nullptr, 0, c.fold_policy != 0))) return rc;
+        } else if (pi_cache && i > 0) {
+            if ((rc = policy(c, H, B * N, rm, noise, c.eps_env, N, toff, prm->min_std))) return rc;
+            if ((rc = flush_split(c))) return rc;
+            if ((rc = policy_from_mu(c, B * P, pm, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std)))
+                return rc;
+        } else if ((rc = policy(c, H, B * T, all, noise, c.eps_env, T, toff, prm->min_std,
+                                pi_cache ? c.k.pimu : nullptr))) {
+            return rc;
+        }
+        if (!f.wide_heads && !c.fold_heads && (rc = terminal_q(c, prm->discount_pow[H]))) return rc;
+        ca.final_iter = i == I - 1;
+        ca.iter = i;
+        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// The per-iteration counts of an iCEM call (host only, before any launch); `who` prefixes the error text.
+bool icem_counts_ok(const tdmpc_icem_params* prm, const tdmpc_dims* d, const char* who) {
+    const int H = prm->horizon, I = prm->iterations, N = d->num_samples, K = d->num_elites, P0 = prm->n_pi0;
+    if (I <= 0 || I > 16) { snprintf(g_err, sizeof g_err, "%s: 1..16 iterations", who); return false; }
+    if (P0 <= 0 || P0 > d->num_pi || prm->n_samples[0] != N) {
+        snprintf(g_err, sizeof g_err, "%s: bad counts", who);
+        return false;
+    }
+    for (int i = 0; i < I; ++i) {
+        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i];
+        if (Ni <= 0 || Ni > N || Pi <= 0 || Pi > P0 || Ei < 0 || Ei > K || Ni + Ei + Pi < K ||
+            (Ei > 0 && i == 0 && !prm->has_elites) ||
+            (i == 0 && Ei > 0 && prm->elite_horizon != H && prm->elite_horizon != H - 1)) {
+            snprintf(g_err, sizeof g_err, "%s: bad counts at iteration %d", who, i);
+            return false;
+        }
+    }
+    return true;
+}
+
+// icem_fill_kernel for iteration i: the reused elites behind its Ni sampled rows, and on the last iteration the mean row
+int icem_fill(const Ctx& c, const tdmpc_icem_params* prm, const float* noise, const float* elites, int i) {
+    const int last = i == prm->iterations - 1, Ei = prm->n_elite[i];
+    if (Ei <= 0 && !last) return 0;
+    FillArgs fa;
+    memset(&fa, 0, sizeof fa);
+    fa.X = c.k.X; fa.x_stride = c.k.x_stride; fa.Kx = c.Kx; fa.apq = c.w.Ap / 4; fa.Tw = c.T;
+    fa.B = c.B; fa.H = c.H; fa.A = c.A; fa.Hmax = c.d->max_horizon; fa.K = c.d->num_elites;
+    fa.n0 = prm->n_samples[i]; fa.E = Ei; fa.mode = i == 0 ? 1 : 2; fa.eH = prm->elite_horizon; fa.mean_row = last;
+    fa.mean = c.k.mean; fa.stdv = c.k.stdv; fa.elites = elites;
+    fa.eps = noise; fa.eps_env = prm->env_stride; fa.reuse_off = prm->reuse_off;
+    const long tot = (long)c.B * c.H * fa.apq * (Ei + fa.mean_row);
+    hipLaunchKernelGGL(icem_fill_kernel, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, c.s, fa);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The iCEM plan (tdmpc_icem_similarity_mlp.py:193-259, tdmpc_icem_similarity_drnn.py:197-262) after encode, its
+// counts checked (icem_counts_ok). Each env's block holds Tw = N + K + num_pi rows: [sampled | reused elites | pi].
+template <class Step>
+int icem_run(Ctx& c, const Step& step, const tdmpc_icem_params* prm, const float* noise, const double* u,
+             float* prev_mean, float* elites, float* action, float* metrics, float* value_out, float* mean_out,
+             float* std_out) {
+    int rc;
+    const int H = c.H, I = prm->iterations, B = c.B, K = c.d->num_elites;
+    const int Tw = c.d->num_samples + K + c.d->num_pi, pi_base = c.d->num_samples + K, P0 = prm->n_pi0;
+    const long A = c.A, env = prm->env_stride;
+    c.T = Tw;
+    // pi pre-rollout of the P0 policy rows (tdmpc_icem_similarity_mlp.py:193-199); their rollout, reward
+    // prefix and z_H are the same in every iteration (same z, same pi actions), so they are computed once
+    const RowMap pm0 = {P0, Tw, pi_base};
+    if ((rc = prep(c, nullptr, 0, c.k.z0))) return rc;   // z0 into X_0's latent columns, all Tw rows
+    for (int t = 0; t < H; ++t) {
+        if ((rc = policy(c, t, B * P0, pm0, noise, env, P0, prm->pi_off + (long)t * P0 * A, prm->min_std))) return rc;
+        if ((rc = step(t, B * P0, pm0, prm->discount_pow[t], t == 0, t == H - 1, 0))) return rc;
+    }
+    CemArgs ca = cem_args(c, prm, noise, u, prev_mean, action, metrics, value_out, mean_out, std_out);
+    ca.I = I; ca.pi_base = pi_base; ca.eps_env = env; ca.eps_act_off = prm->act_off; ca.elite_store = elites;
+    cem_args_qv(ca, c, prm->discount_pow[H]);
+    const size_t cem_lds = cem_lds_bytes(Tw, H, K, c.A);
+    for (int i = 0; i < I; ++i) {
+        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], NE = Ni + prm->n_elite[i];
+        // sampled candidates clamp(mean + std * noise) for rows [0, Ni) (sample_mix_action_sequence)
+        if ((rc = prep_launch(c, noise, Ni, env, prm->samp_off[i], nullptr, nullptr))) return rc;
+        if ((rc = icem_fill(c, prm, noise, elites, i))) return rc;
+        // rollout of the sampled + reused rows (the pi rows' is cached from the pre-rollout)
+        const RowMap blk = {NE, Tw, 0};
+        for (int t = 0; t < H; ++t)
+            if ((rc = step(t, B * NE, blk, prm->discount_pow[t], t == 0, t == H - 1, 1))) return rc;
+        // terminal value of all T_i = NE + Pi candidates: pi(z_H) with this iteration's noise, Q
+        const RowMap pmi = {Pi, Tw, pi_base};
+        if ((rc = policy(c, H, B * NE, blk, noise, env, NE, prm->term_off[i], prm->min_std))) return rc;
+        if ((rc = policy(c, H, B * Pi, pmi, noise, env, Pi, prm->term_off[i] + (long)NE * A, prm->min_std))) return rc;
+        // both row groups on the same Q path, so cem_kernel reads one kind of value (qv or value)
+        const bool qchain = use_chain(c, B * NE, 2, CK_Q) && use_chain(c, B * Pi, 2, CK_Q);
+        if ((rc = terminal_q_rows(c, B * NE, blk, prm->discount_pow[H], qchain))) return rc;
+        if ((rc = terminal_q_rows(c, B * Pi, pmi, prm->discount_pow[H], qchain))) return rc;
+        ca.qv = qchain ? c.k.qv : nullptr;
+        ca.N = Ni; ca.P = Pi; ca.T = NE + Pi; ca.NE = NE;
+        ca.final_iter = i == I - 1;
+        ca.iter = i;
+        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// estimate_value (tdmpc.py:84-92) of `actions` [B][H][T][A] from z0: value and the last step's reward per row, and
+// optionally z_H.
+template <class Step>
+int estimate_value_run(const Ctx& c, const Step& step, const tdmpc_plan_params* prm, const float* z0,
+                       const float* actions, const float* eps_term, float* value, float* reward_last, float* z_last) {
+    int rc;
+    const int H = c.H, B = c.B, T = c.T;
+    if ((rc = load_z0(c, z0))) return rc;
+    hipLaunchKernelGGL(scatter_actions_kernel, dim3(512), dim3(256), 0, c.s, actions, c.k.X, c.k.x_stride, H, T, c.A,
+                       c.w.Ap, c.Kx, B, T, 0);
+    HIPCHK(hipGetLastError());
+    const RowMap all = {T, T, 0};
+    for (int t = 0; t < H; ++t)
+        if ((rc = step(t, B * T, all, prm->discount_pow[t], t == 0, t == H - 1, 0))) return rc;
+    if (z_last) {
+        hipLaunchKernelGGL(gather_z_kernel, dim3(256), dim3(256), 0, c.s, Xt(c, H), c.Kx, c.w.Ap, c.w.L, B * T, z_last);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = policy(c, H, B * T, all, eps_term, (long)T * c.A, T, 0, prm->min_std))) return rc;
+    if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
+    if (use_chain(c, B * T, 2, CK_Q)) {
+        hipLaunchKernelGGL(qvalue_kernel, dim3((B * T + 255) / 256), dim3(256), 0, c.s, c.k.G, c.k.qv, c.k.xrows,
+                           prm->discount_pow[H], c.k.value, B * T);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(drnn_copy2_kernel, dim3(64), dim3(256), 0, c.s, c.k.value, value, c.k.rlast, reward_last, B * T);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The policy pre-rollout alone: pi(z_t) for the P policy rows at every t, where the plan keeps them (rows N..T-1 of
+// each env's block of T). The steps' returns go to the scratch G and are not read.
+template <class Step>
+int pi_rollout_run(const Ctx& c, const Step& step, const tdmpc_plan_params* prm, const float* z0, const float* eps_pi,
+                   float* pi_actions) {
+    int rc;
+    const int H = c.H, B = c.B, N = c.N, P = c.P, T = c.T;
+    const long A = c.A;
+    if (P <= 0) { snprintf(g_err, sizeof g_err, "num_pi is 0"); return TDMPC_E_DIMS; }
+    if ((rc = load_z0(c, z0))) return rc;
+    const RowMap pm = {P, T, N};
+    for (int t = 0; t < H; ++t) {
+        if ((rc = policy(c, t, B * P, pm, eps_pi, (long)H * P * A, P, (long)t * P * A, prm->min_std))) return rc;
+        if (t < H - 1 && (rc = step(t, B * P, pm, prm->discount_pow[t], t == 0, 0, 0))) return rc;
+    }
+    hipLaunchKernelGGL(gather_actions_kernel, dim3(512), dim3(256), 0, c.s, c.k.X, c.k.x_stride, H, P, c.A, c.Kx, B, T,
+                       N, pi_actions);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 #include "pack.inc"
@@ -4760,119 +5026,15 @@ int tdmpc_plan(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* pa
     const int H = prm->horizon, I = prm->iterations, B = prm->batch;
     if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream))) return rc;
     if ((c.path = resolve_path(prm->path, true)) < 0) return TDMPC_E_DIMS;
-    const int N = c.N, P = c.P, T = c.T;
     // TDMPC_PATH_PERSIST: the persistent plan where it applies (one env, supported shape), the auto path elsewhere
     if (c.path == TDMPC_PATH_PERSIST && !use_plan1(c)) c.path = TDMPC_PATH_AUTO;
     // z0 = h(obs) and mean = 0 (warm: prev_mean shifted), std = 2
     if ((rc = encode(c, obs, obs_is_u8, B, prev_mean, prm->warm_start, 0, 2.f, prm->warm_flags))) return rc;
     if (use_plan1(c))
         return plan1_launch(c, prm, noise, u, prev_mean, action, metrics, elite_out, score_out, value_out, mean_out, std_out);
-    if ((rc = prep(c, noise, 0, c.k.z0))) return rc;
-    if (z0c_eligible(c)) {
-        if ((rc = z0c_launch(c))) return rc;
-        c.z0c_ready = 1;
-    }
-    {   // latent 512: the sampled rows' rollout on the wide kernel at every t, through the folded first layer
-        const RowMap rm0 = {N, T, 0};
-        c.fold_ok = fold_on() && c.w.fold && H > 1 && use_wide(c, B * N, rm0, c.z0c_ready != 0) &&
-                    use_wide(c, B * N, rm0, false);
-        // the terminal pi / Q of the sampled rows on the chain x6 kernels with folded first layers (the wide heads
-        // carry no folded form): then the last step stores h2 too and z_H is never formed
-        c.fold_heads = c.fold_ok && !use_wide_heads(c) && use_x6(c) && use_chain(c, B * N, 1, CK_PI) &&
-                       use_chain(c, B * N, 2, CK_Q) && (P == 0 || use_chain(c, B * P, 2, CK_Q));
-        // the policy rows' pre-rollout (iteration 0's pi + TOLD.next on the chain kernels) through the folded layers
-        // too: needs the 32-row x6 chain kernel for their steps (its h2 epilogue)
-        if (c.fold_heads && P > 0 && use_chain(c, B * P, 2, CK_STEP) && use_chain(c, B * P, 1, CK_PI)) {
-            const ChainArgs probe = chain0(c, B * P, RowMap{P, T, N}, 0, c.Kx, 0, 2);
-            c.fold_policy = probe.rb == 32 && probe.x6;
-        }
-    }
-
-    // pi pre-rollout (tdmpc.py:113-118) fused with CEM iteration 0: at each step t the policy rows get
-    // pi(z_t) first, then ONE TOLD.next launch advances all T rows of every env (rollout rows with the
-    // sampled candidates, pi rows with their pi actions). The pi rows' rollout, reward prefix and z_H are
-    // identical in every CEM iteration (same z0, same pi actions), so later iterations only roll out the N
-    // sampled rows and reuse rows N..T-1 of X_t, G and rlast.
-    const RowMap all = {T, T, 0};
-    const RowMap pm = {P, T, N};
-    const RowMap rm = {N, T, 0};
-    if (P > 0) {
-        for (int t = 0; t < H; ++t) {
-            if ((rc = policy(c, t, B * P, pm, noise, c.eps_env, P, (long)t * P * c.A, prm->min_std, nullptr,
-                             c.fold_policy && t >= 1)))
-                return rc;
-            if ((rc = step_next(c, t, B * T, all, prm->discount_pow[t], t == 0, t == H - 1)))
-                return rc;
-        }
-    }
-    CemArgs ca = cem_args0(c);
-    ca.I = I;
-    ca.eps = noise; ca.eps_env = c.eps_env; ca.eps_cem_off = c.eps_cem_off; ca.eps_iter = c.eps_iter;
-    ca.eps_act_off = c.eps_act_off; ca.u = u; ca.prev_mean = prev_mean;
-    ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
-    ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
-    ca.std_floor_p = prm->std_floor_dev;
-    ca.elite_out = elite_out; ca.score_out = score_out; ca.mean_out = mean_out; ca.std_out = std_out;
-    ca.value_out = value_out;
-    ca.status = prm->status;
-    const bool wide_heads = use_wide_heads(c);
-    if (wide_heads || c.fold_heads || use_chain(c, B * T, 2, CK_Q)) {   // q1, q2 per row in k.qv; cem_kernel forms the values
-        ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H];
-    }
-    const size_t cem_lds = cem_lds_bytes(T, H, ca.K, c.A);
-
-    // The pi rows' terminal mean tanh(pi(z_H)) is the same in every iteration: the first iteration's pi launch over
-    // all T rows caches it (chain path), later ones run pi over the N sampled rows only and redraw the pi rows'
-    // TruncatedNormal sample from the cache (TDMPC_PI_CACHE=0: pi over all T rows every iteration).
-    const bool pi_cache = pi_cache_on() && P > 0 && use_chain(c, B * T, 1, CK_PI);
-    const RowMap pmH = {P, T, N};
-    for (int i = 0; i < I; ++i) {
-        const long toff = c.eps_cem_off + (long)i * c.eps_iter + c.eps_term_off;
-        // wide heads: the policy rows' terminal redraw (pi_from_mu) rides in this iteration's prep launch
-        const bool pm_in_prep = wide_heads && P > 0 && i > 0;
-        if (i > 0) {
-            const PiMuArgs pm = pimu_args(c, B * P, pmH, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std);
-            if ((rc = prep(c, noise, i, nullptr, pm_in_prep ? &pm : nullptr))) return rc;
-        }
-        if (i > 0 || P == 0)
-            for (int t = 0; t < H; ++t)
-                if ((rc = step_next(c, t, B * N, rm, prm->discount_pow[t], t == 0, t == H - 1, 1)))
-                    return rc;
-        if (wide_heads) {
-            if (P > 0) {
-                if (i == 0) rc = policy(c, H, B * P, pmH, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std, c.k.pimu);
-                if (rc || (rc = flush_split(c))) return rc;
-            }
-            if ((rc = terminal_wide(c, noise, toff, prm->min_std))) return rc;
-        } else if (c.fold_heads) {
-            // the sampled rows' X_H holds h2_{H-1} (folded first layers), the policy rows' holds z_H: one launch each
-            if ((rc = policy(c, H, B * N, rm, noise, c.eps_env, N, toff, prm->min_std, nullptr, true))) return rc;
-            if (P > 0) {
-                if (i == 0 || !pi_cache)
-                    rc = policy(c, H, B * P, pmH, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std,
-                                pi_cache ? c.k.pimu : nullptr, c.fold_policy != 0);
-                else
-                    rc = policy_from_mu(c, B * P, pmH, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std);
-                if (rc) return rc;
-            }
-            if ((rc = q_chain(c, B * N, rm, nullptr, nullptr, 0, true))) return rc;
-            if (P > 0 && (rc = q_chain(c, B * P, pmH, nullptr, nullptr, 0, c.fold_policy != 0))) return rc;
-        } else if (pi_cache && i > 0) {
-            if ((rc = policy(c, H, B * N, rm, noise, c.eps_env, N, toff, prm->min_std))) return rc;
-            if ((rc = flush_split(c))) return rc;
-            if ((rc = policy_from_mu(c, B * P, pmH, noise, c.eps_env, P, toff + (long)N * c.A, prm->min_std)))
-                return rc;
-        } else if ((rc = policy(c, H, B * T, all, noise, c.eps_env, T, toff, prm->min_std,
-                                pi_cache ? c.k.pimu : nullptr))) {
-            return rc;
-        }
-        if (!wide_heads && !c.fold_heads && (rc = terminal_q(c, prm->discount_pow[H]))) return rc;
-        ca.final_iter = i == I - 1;
-        ca.iter = i;
-        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
+    const PlanFast fast = {z0c_eligible(c), fold_on(), use_wide_heads(c), pi_cache_on() != 0};
+    return cem_run(c, ToldStep{c}, fast, prm, noise, u, prev_mean, action, metrics, elite_out, score_out, value_out,
+                   mean_out, std_out);
 }
 
 int tdmpc_icem_sizes_for(const tdmpc_dims* d, tdmpc_sizes* out) {
@@ -4896,77 +5058,14 @@ int tdmpc_plan_icem(const tdmpc_dims* d, const tdmpc_icem_params* prm, const voi
         return TDMPC_E_NULL;
     Ctx c;
     int rc;
-    const int H = prm->horizon, I = prm->iterations, B = prm->batch, K = d->num_elites;
-    if (I <= 0 || I > 16) { snprintf(g_err, sizeof g_err, "iCEM: 1..16 iterations"); return TDMPC_E_DIMS; }
-    if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, I, (hipStream_t)stream, K))) return rc;
+    if (!icem_counts_ok(prm, d, "iCEM")) return TDMPC_E_DIMS;
+    if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, prm->batch, prm->horizon, prm->iterations, (hipStream_t)stream,
+                        d->num_elites)))
+        return rc;
     if ((c.path = resolve_path(prm->path, false)) < 0) return TDMPC_E_DIMS;
-    const int N = d->num_samples, Pmax = d->num_pi, Tw = N + K + Pmax, pi_base = N + K, P0 = prm->n_pi0;
-    c.T = Tw;
-    if (P0 <= 0 || P0 > Pmax || prm->n_samples[0] != N) { snprintf(g_err, sizeof g_err, "iCEM: bad counts"); return TDMPC_E_DIMS; }
-    for (int i = 0; i < I; ++i) {
-        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i];
-        if (Ni <= 0 || Ni > N || Pi <= 0 || Pi > P0 || Ei < 0 || Ei > K || Ni + Ei + Pi < K ||
-            (Ei > 0 && i == 0 && !prm->has_elites) || (i == 0 && Ei > 0 && prm->elite_horizon != H && prm->elite_horizon != H - 1)) {
-            snprintf(g_err, sizeof g_err, "iCEM: bad counts at iteration %d", i);
-            return TDMPC_E_DIMS;
-        }
-    }
-    const long A = c.A, env = prm->env_stride;
     // z0 = h(obs); mean = 0 (warm: mean[:-1] = prev[1:], mean[-1] = prev[-1]), std = init_std (0.5)
-    if ((rc = encode(c, obs, obs_is_u8, B, prev_mean, prm->warm_start, 1, prm->init_std))) return rc;
-    // pi pre-rollout of the P0 policy rows (tdmpc_icem_similarity_mlp.py:193-199); their rollout, reward
-    // prefix and z_H are the same in every iteration (same z, same pi actions), so they are computed once
-    const RowMap pm0 = {P0, Tw, pi_base};
-    if ((rc = prep(c, nullptr, 0, c.k.z0))) return rc;   // z0 into X_0's latent columns, all Tw rows
-    for (int t = 0; t < H; ++t) {
-        if ((rc = policy(c, t, B * P0, pm0, noise, env, P0, prm->pi_off + (long)t * P0 * A, prm->min_std))) return rc;
-        if ((rc = step_next(c, t, B * P0, pm0, prm->discount_pow[t], t == 0, t == H - 1))) return rc;
-    }
-    CemArgs ca = cem_args0(c);   // (c.T = Tw; N, P, T, NE per iteration below)
-    ca.I = I; ca.pi_base = pi_base;
-    ca.eps = noise; ca.eps_env = env; ca.eps_act_off = prm->act_off; ca.u = u; ca.prev_mean = prev_mean;
-    ca.eval_mode = prm->eval_mode; ca.temperature = prm->temperature; ca.momentum = prm->momentum;
-    ca.omm = prm->one_minus_momentum; ca.std_floor = prm->std_floor; ca.action = action; ca.metrics = metrics;
-    ca.mean_out = mean_out; ca.std_out = std_out; ca.elite_store = elites;
-    ca.G = c.k.G; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H]; ca.value_out = value_out;
-    ca.status = prm->status;
-    const size_t cem_lds = cem_lds_bytes(Tw, H, K, c.A);
-    for (int i = 0; i < I; ++i) {
-        const int Ni = prm->n_samples[i], Pi = prm->n_pi[i], Ei = prm->n_elite[i], NE = Ni + Ei;
-        // sampled candidates clamp(mean + std * noise) for rows [0, Ni) (sample_mix_action_sequence)
-        if ((rc = prep_launch(c, noise, Ni, env, prm->samp_off[i], nullptr, nullptr))) return rc;
-        if (Ei > 0 || i == I - 1) {
-            FillArgs fa;
-            memset(&fa, 0, sizeof fa);
-            fa.X = c.k.X; fa.x_stride = c.k.x_stride; fa.Kx = c.Kx; fa.apq = c.w.Ap / 4; fa.Tw = Tw;
-            fa.B = B; fa.H = H; fa.A = c.A; fa.Hmax = d->max_horizon; fa.K = K;
-            fa.n0 = Ni; fa.E = Ei; fa.mode = i == 0 ? 1 : 2; fa.eH = prm->elite_horizon; fa.mean_row = i == I - 1;
-            fa.mean = c.k.mean; fa.stdv = c.k.stdv; fa.elites = elites;
-            fa.eps = noise; fa.eps_env = env; fa.reuse_off = prm->reuse_off;
-            const long tot = (long)B * H * fa.apq * (Ei + fa.mean_row);
-            hipLaunchKernelGGL(icem_fill_kernel, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, c.s, fa);
-            HIPCHK(hipGetLastError());
-        }
-        // rollout of the sampled + reused rows (the pi rows' is cached from the pre-rollout)
-        const RowMap blk = {NE, Tw, 0};
-        for (int t = 0; t < H; ++t)
-            if ((rc = step_next(c, t, B * NE, blk, prm->discount_pow[t], t == 0, t == H - 1, 1))) return rc;
-        // terminal value of all T_i = NE + Pi candidates: pi(z_H) with this iteration's noise, Q
-        const RowMap pmi = {Pi, Tw, pi_base};
-        if ((rc = policy(c, H, B * NE, blk, noise, env, NE, prm->term_off[i], prm->min_std))) return rc;
-        if ((rc = policy(c, H, B * Pi, pmi, noise, env, Pi, prm->term_off[i] + (long)NE * A, prm->min_std))) return rc;
-        // both row groups on the same Q path, so cem_kernel reads one kind of value (qv or value)
-        const bool qchain = use_chain(c, B * NE, 2, CK_Q) && use_chain(c, B * Pi, 2, CK_Q);
-        if ((rc = terminal_q_rows(c, B * NE, blk, prm->discount_pow[H], qchain))) return rc;
-        if ((rc = terminal_q_rows(c, B * Pi, pmi, prm->discount_pow[H], qchain))) return rc;
-        ca.qv = qchain ? c.k.qv : nullptr;
-        ca.N = Ni; ca.P = Pi; ca.T = NE + Pi; ca.NE = NE;
-        ca.final_iter = i == I - 1;
-        ca.iter = i;
-        hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds, c.s, ca);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
+    if ((rc = encode(c, obs, obs_is_u8, c.B, prev_mean, prm->warm_start, 1, prm->init_std))) return rc;
+    return icem_run(c, ToldStep{c}, prm, noise, u, prev_mean, elites, action, metrics, value_out, mean_out, std_out);
 }
 
 int tdmpc_estimate_value(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* packed, const float* z0,
@@ -4976,33 +5075,10 @@ int tdmpc_estimate_value(const tdmpc_dims* d, const tdmpc_plan_params* prm, cons
         return TDMPC_E_NULL;
     Ctx c;
     int rc;
-    const int H = prm->horizon, B = prm->batch;
-    if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
+    if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, prm->batch, prm->horizon, 1, (hipStream_t)stream))) return rc;
     if ((c.path = resolve_path(prm->path, false)) < 0) return TDMPC_E_DIMS;
     if (rows != c.T) { snprintf(g_err, sizeof g_err, "rows must equal N+P"); return TDMPC_E_DIMS; }
-    const int T = c.T, L = c.w.L;
-    if ((rc = load_z0(c, z0))) return rc;
-    hipLaunchKernelGGL(scatter_actions_kernel, dim3(512), dim3(256), 0, c.s, actions, c.k.X, c.k.x_stride, H, T, c.A,
-                       c.w.Ap, c.Kx, B, T, 0);
-    HIPCHK(hipGetLastError());
-    const RowMap all = {T, T, 0};
-    for (int t = 0; t < H; ++t)
-        if ((rc = step_next(c, t, B * T, all, prm->discount_pow[t], t == 0, t == H - 1)))
-            return rc;
-    if (z_last) {
-        hipLaunchKernelGGL(gather_z_kernel, dim3(256), dim3(256), 0, c.s, Xt(c, H), c.Kx, c.w.Ap, L, B * T, z_last);
-        HIPCHK(hipGetLastError());
-    }
-    if ((rc = policy(c, H, B * T, all, eps_term, (long)T * c.A, T, 0, prm->min_std))) return rc;
-    if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
-    if (use_chain(c, B * T, 2, CK_Q)) {
-        hipLaunchKernelGGL(qvalue_kernel, dim3((B * T + 255) / 256), dim3(256), 0, c.s, c.k.G, c.k.qv, c.k.xrows,
-                           prm->discount_pow[H], c.k.value, B * T);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(value, c.k.value, (size_t)B * T * 4, hipMemcpyDeviceToDevice, c.s));
-    HIPCHK(hipMemcpyAsync(reward_last, c.k.rlast, (size_t)B * T * 4, hipMemcpyDeviceToDevice, c.s));
-    return 0;
+    return estimate_value_run(c, ToldStep{c}, prm, z0, actions, eps_term, value, reward_last, z_last);
 }
 
 int tdmpc_pi_rollout(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* packed, const float* z0,
@@ -5010,23 +5086,9 @@ int tdmpc_pi_rollout(const tdmpc_dims* d, const tdmpc_plan_params* prm, const vo
     if (!d || !prm || !packed || !z0 || !eps_pi || !pi_actions || !workspace) return TDMPC_E_NULL;
     Ctx c;
     int rc;
-    const int H = prm->horizon, B = prm->batch;
-    if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, B, H, 1, (hipStream_t)stream))) return rc;
+    if ((rc = setup_ctx(c, d, packed, workspace, ws_bytes, prm->batch, prm->horizon, 1, (hipStream_t)stream))) return rc;
     if ((c.path = resolve_path(prm->path, false)) < 0) return TDMPC_E_DIMS;
-    const int N = c.N, P = c.P, T = c.T;
-    const long A = c.A;
-    if (P <= 0) { snprintf(g_err, sizeof g_err, "num_pi is 0"); return TDMPC_E_DIMS; }
-    if ((rc = load_z0(c, z0))) return rc;
-    // the policy rows sit where tdmpc_plan keeps them: rows N..T-1 of each env's block of T
-    const RowMap pm = {P, T, N};
-    for (int t = 0; t < H; ++t) {
-        if ((rc = policy(c, t, B * P, pm, eps_pi, (long)H * P * A, P, (long)t * P * A, prm->min_std))) return rc;
-        if (t < H - 1 && (rc = step_next(c, t, B * P, pm, prm->discount_pow[t], t == 0, 0))) return rc;
-    }
-    hipLaunchKernelGGL(gather_actions_kernel, dim3(512), dim3(256), 0, c.s, c.k.X, c.k.x_stride, H, P, c.A, c.Kx, B,
-                       T, N, pi_actions);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return pi_rollout_run(c, ToldStep{c}, prm, z0, eps_pi, pi_actions);
 }
 
 int tdmpc_cem_iter(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void* packed, const float* z0,
@@ -5061,13 +5123,10 @@ int tdmpc_cem_iter(const tdmpc_dims* d, const tdmpc_plan_params* prm, const void
         if ((rc = step_next(c, t, B * T, all, prm->discount_pow[t], t == 0, t == H - 1, 1))) return rc;
     if ((rc = policy(c, H, B * T, all, eps_term, (long)T * A, T, 0, prm->min_std))) return rc;
     if ((rc = terminal_q(c, prm->discount_pow[H]))) return rc;
-    CemArgs ca = cem_args0(c);
-    ca.I = 1; ca.iter = 0; ca.final_iter = 1; ca.no_pick = 1;
-    ca.temperature = prm->temperature; ca.momentum = prm->momentum; ca.omm = prm->one_minus_momentum;
-    ca.std_floor = prm->std_floor; ca.std_floor_p = prm->std_floor_dev;
-    ca.elite_out = elite_actions; ca.score_out = score; ca.value_out = value; ca.reward_out = reward_mean;
-    ca.status = prm->status;
-    if (use_chain(c, B * T, 2, CK_Q)) { ca.G = c.k.G; ca.qv = c.k.qv; ca.q_ld = c.k.xrows; ca.discH = prm->discount_pow[H]; }
+    CemArgs ca = cem_args(c, prm, nullptr, nullptr, nullptr, nullptr, nullptr, value, nullptr, nullptr);
+    ca.I = 1; ca.iter = 0; ca.final_iter = 1; ca.no_pick = 1; ca.std_floor_p = prm->std_floor_dev;
+    ca.elite_out = elite_actions; ca.score_out = score; ca.reward_out = reward_mean;
+    if (use_chain(c, B * T, 2, CK_Q)) cem_args_qv(ca, c, prm->discount_pow[H]);
     hipLaunchKernelGGL(cem_kernel, dim3(B), dim3(1024), cem_lds_bytes(T, H, ca.K, A), c.s, ca);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy2DAsync(mean, HA * 4, c.k.mean, mp, HA * 4, B, hipMemcpyDeviceToDevice, c.s));

@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from .config import linear_schedule
 from .dssm import DSSM, check_dssm_cfg, float_tensors
-from .tdmpc import HipPlanner
+from .tdmpc import Checkpointed, HipPlanner
 
 
 def _schedule_ends(schdl):
@@ -179,7 +179,7 @@ class DrnnPlanner(HipPlanner):
         return out
 
 
-class TdMpcDrnn:
+class TdMpcDrnn(Checkpointed):
     """Drop-in for the reference `TdMpcSimDssm` planning interface (tdmpc_similarity_drnn.py:87-267)."""
 
     MAX_GRAPHS = 8   # captured plans kept per agent (one per (horizon, iterations, batch, num_pi, eval_mode))
@@ -221,18 +221,6 @@ class TdMpcDrnn:
         if not self._has_prev[0]:
             raise AttributeError("_prev_mean")
         return self.planner.prev_mean_view(int(self._prev_H[0]), 1)[0]
-
-    def state_dict(self):
-        return {"model": self.model.state_dict(), "model_target": self.model_target.state_dict()}
-
-    def save(self, fp):
-        torch.save(self.state_dict(), fp)
-
-    def load(self, fp):
-        """A reference checkpoint ({'model': sd, 'model_target': sd}): weights_only, strict keys."""
-        d = torch.load(fp, map_location=self.device, weights_only=True)
-        self.model.load_state_dict(d["model"])
-        self.model_target.load_state_dict(d["model_target"])
 
     @torch.no_grad()
     def plan(self, obs, hidden, eval_mode=False, step=None, t0=True, noise=None, trace=None):

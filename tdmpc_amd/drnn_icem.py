@@ -32,7 +32,8 @@ from .colored_noise import irfft_matrices, powerlaw_psd_gaussian, spectrum_rows
 from .config import linear_schedule
 from .drnn import DrnnPlanner
 from .dssm import DSSM, check_dssm_cfg
-from .tdmpc import _discount_pows
+from .icem import icem_counts, icem_layout, icem_load, icem_params, icem_trace_values
+from .tdmpc import Checkpointed
 
 
 def colored_noise_params(L, A, batch, env_stride, normals_env, jobs, betas):
@@ -81,7 +82,7 @@ class IcemDrnnPlanner(DrnnPlanner):
         return sz
 
 
-class TdIcemDrnn:
+class TdIcemDrnn(Checkpointed):
     """Drop-in for the reference `TdICemSimDssm` planning interface (tdmpc_icem_similarity_drnn.py:81-272)."""
 
     MAX_GRAPHS = 8   # captured plans kept per agent
@@ -138,47 +139,13 @@ class TdIcemDrnn:
             raise AttributeError("_elite_actions")
         return self.elites[0, :self.plan_horizon]
 
-    def state_dict(self):
-        return {"model": self.model.state_dict(), "model_target": self.model_target.state_dict()}
-
-    def save(self, fp):
-        torch.save(self.state_dict(), fp)
-
-    def load(self, fp):
-        """A reference checkpoint ({'model': sd, 'model_target': sd}): weights_only, strict keys."""
-        d = torch.load(fp, map_location=self.device, weights_only=True)
-        self.model.load_state_dict(d["model"])
-        self.model_target.load_state_dict(d["model_target"])
-
-    # ------------------------------------------------------------------ counts and layout
+    # ------------------------------------------------------------------ counts and layout (tdmpc_amd.icem's)
     def counts(self, mixture, has_elites, t0):
         """(N_i, P_i, E_i) per iteration (:205-215): reused elites only inside an episode."""
-        cfg, out, n = self.cfg, [], self.cfg.num_samples
-        for i in range(cfg.iterations):
-            if i > 0:
-                n = max(2 * cfg.num_elites, int(n / cfg.factor_decrease_num))
-            p = int(mixture * n)
-            e = self.E_max if (cfg.fraction_elites_reused > 0 and not t0 and (has_elites or i > 0)) else 0
-            out.append((n, p, e))
-        return out
+        return icem_counts(self.cfg, self.E_max, mixture, has_elites, reuse_ok=not t0)
 
     def layout(self, H, cts, reuse):
-        """Per-env noise stream offsets (floats): the pre-rollout's draws, per iteration [samples | at i = 0 with
-        reuse the fresh elite tail | terminal policy noise], the action noise."""
-        A = self.cfg.action_dim
-        off = {"pi": 0, "samp": [], "term": [], "reuse": 0}
-        o = H * cts[0][1] * A
-        for i, (n, p, e) in enumerate(cts):
-            off["samp"].append(o)
-            o += H * n * A
-            if i == 0 and reuse:
-                off["reuse"] = o
-                o += H * e * A
-            off["term"].append(o)
-            o += (n + e + p) * A
-        off["act"] = o
-        off["total"] = o + A
-        return off
+        return icem_layout(self.cfg.action_dim, H, cts, reuse)
 
     def _colored_blocks(self, H, cts, off, reuse):
         """The coloured blocks of one env's stream in draw order: (n, stream offset)."""
@@ -257,20 +224,8 @@ class TdIcemDrnn:
         return u
 
     def _load(self, e, H, cts, off, reuse, nz):
-        """Explicit draws (eps_pi [H, P0, A], samp[i] [H, N_i, A], reuse [H, E, A], term[i] [T_i, A], u, eps_act [A])
-        into env e's stream."""
-        A, S, dev = self.cfg.action_dim, off["total"], self.device
-        buf = self.planner.noise_flat[e * S:(e + 1) * S]
-        P0 = cts[0][1]
-        buf[:H * P0 * A].copy_(nz.eps_pi.reshape(-1).to(dev, torch.float32))
-        for i, (n, p, ne) in enumerate(cts):
-            buf[off["samp"][i]:off["samp"][i] + H * n * A].copy_(nz.samp[i].reshape(-1).to(dev, torch.float32))
-            if i == 0 and reuse:
-                buf[off["reuse"]:off["reuse"] + H * ne * A].copy_(nz.reuse.reshape(-1).to(dev, torch.float32))
-            buf[off["term"][i]:off["term"][i] + (n + ne + p) * A].copy_(nz.term[i].reshape(-1).to(dev, torch.float32))
-        if nz.eps_act is not None:
-            buf[off["act"]:off["act"] + A].copy_(nz.eps_act.to(dev, torch.float32))
-        return float(nz.u)
+        S = off["total"]
+        return icem_load(self.planner.noise_flat[e * S:(e + 1) * S], self.cfg.action_dim, H, cts, off, reuse, nz)
 
     # ------------------------------------------------------------------ plan
     @torch.no_grad()
@@ -299,26 +254,6 @@ class TdIcemDrnn:
             return a, None, [dict(self.METRICS0) for _ in range(B)]
         hidden = torch.as_tensor(hidden, dtype=torch.float32).reshape(B, -1)
         return self._plan_envs(obs.view(B, -1), hidden, eval_mode, step, bool(t0), noise, trace)
-
-    def _params(self, B, H, cts, off, reuse, warm, eval_mode):
-        cfg, pl = self.cfg, self.planner
-        p = _lib.IcemParams()
-        p.horizon, p.iterations, p.batch = H, cfg.iterations, B
-        p.warm_start, p.eval_mode, p.has_elites = int(warm), int(eval_mode), int(reuse)
-        p.elite_horizon = H   # (reuse happens inside an episode only, where the horizon does not move)
-        p.n_pi0 = cts[0][1]
-        p.path = _lib.PATHS["chain_x6"]
-        for i, (n, pp, e) in enumerate(cts):
-            p.n_samples[i], p.n_pi[i], p.n_elite[i] = n, pp, e
-            p.samp_off[i], p.term_off[i] = off["samp"][i], off["term"][i]
-        p.reuse_off, p.pi_off, p.act_off, p.env_stride = off["reuse"], 0, off["act"], off["total"]
-        p.min_std, p.temperature, p.momentum = cfg.min_std, cfg.temperature, cfg.momentum
-        p.one_minus_momentum = float(1 - cfg.momentum)
-        p.std_floor, p.init_std = float(self.std), 0.5
-        for t, v in enumerate(_discount_pows(cfg.discount, H)):
-            p.discount_pow[t] = v
-        p.status = pl.status.data_ptr()
-        return p
 
     def _launch(self, p, outs):
         pl = self.planner
@@ -374,7 +309,8 @@ class TdIcemDrnn:
         elif self.rng == "reference":
             us = [self._draw_reference(e, H, cts, off, reuse, eval_mode) for e in range(B)]
             pl.u[:B].copy_(torch.tensor(us, dtype=torch.float64))
-        p = self._params(B, H, cts, off, reuse, warm, eval_mode)
+        # (elite_horizon = H: reuse happens inside an episode only, where the horizon does not move)
+        p = icem_params(cfg, B, H, cts, off, reuse, warm, eval_mode, self.std, pl.status, "chain_x6", H)
         outs = {}
         if trace is not None:
             I, A, dev = cfg.iterations, cfg.action_dim, self.device
@@ -401,7 +337,7 @@ class TdIcemDrnn:
         else:
             device_work()
         if trace is not None:
-            trace.update(value=[outs["value"][:, i, :n + e + pp] for i, (n, pp, e) in enumerate(cts)],
+            trace.update(value=icem_trace_values(outs["value"], cts),
                          mean=outs["mean"], std=outs["std"], counts=cts, z_in=pl.z_in[:B].clone())
         self._has_prev = True
         self._has_elites = True

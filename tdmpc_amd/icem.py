@@ -32,7 +32,7 @@ import torch
 from . import _lib
 from .colored_noise import BatchedColoredNoise, _scales as _spectrum
 from .config import linear_schedule
-from .tdmpc import _discount_pows, pack_told
+from .tdmpc import Checkpointed, _discount_pows, pack_told
 from .told import TOLD
 
 
@@ -41,7 +41,81 @@ def _thirds(n):
     return [q, q, q] if r == 0 else ([q, q + 1, q] if r == 1 else [q, q + 1, q + 1])
 
 
-class TdICEM:
+# ---------------------------------------------------------------------- bookkeeping shared with drnn_icem.TdIcemDrnn
+def icem_counts(cfg, E_max, mixture, has_elites, reuse_ok=True):
+    """(N_i, P_i, E_i) per iteration (tdmpc_icem_similarity_mlp.py:201-210, _drnn.py:205-215). reuse_ok: this call may
+    re-evaluate elites at all (the recurrent agent's file allows it only inside an episode: `not t0`)."""
+    out, n = [], cfg.num_samples
+    for i in range(cfg.iterations):
+        if i > 0:
+            n = max(2 * cfg.num_elites, int(n / cfg.factor_decrease_num))
+        p = int(mixture * n)
+        e = E_max if (cfg.fraction_elites_reused > 0 and reuse_ok and (has_elites or i > 0)) else 0
+        out.append((n, p, e))
+    return out
+
+
+def icem_layout(A, H, cts, reuse):
+    """Per-env noise stream offsets (floats): the pre-rollout's draws, per iteration [samples | at i = 0 with reuse
+    the fresh elite tail | terminal policy noise], the action noise."""
+    off = {"pi": 0, "samp": [], "term": [], "reuse": 0}
+    o = H * cts[0][1] * A
+    for i, (n, p, e) in enumerate(cts):
+        off["samp"].append(o)
+        o += H * n * A
+        if i == 0 and reuse:
+            off["reuse"] = o
+            o += H * e * A
+        off["term"].append(o)
+        o += (n + e + p) * A
+    off["act"] = o
+    off["total"] = o + A
+    return off
+
+
+def icem_load(buf, A, H, cts, off, reuse, nz):
+    """Explicit draws (oracle IcemNoise: eps_pi [H, P0, A], samp[i] [H, N_i, A], reuse [H, E, A], term[i] [T_i, A], u,
+    eps_act [A]) into one env's stream `buf`; returns u."""
+    def put(o, count, t):   # (a draw of another size than the layout's fails in copy_)
+        buf[o:o + count].copy_(t.reshape(-1).to(buf.device, torch.float32))
+    put(0, H * cts[0][1] * A, nz.eps_pi)
+    for i, (n, p, e) in enumerate(cts):
+        put(off["samp"][i], H * n * A, nz.samp[i])
+        if i == 0 and reuse:
+            put(off["reuse"], H * e * A, nz.reuse)
+        put(off["term"][i], (n + e + p) * A, nz.term[i])
+    if nz.eps_act is not None:
+        put(off["act"], A, nz.eps_act)
+    return float(nz.u)
+
+
+def icem_params(cfg, B, H, cts, off, reuse, warm, eval_mode, std, status, path, elite_horizon):
+    """tdmpc_icem_params of one call (status: the agent's device status word)."""
+    p = _lib.IcemParams()
+    p.horizon, p.iterations, p.batch = H, cfg.iterations, B
+    p.warm_start, p.eval_mode, p.has_elites = int(warm), int(eval_mode), int(reuse)
+    p.elite_horizon = elite_horizon
+    p.n_pi0 = cts[0][1]
+    p.path = _lib.PATHS[path]
+    for i, (n, pp, e) in enumerate(cts):
+        p.n_samples[i], p.n_pi[i], p.n_elite[i] = n, pp, e
+        p.samp_off[i], p.term_off[i] = off["samp"][i], off["term"][i]
+    p.reuse_off, p.pi_off, p.act_off, p.env_stride = off["reuse"], 0, off["act"], off["total"]
+    p.min_std, p.temperature, p.momentum = cfg.min_std, cfg.temperature, cfg.momentum
+    p.one_minus_momentum = float(1 - cfg.momentum)
+    p.std_floor, p.init_std = float(std), 0.5
+    for t, v in enumerate(_discount_pows(cfg.discount, H)):
+        p.discount_pow[t] = v
+    p.status = status.data_ptr()
+    return p
+
+
+def icem_trace_values(value, cts):
+    """value_out [B, I, Tw] -> per iteration the values of its T_i = N_i + E_i + P_i candidates, [B, T_i]."""
+    return [value[:, i, :n + e + pp] for i, (n, pp, e) in enumerate(cts)]
+
+
+class TdICEM(Checkpointed):
     def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", path: str = "auto"):
         if getattr(cfg, "modality", "state") != "state":
             raise NotImplementedError("iCEM drop-in: state observations (the pixel DSSM encoder is rlpyt's)")
@@ -119,34 +193,10 @@ class TdICEM:
 
     # ------------------------------------------------------------------ plan
     def counts(self, mixture, has_elites):
-        """(N_i, P_i, E_i) per iteration (tdmpc_icem_similarity_mlp.py:201-210)."""
-        cfg, out, n = self.cfg, [], self.cfg.num_samples
-        for i in range(cfg.iterations):
-            if i > 0:
-                n = max(2 * cfg.num_elites, int(n / cfg.factor_decrease_num))
-            p = int(mixture * n)
-            e = self.E_max if (cfg.fraction_elites_reused > 0 and (has_elites or i > 0)) else 0
-            out.append((n, p, e))
-        return out
+        return icem_counts(self.cfg, self.E_max, mixture, has_elites)
 
     def _layout(self, H, cts, reuse):
-        """Per-env noise stream offsets (floats)."""
-        A = self.cfg.action_dim
-        off = {"pi": 0}
-        o = H * cts[0][1] * A
-        off["samp"], off["term"] = [], []
-        off["reuse"] = 0
-        for i, (n, p, e) in enumerate(cts):
-            off["samp"].append(o)
-            o += H * n * A
-            if i == 0 and reuse:
-                off["reuse"] = o
-                o += H * e * A
-            off["term"].append(o)
-            o += (n + e + p) * A
-        off["act"] = o
-        off["total"] = o + A
-        return off
+        return icem_layout(self.cfg.action_dim, H, cts, reuse)
 
     def _colored_specs(self, H, cts, reuse):
         """The coloured-noise draws of one plan call in the reference's order: (beta, n, length, kind, i)."""
@@ -279,21 +329,8 @@ class TdICEM:
         return u
 
     def _load(self, e, H, cts, off, reuse, nz):
-        """Write explicit draws (oracle IcemNoise) into env e's stream."""
-        A = self.cfg.action_dim
         S = off["total"]
-        buf = self.noise[e * S:(e + 1) * S]
-        dev = self.device
-        P0 = cts[0][1]
-        buf[:H * P0 * A].copy_(nz.eps_pi.reshape(-1).to(dev))
-        for i, (n, p, ne) in enumerate(cts):
-            buf[off["samp"][i]:off["samp"][i] + H * n * A].copy_(nz.samp[i].reshape(-1).to(dev))
-            if i == 0 and reuse:
-                buf[off["reuse"]:off["reuse"] + H * ne * A].copy_(nz.reuse.reshape(-1).to(dev))
-            buf[off["term"][i]:off["term"][i] + (n + ne + p) * A].copy_(nz.term[i].reshape(-1).to(dev))
-        if nz.eps_act is not None:
-            buf[off["act"]:off["act"] + A].copy_(nz.eps_act.to(dev))
-        return float(nz.u)
+        return icem_load(self.noise[e * S:(e + 1) * S], self.cfg.action_dim, H, cts, off, reuse, nz)
 
     @torch.no_grad()
     def plan(self, obs, eval_mode=False, step=None, t0=True, noise=None, trace=None):
@@ -370,24 +407,8 @@ class TdICEM:
         else:
             us = [self._draw(e, H, cts, off, reuse, eval_mode) for e in range(B)]
             self.u[:B].copy_(torch.tensor(us, dtype=torch.float64))
-        p = _lib.IcemParams()
-        p.horizon, p.iterations, p.batch = H, cfg.iterations, B
-        p.warm_start = int((not t0) and self._has_prev)
-        p.eval_mode = int(eval_mode)
-        p.has_elites = int(reuse)
-        p.elite_horizon = self._elite_H if reuse else H
-        p.n_pi0 = cts[0][1]
-        p.path = _lib.PATHS[self.path]
-        for i, (n, pp, e) in enumerate(cts):
-            p.n_samples[i], p.n_pi[i], p.n_elite[i] = n, pp, e
-            p.samp_off[i], p.term_off[i] = off["samp"][i], off["term"][i]
-        p.reuse_off, p.pi_off, p.act_off, p.env_stride = off["reuse"], 0, off["act"], off["total"]
-        p.min_std, p.temperature, p.momentum = cfg.min_std, cfg.temperature, cfg.momentum
-        p.one_minus_momentum = float(1 - cfg.momentum)
-        p.std_floor, p.init_std = float(self.std), 0.5
-        for t, v in enumerate(_discount_pows(cfg.discount, H)):
-            p.discount_pow[t] = v
-        p.status = self.status.data_ptr()
+        p = icem_params(cfg, B, H, cts, off, reuse, (not t0) and self._has_prev, eval_mode, self.std, self.status,
+                        self.path, self._elite_H if reuse else H)
         dev = self.device
         value_out = mean_out = std_out = None
         if trace is not None:
@@ -405,7 +426,7 @@ class TdICEM:
             C.c_void_p(self.workspace.data_ptr()), self.workspace.numel() * 4, C.c_void_p(stream))
         _lib.check(rc, "tdmpc_plan_icem")
         if trace is not None:
-            trace.update(value=[value_out[0, i, :n + e + pp] for i, (n, pp, e) in enumerate(cts)],
+            trace.update(value=[v[0] for v in icem_trace_values(value_out, cts)],
                          mean=mean_out[0], std=std_out[0], counts=cts,
                          value_all=value_out, mean_all=mean_out, std_all=std_out)   # (every env: [B, I, ...])
         self._has_prev = True

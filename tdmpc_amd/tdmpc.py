@@ -53,6 +53,19 @@ def load_checkpoint(fp, model, model_target, device="cpu"):
     model_target.load_state_dict(d["model_target"])
 
 
+class Checkpointed:
+    """The reference agents' checkpoint interface, for every agent here with `model`, `model_target` and `device`."""
+
+    def state_dict(self):
+        return {"model": self.model.state_dict(), "model_target": self.model_target.state_dict()}
+
+    def save(self, fp):
+        torch.save(self.state_dict(), fp)
+
+    def load(self, fp):
+        load_checkpoint(fp, self.model, self.model_target, self.device)
+
+
 def pack_told(pl, model):
     """Pack `model`'s parameters (reference state_dict order) into pl.packed through tdmpc_pack_weights when any
     of them changed since the last call (pl: an object with L, dims, device, packed and the _packed_* cache)."""
@@ -499,7 +512,7 @@ class HipPlanner:
         return z0
 
 
-class TDMPC:
+class TDMPC(Checkpointed):
     """Drop-in for the reference `TDMPC` planning interface (tdmpc.py:53-163)."""
 
     def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", graph: bool = True, path: str = "auto"):
@@ -523,15 +536,6 @@ class TDMPC:
         self._prev_H = np.zeros(max_batch, dtype=np.int64)
 
     # ------------------------------------------------------------------ reference API
-    def state_dict(self):
-        return {"model": self.model.state_dict(), "model_target": self.model_target.state_dict()}
-
-    def save(self, fp):
-        torch.save(self.state_dict(), fp)
-
-    def load(self, fp):
-        load_checkpoint(fp, self.model, self.model_target, self.device)
-
     # ------------------------------------------------------------------ learner (tdmpc.py:165-245)
     def learner(self, graph: bool = True, warmup: int = 3):
         """The GPU learner (tdmpc_amd/learner.py), created on first use with its Adam optimisers."""
