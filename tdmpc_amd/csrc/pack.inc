@@ -175,9 +175,7 @@ __global__ void __launch_bounds__(256) fold_split_kernel(const FoldArgs a, long 
     else if (k < a.zoff + a.M && k < a.pk) x = a.fw[(size_t)r * a.M + (k - a.zoff)];
     __bf16 h, m, l;
     split3(x, h, m, l);
-    a.x6[(blk * 3 + 0) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, h);
-    a.x6[(blk * 3 + 1) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, m);
-    a.x6[(blk * 3 + 2) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, l);
+    x6_put(a.x6, (size_t)blk, lane, j, h, m, l);
 }
 int fold_one(const Layout& w, float* pw, hipStream_t s, size_t W, int R, int Kp, int zoff, size_t b, size_t fw,
              size_t bf, size_t x6, int kind, int pk, bool gemm = true) {

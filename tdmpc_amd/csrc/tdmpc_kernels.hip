@@ -3222,6 +3222,7 @@ int set_max_lds() {
 }
 
 #include "plan1.inc"
+#include "wide_ring.inc"
 #include "wide_step.inc"
 #include "wide_heads.inc"
 #include "drnn.inc"

@@ -1,9 +1,9 @@
-// wide_heads.inc -- included by tdmpc_kernels.hip after wide_step.inc (uses its ring geometry, LDS-DMA, the three-plane
-// X6U operands, RowMap, tanh_f / elu_f, the reference-rounding helpers and the constant-space vector loads).
+// wide_heads.inc -- included by tdmpc_kernels.hip after wide_ring.inc (the design: the ring with its read-ahead, the
+// fragment stream, the x tile, the shape of the two-layer super-chunk and of the last layer) and wide_step.inc
+// (uses also RowMap, tanh_f / elu_f and the reference-rounding helpers).
 //
-// The terminal heads of estimate_value (/root/reference/src/algorithm/tdmpc.py:91-92) on the wide step kernel's
-// design -- one workgroup per CU and head-block of 128 rows, 8 waves x 16 rows x ALL 512 hidden columns of layer 2 in
-// registers, the head's x6q weight fragments LDS-DMA'd once per workgroup into a ring read by all 8 waves:
+// The terminal heads of estimate_value (/root/reference/src/algorithm/tdmpc.py:91-92) on the wide kernels' design,
+// one workgroup per CU and head-block of 128 rows:
 //  * WH_PI: TOLD.pi + TruncatedNormal.sample (tdmpc.py:39-45, helper.py:86-96): Linear(L -> M), ELU, Linear(M -> M),
 //    ELU, Linear(M -> A), tanh, (eps * std).clamp(+-0.3), clamp(mu + eps, +-(1 - 1e-6)) -> the X_H action columns;
 //  * WH_Q: helper.q (helper.py:197-201): Linear(L + A -> M), LayerNorm, Tanh, Linear(M -> M), LayerNorm, ELU,
@@ -84,108 +84,50 @@ DEVI const w2cf* wh_cp(const float* p) {
 template <int G1, int NB3, int GX>
 DEVI void wh_pi(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
     constexpr int NS = ws_ns<GX>();
-    constexpr int VM = 3 * (NS - 3);
-    constexpr int SPC2 = G1 + 16;
-    static_assert(NS >= 3 && NS - 1 < SPC2, "ring depth");
+    static_assert(NS >= 3 && NS - 1 < G1 + 16, "ring depth");
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    char* ring = wsm;
     p1f4* sx = (p1f4*)(wsm + NS * WS_SLOT) + wave * (G1 * 2 * 64) + lane;
     const float* sb2 = (const float*)(wsm + NS * WS_SLOT);   // [512] (after the last first layer)
     const float* sb3 = sb2 + 512;                             // [256]
     const int m0 = rb * 128 + wave * 16;
     const bool live = m0 < J.rows;
     const int xr0 = live ? map_row(J.map, m0) : 0;
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)ring;
-    const unsigned voff = lane * 16;
-    auto src_main2 = [&](int sc, int j) __attribute__((always_inline)) -> const unsigned short* {
-        if (j < G1) return a.P1 + ((size_t)(8 * sc + wave) * a.pg1s + j) * 1536;
-        const int s2 = j - G1, co = s2 >> 3, st = s2 & 7;
-        return a.P2 + ((size_t)(8 * (st & 3) + wave) * 16 + 2 * (2 * sc + co) + (st >> 2)) * 1536;
-    };
-    auto src_tail = [&](int l) __attribute__((always_inline)) -> const unsigned short* {
-        if (l < 2 * NB3) {   // layer 3 group-major: fragment f3 = 8l + wave = group x NB3 + tile
-            const int f3 = 8 * l + wave;
-            return a.P3 + ((size_t)(f3 % NB3) * 16 + f3 / NB3) * 1536;
-        }
-        return a.P2;   // (dummy refills past the end, never consumed)
-    };
-    auto src_next2 = [&](int sc, int j) __attribute__((always_inline)) -> const unsigned short* {
-        const int jt = j + NS - 1;
-        if (jt < SPC2) return src_main2(sc, jt);
-        return sc < 3 ? src_main2(sc + 1, jt - SPC2) : src_tail(jt - SPC2);
-    };
-    auto issue = [&](int k, const unsigned short* src) __attribute__((always_inline)) {
-        const unsigned dst = ring_lds + (unsigned)((k % NS) * WS_SLOT + wave * WS_FRAG);
-#pragma unroll
-        for (int p = 0; p < 3; ++p) w2_glds(src + p * 512, voff, dst + p * 1024);
+    WRing<NS, WS_SLOT, 3 * (NS - 3), w2_glds> R(wsm, lane, wave);
+    auto src_main2 = [&](int sc, int j) __attribute__((always_inline)) { return wr_src<G1>(a.P1, a.pg1s, a.P2, wave, sc, j); };
+    auto src_tail = [&](int l) __attribute__((always_inline)) {   // layer 3, then dummy refills
+        return l < 2 * NB3 ? wr_l3_src<NB3>(a.P3, l, wave) : a.P2;
     };
 #pragma unroll
-    for (int k = 0; k < NS - 1; ++k) issue(k, src_main2(0, k));
-    // x: the latent quads [pq1, pq1 + pkq) of X_H; k group g = quads 8g + q and 8g + 4 + q of them
-    const float* xp = a.X + (size_t)(xr0 >> 5) * a.x_ts + (size_t)a.pq1 * 128 + ((xr0 & 31) + n) * 4;
-    const p1f4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    float xsum = 0.f;
-#pragma unroll
-    for (int g = 0; g < G1; ++g) {
-        const int qa = 8 * g + q, qb = qa + 4;
-        const p1f4 va = live && qa < a.pkq ? *(const p1f4*)(xp + (size_t)qa * 128) : zero4;
-        const p1f4 vb = live && qb < a.pkq ? *(const p1f4*)(xp + (size_t)qb * 128) : zero4;
-        sx[(2 * g) * 64] = va;
-        sx[(2 * g + 1) * 64] = vb;
-        xsum += ((va[0] + va[1]) + (va[2] + va[3])) + ((vb[0] + vb[1]) + (vb[2] + vb[3]));
-    }
-    const bool xfin = ws_wave_finite(xsum);
+    for (int k = 0; k < NS - 1; ++k) R.issue(k, src_main2(0, k));
+    // x: the latent quads [pq1, pq1 + pkq) of X_H
+    const bool xfin = wr_xtile<G1>(sx, a.X, a.x_ts, xr0, n, q, a.pq1, a.pkq, live);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-
-    int k = 0;
-    auto sync = [&](const unsigned short* nsrc, bool tail_bias = false) __attribute__((always_inline)) -> const char* {
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(VM) : "memory");
-        const char* sl = ring + (k % NS) * WS_SLOT + lane * 16;
-        issue(k + NS - 1, nsrc);
-        if (tail_bias && wave < 3)   // b2 [512] | b3 [256] into the dead x tile (see wide_step_kernel)
-            w2_glds(wave < 2 ? a.pb2 + 256 * wave : a.pb3, voff, ring_lds + (unsigned)(NS * WS_SLOT) + wave * 1024);
-        ++k;
-        return sl;
-    };
-    uint4 fc[WS_AHEAD][3];
-    auto rd = [&](uint4 (&f)[3], const char* p) __attribute__((always_inline)) {
-        f[0] = *(const uint4*)p;
-        f[1] = *(const uint4*)(p + 1024);
-        f[2] = *(const uint4*)(p + 2048);
-    };
-#pragma unroll
-    for (int d = 0; d < WS_AHEAD; ++d) rd(fc[d], ring + d * WS_FRAG + lane * 16);
-    auto frag = [&](const char* sl, int i, uint4& w0, uint4& w1, uint4& w2) __attribute__((always_inline)) {
-        w0 = fc[0][0];
-        w1 = fc[0][1];
-        w2 = fc[0][2];
-#pragma unroll
-        for (int d = 0; d + 1 < WS_AHEAD; ++d)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fc[d][p] = fc[d + 1][p];
-        rd(fc[WS_AHEAD - 1], i + WS_AHEAD <= WS_NW - 1 ? sl + (i + WS_AHEAD) * WS_FRAG
-                                                       : ring + (k % NS) * WS_SLOT + (i + WS_AHEAD - WS_NW) * WS_FRAG + lane * 16);
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    R.prime();
 
     floatx4 acc[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int sc = 0; sc < 4; ++sc) {
+        auto sync = [&](int j, bool tail_bias) __attribute__((always_inline)) {
+            return R.sync(wr_next<G1, NS>(src_main2, src_tail, sc, j), [&](int) __attribute__((always_inline)) {
+                if (tail_bias && wave < 3)   // b2 [512] | b3 [256] into the dead x tile (see wide_step_kernel)
+                    w2_glds(wave < 2 ? a.pb2 + 256 * wave : a.pb3, R.voff, R.lds + (unsigned)(NS * WS_SLOT) + wave * 1024);
+            });
+        };
         floatx4 a1[8];
 #pragma unroll
         for (int b = 0; b < 8; ++b) a1[b] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int g = 0; g < G1; ++g) {
-            const char* sl = sync(src_next2(sc, g));
+            const char* sl = sync(g, false);
             const p1f4 x0 = sx[(2 * g) * 64], x1 = sx[(2 * g + 1) * 64];
             const WSX xb = ws_opnd(make_float4(x0[0], x0[1], x0[2], x0[3]), make_float4(x1[0], x1[1], x1[2], x1[3]), xfin);
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 uint4 w0, w1, w2;
-                frag(sl, b, w0, w1, w2);
+                R.frag(sl, b, w0, w1, w2);
                 ws_prod(a1[b], w0, w1, w2, xb);
             }
         }
@@ -214,25 +156,19 @@ DEVI void wh_pi(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
                 const WSX xb = ws_opnd(make_float4(t0[0], t0[1], t0[2], t0[3]), make_float4(t1[0], t1[1], t1[2], t1[3]), hfin);
 #pragma unroll
                 for (int jq = 0; jq < 4; ++jq) {
-                    const char* sl = sync(src_next2(sc, G1 + 8 * co + 4 * s2 + jq), sc == 3 && co == 0 && s2 == 0 && jq == 0);
+                    const char* sl = sync(G1 + 8 * co + 4 * s2 + jq, sc == 3 && co == 0 && s2 == 0 && jq == 0);
 #pragma unroll
                     for (int jj = 0; jj < 8; ++jj) {
                         uint4 w0, w1, w2;
-                        frag(sl, jj, w0, w1, w2);
+                        R.frag(sl, jj, w0, w1, w2);
                         ws_prod(acc[8 * jq + jj], w0, w1, w2, xb);
                     }
                 }
             }
         }
     }
-    int l16 = (int)voff;
-    asm volatile("" : "+v"(l16));
-    const int n_ep = (l16 >> 4) & 15, q_ep = (l16 >> 8) & 3;
-    auto h2t = [&](int t) __attribute__((always_inline)) -> float4 {
-        const float4 bv = *(const float4*)(sb2 + 16 * t + 4 * q);
-        return make_float4(elu_f(acc[t][0] + bv.x), elu_f(acc[t][1] + bv.y), elu_f(acc[t][2] + bv.z),
-                           elu_f(acc[t][3] + bv.w));
-    };
+    int n_ep, q_ep;
+    wr_lane_ep(R.voff, n_ep, q_ep);
     // ---- layer 3: mu = W3 h2 + b3 (NB3 16-column tiles), group-major fragments, 8 per step
     floatx4 a3[NB3];
 #pragma unroll
@@ -240,14 +176,14 @@ DEVI void wh_pi(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
     const char* sl = nullptr;
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-        const float4 ha = h2t(2 * g), hb = h2t(2 * g + 1);
+        const float4 ha = wr_h2t(acc, sb2, 2 * g, q), hb = wr_h2t(acc, sb2, 2 * g + 1, q);
         const WSX xb = ws_opnd(ha, hb, ws_wave_finite(ws_sum8(ha, hb)));
 #pragma unroll
         for (int jj = 0; jj < NB3; ++jj) {
             const int f = g * NB3 + jj;
-            if (f % WS_NW == 0) sl = sync(src_tail(f / WS_NW + NS - 1));
+            if (f % WS_NW == 0) sl = R.sync(src_tail(f / WS_NW + NS - 1));
             uint4 w0, w1, w2;
-            frag(sl, f % WS_NW, w0, w1, w2);
+            R.frag(sl, f % WS_NW, w0, w1, w2);
             ws_prod(a3[jj], w0, w1, w2, xb);
         }
     }
@@ -287,91 +223,30 @@ DEVI void wh_pi(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
 template <int G1, int NST, int GX>
 DEVI void wh_q(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
     constexpr int NS = ws_ns<GX>();
-    constexpr int VM = 3 * (NS - 3);
     constexpr int SPC2 = G1 + 16;
     constexpr int NSS = WH_STATS_ON * (NST / 8) * G1;   // statistics steps: 8 blocks x one k group each
     static_assert(NST % 8 == 0 && NS >= 3 && NS - 1 < SPC2 && NS - 1 <= NSS + SPC2, "ring depth");
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const WHQHead Hd = J.head ? a.q[1] : a.q[0];   // (selects: no dynamic index into the kernel arguments)
-    char* ring = wsm;
     p1f4* sx = (p1f4*)(wsm + NS * WS_SLOT) + wave * (G1 * 2 * 64) + lane;
     const float* sv = (const float*)(wsm + NS * WS_SLOT);   // b2 | g2 | be2 | w3 [512] each (after the last first layer)
     const int m0 = rb * 128 + wave * 16;
     const bool live = m0 < J.rows;
     const int xr0 = live ? map_row(J.map, m0) : 0;
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)ring;
-    const unsigned voff = lane * 16;
+    WRing<NS, WS_SLOT, 3 * (NS - 3), w2_glds> R(wsm, lane, wave);
     // the static fragment stream: NSS statistics steps, then 4 super-chunks of G1 + 16 steps, then dummies
-    auto src_main2 = [&](int sc, int j) __attribute__((always_inline)) -> const unsigned short* {
-        if (sc > 3) return Hd.X2;
-        if (j < G1) return Hd.X1 + ((size_t)(8 * sc + wave) * a.qg1s + j) * 1536;
-        const int s2 = j - G1, co = s2 >> 3, st = s2 & 7;
-        return Hd.X2 + ((size_t)(8 * (st & 3) + wave) * 16 + 2 * (2 * sc + co) + (st >> 2)) * 1536;
-    };
+    auto src_main2 = [&](int sc, int j) __attribute__((always_inline)) { return wr_src<G1>(Hd.X1, a.qg1s, Hd.X2, wave, sc, j); };
+    auto src_tail = [&](int) __attribute__((always_inline)) { return Hd.X2; };
     auto src_abs = [&](int j) __attribute__((always_inline)) -> const unsigned short* {   // step j of the stream
         if (j < NSS) return Hd.S + ((size_t)(8 * (j / G1) + wave) * a.qg1s + j % G1) * 1536;
         return src_main2((j - NSS) / SPC2, (j - NSS) % SPC2);
     };
-    auto src_next2 = [&](int sc, int j) __attribute__((always_inline)) -> const unsigned short* {
-        const int jt = j + NS - 1;
-        if (jt < SPC2) return src_main2(sc, jt);
-        return src_main2(sc + 1, jt - SPC2);
-    };
-    auto issue = [&](int k, const unsigned short* src) __attribute__((always_inline)) {
-        const unsigned dst = ring_lds + (unsigned)((k % NS) * WS_SLOT + wave * WS_FRAG);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) w2_glds(src + p * 512, voff, dst + p * 1024);
-    };
-#pragma unroll
-    for (int k = 0; k < NS - 1; ++k) issue(k, src_abs(k));
-    const float* xp = a.X + (size_t)(xr0 >> 5) * a.x_ts + ((xr0 & 31) + n) * 4;
-    const p1f4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    float xsum = 0.f;
-#pragma unroll
-    for (int g = 0; g < G1; ++g) {
-        const int qa = 8 * g + q, qb = qa + 4;
-        const p1f4 va = live && qa < a.qkq ? *(const p1f4*)(xp + (size_t)qa * 128) : zero4;
-        const p1f4 vb = live && qb < a.qkq ? *(const p1f4*)(xp + (size_t)qb * 128) : zero4;
-        sx[(2 * g) * 64] = va;
-        sx[(2 * g + 1) * 64] = vb;
-        xsum += ((va[0] + va[1]) + (va[2] + va[3])) + ((vb[0] + vb[1]) + (vb[2] + vb[3]));
-    }
-    const bool xfin = ws_wave_finite(xsum);
+    for (int k = 0; k < NS - 1; ++k) R.issue(k, src_abs(k));
+    const bool xfin = wr_xtile<G1>(sx, a.X, a.x_ts, xr0, n, q, 0, a.qkq, live);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-
-    int k = 0;
-    auto sync = [&](const unsigned short* nsrc, bool tail_bias = false) __attribute__((always_inline)) -> const char* {
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(VM) : "memory");
-        const char* sl = ring + (k % NS) * WS_SLOT + lane * 16;
-        issue(k + NS - 1, nsrc);
-        if (tail_bias) {   // b2 | g2 | be2 | w3 into the dead x tile: one 1 KiB LDS-DMA per wave
-            const float* vs[4] = {Hd.b2, Hd.g2, Hd.be2, Hd.w3};
-            w2_glds(vs[wave >> 1] + 256 * (wave & 1), voff, ring_lds + (unsigned)(NS * WS_SLOT) + wave * 1024);
-        }
-        ++k;
-        return sl;
-    };
-    uint4 fc[WS_AHEAD][3];
-    auto rd = [&](uint4 (&f)[3], const char* p) __attribute__((always_inline)) {
-        f[0] = *(const uint4*)p;
-        f[1] = *(const uint4*)(p + 1024);
-        f[2] = *(const uint4*)(p + 2048);
-    };
-#pragma unroll
-    for (int d = 0; d < WS_AHEAD; ++d) rd(fc[d], ring + d * WS_FRAG + lane * 16);
-    auto frag = [&](const char* sl, int i, uint4& w0, uint4& w1, uint4& w2) __attribute__((always_inline)) {
-        w0 = fc[0][0];
-        w1 = fc[0][1];
-        w2 = fc[0][2];
-#pragma unroll
-        for (int d = 0; d + 1 < WS_AHEAD; ++d)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fc[d][p] = fc[d + 1][p];
-        rd(fc[WS_AHEAD - 1], i + WS_AHEAD <= WS_NW - 1 ? sl + (i + WS_AHEAD) * WS_FRAG
-                                                       : ring + (k % NS) * WS_SLOT + (i + WS_AHEAD - WS_NW) * WS_FRAG + lane * 16);
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    R.prime();
     // the lane's 4 features of tile t (16t + 4q + i) of a per-feature vector, by scalar loads
     const bool qb0 = (q & 1) != 0, qb1 = (q & 2) != 0;
     const w2cf* vb1 = wh_cp(Hd.b1);
@@ -396,13 +271,13 @@ DEVI void wh_q(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
         for (int b = 0; b < 8; ++b) as[b] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int g = 0; g < G1; ++g) {
-            const char* sl = sync(src_abs(ss * G1 + g + NS - 1));
+            const char* sl = R.sync(src_abs(ss * G1 + g + NS - 1));
             const p1f4 x0 = sx[(2 * g) * 64], x1 = sx[(2 * g + 1) * 64];
             const WSX xb = ws_opnd(make_float4(x0[0], x0[1], x0[2], x0[3]), make_float4(x1[0], x1[1], x1[2], x1[3]), xfin);
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 uint4 w0, w1, w2;
-                frag(sl, b, w0, w1, w2);
+                R.frag(sl, b, w0, w1, w2);
                 ws_prod(as[b], w0, w1, w2, xb);
             }
         }
@@ -427,18 +302,26 @@ DEVI void wh_q(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
     for (int j = 0; j < 32; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int sc = 0; sc < 4; ++sc) {
+        auto sync = [&](int j, bool tail_bias) __attribute__((always_inline)) {
+            return R.sync(wr_next<G1, NS>(src_main2, src_tail, sc, j), [&](int) __attribute__((always_inline)) {
+                if (tail_bias) {   // b2 | g2 | be2 | w3 into the dead x tile: one 1 KiB LDS-DMA per wave
+                    const float* vs[4] = {Hd.b2, Hd.g2, Hd.be2, Hd.w3};
+                    w2_glds(vs[wave >> 1] + 256 * (wave & 1), R.voff, R.lds + (unsigned)(NS * WS_SLOT) + wave * 1024);
+                }
+            });
+        };
         floatx4 a1[8];
 #pragma unroll
         for (int b = 0; b < 8; ++b) a1[b] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int g = 0; g < G1; ++g) {
-            const char* sl = sync(src_next2(sc, g));
+            const char* sl = sync(g, false);
             const p1f4 x0 = sx[(2 * g) * 64], x1 = sx[(2 * g + 1) * 64];
             const WSX xb = ws_opnd(make_float4(x0[0], x0[1], x0[2], x0[3]), make_float4(x1[0], x1[1], x1[2], x1[3]), xfin);
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 uint4 w0, w1, w2;
-                frag(sl, b, w0, w1, w2);
+                R.frag(sl, b, w0, w1, w2);
                 ws_prod(a1[b], w0, w1, w2, xb);
             }
         }
@@ -470,11 +353,11 @@ DEVI void wh_q(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
                 const WSX xb = ws_opnd(make_float4(t0[0], t0[1], t0[2], t0[3]), make_float4(t1[0], t1[1], t1[2], t1[3]), hfin);
 #pragma unroll
                 for (int jq = 0; jq < 4; ++jq) {
-                    const char* sl = sync(src_next2(sc, G1 + 8 * co + 4 * s2 + jq), sc == 3 && co == 0 && s2 == 0 && jq == 0);
+                    const char* sl = sync(G1 + 8 * co + 4 * s2 + jq, sc == 3 && co == 0 && s2 == 0 && jq == 0);
 #pragma unroll
                     for (int jj = 0; jj < 8; ++jj) {
                         uint4 w0, w1, w2;
-                        frag(sl, jj, w0, w1, w2);
+                        R.frag(sl, jj, w0, w1, w2);
                         ws_prod(acc[8 * jq + jj], w0, w1, w2, xb);
                     }
                 }
@@ -483,9 +366,8 @@ DEVI void wh_q(const WHArgs& a, const WHJob& J, int rb, char* wsm) {
     }
     // the ring's dummy refills and the vectors' DMA landed; every wave's DMA visible
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    int l16 = (int)voff;
-    asm volatile("" : "+v"(l16));
-    const int n_ep = (l16 >> 4) & 15, q_ep = (l16 >> 8) & 3;
+    int n_ep, q_ep;
+    wr_lane_ep(R.voff, n_ep, q_ep);
     auto lv = [&](int vsel, int t) __attribute__((always_inline)) -> float4 {
         return *(const float4*)(sv + vsel * 512 + 16 * t + 4 * q_ep);
     };
@@ -663,7 +545,7 @@ __global__ void __launch_bounds__(1024) qstat_chol_kernel(const QStatArgs a) {
         }
         __syncthreads();
     }
-    // the block: element (r, kk) of the [nsr][32 g1s] panel -> x6q block (r / 16, kk / 32), lane, element
+    // the block: element (r, kk) of the [nsr][32 g1s] panel into the x6q layout
     const int G = a.g1s, K = 32 * G;
     unsigned short* d = a.S + (size_t)h * (a.nsr / 16) * G * 1536;
     for (int e = tid; e < a.nsr * K; e += 1024) {
@@ -675,14 +557,7 @@ __global__ void __launch_bounds__(1024) qstat_chol_kernel(const QStatArgs a) {
             if (r == 0) v = mu[src];
             else if (r - 1 < n && src >= r - 1) v = U[ix(r - 1, src)];
         }
-        __bf16 hi, md, lo;
-        split3((float)v, hi, md, lo);
-        const int nb = r / 16, g = kk / 32, k2 = kk % 32;
-        const int lane = (r % 16) + 16 * ((k2 % 16) / 4), j = 4 * (k2 / 16) + (k2 % 4);
-        const size_t blk = (size_t)nb * G + g;
-        d[(blk * 3 + 0) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, hi);
-        d[(blk * 3 + 1) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, md);
-        d[(blk * 3 + 2) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, lo);
+        x6q_put(d, G, r, kk, (float)v);
     }
     for (int r = tid; r < a.nsr; r += 1024)
         a.bs[h * a.nsr + r] = r == 0 ? (float)mu[n - 1] : r - 1 < n ? (float)U[ix(r - 1, n - 1)] : 0.f;
@@ -693,14 +568,7 @@ __global__ void __launch_bounds__(1024) qstat_chol_kernel(const QStatArgs a) {
         const int src = kk < a.A ? kk : kk >= a.Ap && kk < a.Ap + a.L ? a.A + kk - a.Ap : -1;
         const double g = (double)a.g1[h * a.M + r];
         const double v = src >= 0 ? g * ((double)a.W1[qs_pidx(h * a.M + r, kk, a.Kx)] - mu[src]) : 0.0;
-        __bf16 hi, md, lo;
-        split3((float)v, hi, md, lo);
-        const int nb = r / 16, gq = kk / 32, k2 = kk % 32;
-        const int lane = (r % 16) + 16 * ((k2 % 16) / 4), j = 4 * (k2 / 16) + (k2 % 4);
-        const size_t blk = (size_t)nb * G + gq;
-        f[(blk * 3 + 0) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, hi);
-        f[(blk * 3 + 1) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, md);
-        f[(blk * 3 + 2) * 512 + lane * 8 + j] = __builtin_bit_cast(unsigned short, lo);
+        x6q_put(f, G, r, kk, (float)v);
     }
     for (int r = tid; r < a.M; r += 1024)
         a.bf[h * a.M + r] = (float)((double)a.g1[h * a.M + r] * ((double)a.b1[h * a.M + r] - mu[n - 1]));

@@ -1,64 +1,25 @@
-// wide_step.inc -- included by tdmpc_kernels.hip inside its anonymous namespace (uses its X6B split, elu_f, RowMap,
-// the x6q weight layout and the reference-rounding helpers).
+// wide_step.inc -- included by tdmpc_kernels.hip inside its anonymous namespace after wide_ring.inc (the design: the
+// LDS weight ring with its read-ahead, the static fragment stream, the x tile and the shape of the two-layer
+// super-chunk and of the group-major last layer; uses also RowMap, elu_f and the reference-rounding helpers).
 //
 // TOLD.next (/root/reference/src/algorithm/tdmpc.py:34-37: _dynamics and _reward, helper.mlp helper.py:169-176) plus
 // the return update of estimate_value (tdmpc.py:88-90) for the wide step launches (>= one 128-row block per CU and
 // head: B >= 32 envs at N = 512), on 128-row workgroups.
 //
-// Why a second step kernel. chain_kernel carries a 32-row block through a head with the hidden activations in LDS;
-// every workgroup streams the head's whole x6 weight set (2.3 MB for the dynamics head) from L2 into registers, so a CU
-// needs 64 B/clk of weight fragments to keep its MFMA pipes busy and its vector-memory path delivers ~35 B/clk
-// (profiles/r02/x6_stream_probe.txt): MFMA busy ~0.5, 0.42 of the x6 roof. Rows per weight fragment are what buy that
-// back, and LDS (2 KB per fp32 hidden row) capped chain_kernel at 32.
-//
-// Design (one workgroup per CU, 8 waves = two per SIMD, 256 registers per lane):
-//  * Each wave owns 16 ROWS and ALL 512 hidden columns: the hidden layer's accumulators (16 x 512 fp32 = 128
-//    registers per lane, 32 tiles of v_mfma_f32_16x16x32_bf16) never leave registers, so the activations need no LDS.
-//    Two waves per SIMD: one wave's activation splits, ELUs, LDS reads and barrier waits run under the other's MFMAs.
-//  * Layer 1 streams into layer 2 by 64-column chunks: chunk c of h1 = ELU(W1[64c:64c+64] x + b1) is produced in
-//    registers (4 accumulator tiles) and consumed at once as the 64-deep k slice [64c, 64c+64) of layer 2 -- the
-//    accumulator-as-operand map: a lane of tile t holds features 16t + 4q + i (q = lane >> 4) of its row, so tiles 2s
-//    and 2s + 1 together are the B operand of k group s in the x6q k order (below) with no data movement.
-//  * Layer 3 of the dynamics head (M -> L, L rounded up to 16-row tiles) reads h2 = ELU(acc + b2) from the same
-//    registers; the reward head's Linear(M -> 1) is a per-lane dot + two cross-lane shuffles (each wave holds whole
-//    rows: no cross-wave sums).
-//  * Weights: the head's x6q fragments (16 output features x 32 k x 3 bf16 planes = 3 KiB) are streamed from L2 into
-//    an LDS ring ONCE per workgroup by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave instruction, no VGPR) and read
-//    by all 8 waves: 128 rows per fragment, 16 B/clk of L2 -> LDS traffic per CU at the full MFMA rate. Pipeline
-//    step = 8 fragments (one loaded by each wave, 3 DMA instructions); per step: counted vmcnt (this wave's DMA of
-//    the step and the next has landed) + one barrier (every wave's has; every wave is done with the slot about to be
-//    refilled), then the refill of the step ws_ns() - 1 ahead, then 48 MFMAs per wave. The fragment stream is static
-//    (super-chunk-major: W1 blocks 8sc..8sc+7 over the first-layer groups, then W2's 32 blocks over k groups
-//    4sc..4sc+3; then W3 group-major), its addresses resolved per step position at compile time, and every wave issues exactly 3 DMA
-//    instructions per step, so the vmcnt count is a constant.
-//  * Each wave reads the fragments two ahead of its products (the LDS latency runs under twelve MFMAs); a
-//    sched_barrier pins the reads above the products they precede.
-//  * The x tile (the wave's 16 input rows, fp32) sits in LDS beside the ring and is split into bf16 parts again by
-//    super-chunk; b1 comes by scalar loads; b2 / w3 / b3 are DMA'd into the x tile's place once the last
-//    super-chunk's first layer is done.
+// This kernel's own:
+//  * Two heads per launch. Layer 3 of the dynamics head (M -> L, L rounded up to 16-row tiles) is the design's last
+//    layer; the reward head's Linear(M -> 1) is a per-lane dot + two cross-lane shuffles (each wave holds whole rows:
+//    no cross-wave sums).
+//  * b1 comes by scalar loads; b2 / w3 / b3 are DMA'd into the x tile's place once the last super-chunk's first layer
+//    is done.
 //  * XCD-aware placement: dispatch groups 0-3 (blocks b with b % 8 < 4) run the dynamics head, 4-7 the reward head,
 //    so each XCD's 4 MB L2 holds one head's x6 weights (2.3 / 1.9 MB) rather than both (4.2 MB). Speed only.
-//  * Products: the x6 form (six v_mfma_f32_16x16x32_bf16 per fp32 product, fp32 accumulation), non-finite-safe split
-//    (split8) for every activation. The MFMAs are builtins (the compiler schedules them and their hazards); only the
-//    LDS-DMA and the per-step wait are inline asm.
 // Measured (profiles/r04/, DESIGN.md §4): 104 us per humanoid B = 32 launch (16,384 rows x 2 heads), MFMA busy 0.55;
 // the losing variants of rounds 3-4 (paired fragments, pipelined splits, register-staged or spread fills,
 // non-temporal fills, rotated chunk order, one-chunk first layer) live in git history and DESIGN.md §4's table.
 // Shape limits (use_wide): M = 512, N and T multiples of 16 (a wave's 16 rows lie in one X panel block), first-layer
 // 32-k groups <= 5, L in (48, 64] or (96, 112]; with the per-env first-layer bias (z0c, t = 0) env groups of whole
 // workgroups.
-
-constexpr int WS_NW = 8;                         // waves, two per SIMD
-constexpr int WS_AHEAD = 2;                      // weight fragments read ahead of their products (3: 1.3 % slower, spills)
-constexpr int WS_FRAG = 3072;                    // bytes of one x6q fragment (3 planes x 1 KiB)
-constexpr int WS_SLOT = WS_NW * WS_FRAG;         // one pipeline step: 8 fragments
-// LDS: ring of ws_ns() steps | x tile [WS_NW waves][G1 groups][2 halves][64 lanes] float4 (re-read by every chunk's
-// first layer; after the last one the head's b2 [512] | w3 [512] | b3 [256] land in its place)
-template <int G1> constexpr int ws_xbytes() { return WS_NW * G1 * 2048; }
-template <int G1> constexpr int ws_ns() {   // ring steps beside the x tile, at most 6: 6 / 5 / 4 / 4 / 3 for G1 = 1..5
-    return (160 * 1024 - ws_xbytes<G1>()) / WS_SLOT < 6 ? (160 * 1024 - ws_xbytes<G1>()) / WS_SLOT : 6;
-}
-template <int G1> constexpr size_t ws_lds() { return (size_t)ws_ns<G1>() * WS_SLOT + ws_xbytes<G1>(); }
 
 // wide_step_kernel modes (template MODE bits):
 //  WS_XS   the x operand streamed through the ring (latent 512: 17 first-layer 32-k groups, a 272 KB x tile, do not
@@ -110,70 +71,15 @@ struct WideArgs {
     unsigned long long* stamps;  // diagnostic build (-DWS_STAMPS): per-step shader clocks of workgroups 0 and 4
 };
 
-// One 1 KiB LDS-DMA (global_load_lds_dwordx4: lane l's 16 bytes at gsrc + voff land at lds + 16 l) in inline asm, so
-// hipcc neither counts it nor inserts its conservative vmcnt(0) before every later ds_read of the ring (it cannot see
-// which LDS bytes the DMA writes); the kernel waits with counted vmcnt itself. M0 is saved and restored. The SGPR
-// operands are SALU results (the wave index is read into an SGPR once at kernel start), so no VALU-write -> VMEM-read
-// wait is needed (a v_readfirstlane-produced base would need s_nop 4 first).
-DEVI void ws_glds(const void* gsrc, unsigned voff, unsigned lds) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(lds), "s"(gsrc)
-                 : "memory");
-}
-
-// six x6 products into one accumulator, small terms first: (w_mid, x_mid), (w_lo, x_hi*), (w_hi, x_lo), (w_mid, x_hi*),
-// (w_hi, x_mid), (w_hi, x_hi); x_hi* = 0 where x is not finite (the general split)
-DEVI void w2_x6(floatx4& acc, const uint4& u0, const uint4& u1, const uint4& u2, const X6U& b) {
-    const bf16x8_t w0 = as_bf16x8(u0), w1 = as_bf16x8(u1), w2 = as_bf16x8(u2);
-    const bf16x8_t bh = as_bf16x8(b.h), bm = as_bf16x8(b.m), bl = as_bf16x8(b.l);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, bh, acc, 0, 0, 0);
-}
-
-// The activation operand in the three-plane form: the finite-only split when the wave's values are all finite (a
-// wave-uniform branch; 100.5 vs 103.3 us per humanoid B = 32 launch against split8's four planes), the general one
-// (non-finite x -> h = m = 0, l = x, so only w_hi x carries it) otherwise; products bitwise split8's for finite operands
-typedef X6U WSX;
-DEVI WSX ws_opnd(const float4& a0, const float4& a1, bool fin) {
-#ifdef WS_DIAG_NOSPLIT
-    (void)fin;
-    X6U b;
-    b.h = b.m = b.l = *(const uint4*)&a0;
-    return b;
+// the step kernel's LDS-DMA: ws_glds where every step position is compile-time (SGPR operands), w2_glds elsewhere
+template <bool SGPR>
+DEVI void ws_dma(const void* gsrc, unsigned voff, unsigned lds) {
+#ifndef WS_DIAG_NODMA
+    if constexpr (SGPR) ws_glds(gsrc, voff, lds);
+    else w2_glds(gsrc, voff, lds);
 #else
-    X6U b;
-    if (fin) b = w2_split8_fin(a0, a1);
-    else b = w2_split8(a0, a1);
-    return b;
+    (void)gsrc; (void)voff; (void)lds;
 #endif
-}
-DEVI void ws_prod(floatx4& acc, const uint4& u0, const uint4& u1, const uint4& u2, const WSX& b) { w2_x6(acc, u0, u1, u2, b); }
-
-// per-feature vectors read through the constant address space: wave-uniform loads there become scalar loads
-// (s_load, counted by lgkmcnt, scheduled by the compiler), which leave the ring's counted vmcnt waits alone
-typedef const __attribute__((address_space(4))) float w2cf;
-
-// ws_glds with its scalar operands made scalar explicitly: under SGPR pressure the compiler may keep a uniform value in
-// a VGPR, which the inline asm's "s" constraint does not convert; v_readfirstlane does, and the s_nop 4 covers the
-// VALU-writes-SGPR -> VMEM-reads-it hazard the compiler cannot see through the asm
-DEVI void w2_glds(const void* gsrc, unsigned voff, unsigned lds) {
-    const unsigned long long g = (unsigned long long)gsrc;
-    const unsigned glo = __builtin_amdgcn_readfirstlane((unsigned)g), ghi = __builtin_amdgcn_readfirstlane((unsigned)(g >> 32));
-    const unsigned long long gs = ((unsigned long long)ghi << 32) | glo;
-    const unsigned ls = __builtin_amdgcn_readfirstlane(lds);
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(ls), "s"(gs)
-                 : "memory");
 }
 
 template <int G1, int NB3, int MODE>
@@ -186,10 +92,7 @@ wide_step_kernel(const WideArgs a) {
     // k + 1's first fragment is read during step k). WS_XS: at most step k + 2's refill (3 weight DMAs, + 2 x DMAs on a
     // first-layer step, of which vmcnt(3) lets the x pair or the first two weight DMAs land early -- stricter, still exact)
     constexpr int VM = XS ? 3 : 3 * (WS_NS - 3);
-    // Paired chunks: super-chunk sc = 64-column chunks 2sc, 2sc + 1; its first-layer steps take one k group each over
-    // the pair's 8 W1 blocks (each group's operand split feeds 48 MFMAs, once per pair of chunks; 101.2 vs 102.8 us
-    // against one chunk at a time), then the two chunks' 8 layer-2 steps each. Steps per super-chunk: G1 + 16.
-    constexpr int SPC2 = G1 + 16;
+    constexpr int SPC2 = G1 + 16;   // steps per super-chunk
     // the dynamics head's layer 3 after the last super-chunk: NB3 <= 8 tiles in one group-major pass (2 NB3 steps of 8
     // fragments), or (latent 512) NB3 / 8 passes of 8 tiles over the 16 k groups (16 steps each, h2's operand split
     // again per pass: a3 stays at 8 tiles beside the 32 of h2); none with WS_OUTH
@@ -207,7 +110,6 @@ wide_step_kernel(const WideArgs a) {
     const int rb = (bid >> 3) * 4 + (bid & 3);
     if (rb >= a.nrb) return;                          // (grid padded to whole dispatch groups; uniform per workgroup)
     const WideHead& P = a.p[head];
-    char* ring = wsm;
     // this lane's x (not WS_XS): group g at [2g], [2g + 1]
     p1f4* sx = (p1f4*)(wsm + WS_NS * WS_SLOT) + wave * (G1 * 2 * 64) + lane;
     const float* sb2 = (const float*)(wsm + wsm_bias<G1, MODE>());   // [512] (after the chunk loop)
@@ -218,84 +120,48 @@ wide_step_kernel(const WideArgs a) {
     const int xr0 = live ? map_row(a.amap, m0) : 0;   // its 16 rows lie in one X panel block
 
     // ---- the first steps' weights in flight first (LDS-DMA), then the wave's input rows, biases and G
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)ring;
-    const unsigned voff = lane * 16;
-    // The static fragment stream: this wave's fragment of step j (compile-time) of super-chunk sc, and of tail step l
-    // (the dynamics head's layer 3 after the last super-chunk; dummy refills of any valid address past the end, never
-    // consumed)
-    auto src_main2 = [&](int sc, int j) __attribute__((always_inline)) -> const unsigned short* {
-        if (j < G1) return P.X1 + ((size_t)(8 * sc + wave) * a.g1s + j) * 1536;
-        const int s2 = j - G1, co = s2 >> 3, st = s2 & 7;
-        return P.X2 + ((size_t)(8 * (st & 3) + wave) * 16 + 2 * (2 * sc + co) + (st >> 2)) * 1536;
-    };
+    WRing<WS_NS, SLOT, VM, ws_dma<MODE == 0 && NB3 <= 8>> R(wsm, lane, wave);
+    auto src_main2 = [&](int sc, int j) __attribute__((always_inline)) { return wr_src<G1>(P.X1, a.g1s, P.X2, wave, sc, j); };
+    // the stream's tail: the dynamics head's layer 3 after the last super-chunk, then dummy refills
     auto src_tail = [&](int l) __attribute__((always_inline)) -> const unsigned short* {
         if (!OUTH && head == 0 && l < TAIL) {
             if constexpr (NB3 > 8) {   // pass p = l / 16 over group g = l % 16: tile 8p + wave
                 return a.X3 + ((size_t)(8 * (l >> 4) + wave) * 16 + (l & 15)) * 1536;
-            } else {                   // W3 group-major: fragment f3 = 8l + wave = group x NB3 + tile
-                const int f3 = 8 * l + wave;
-                return a.X3 + ((size_t)(f3 % NB3) * 16 + f3 / NB3) * 1536;
+            } else {
+                return wr_l3_src<NB3>(a.X3, l, wave);
             }
         }
         return P.X2;
     };
-    // refill target of step j of super-chunk sc: step j + WS_NS - 1 of it, or of the next one, or the tail; its x group
-    // (WS_XS: first-layer steps stream their x beside the weights) or -1
-    auto src_next2 = [&](int sc, int j) __attribute__((always_inline)) -> const unsigned short* {
-        const int jt = j + WS_NS - 1;
-        if (jt < SPC2) return src_main2(sc, jt);
-        return sc < 3 ? src_main2(sc + 1, jt - SPC2) : src_tail(jt - SPC2);
+    auto src_next2 = [&](int sc, int j) __attribute__((always_inline)) { return wr_next<G1, WS_NS>(src_main2, src_tail, sc, j); };
+    // WS_XS: first-layer steps stream their x beside the weights -- the wave's x rows of group xg (row block base by
+    // SGPR, row and quad by lane offset; quads past the input clamped to a valid address and zeroed after the read) into
+    // the x area of step kk's slot
+    const float* xrow = a.X + (size_t)(xr0 >> 5) * a.x_ts;
+    const unsigned xlo = (unsigned)(((xr0 & 31) + n) * 16);
+    auto issue_x = [&](int kk, int xg) __attribute__((always_inline)) {
+        if constexpr (XS) {
+            if (xg >= 0) {
+                const unsigned xdst = R.lds + (unsigned)((kk % WS_NS) * SLOT + WS_SLOT + wave * 2048);
+                const int qa = min(8 * xg + q, a.kq - 1), qb = min(8 * xg + 4 + q, a.kq - 1);
+                ws_dma<false>(xrow, xlo + (unsigned)qa * 512u, xdst);
+                ws_dma<false>(xrow, xlo + (unsigned)qb * 512u, xdst + 1024);
+            }
+        }
     };
+    // the x group of step j's refill target (step j + WS_NS - 1 of super-chunk sc, or of the next one), or -1
     auto xg_next2 = [&](int sc, int j) __attribute__((always_inline)) -> int {
         const int jt = j + WS_NS - 1;
         if (jt < SPC2) return jt < G1 ? jt : -1;
         return sc < 3 && jt - SPC2 < G1 ? jt - SPC2 : -1;
     };
-    // WS_XS: the wave's x rows (row block base by SGPR, row and quad by lane offset; quads past the input clamped to a
-    // valid address and zeroed after the read)
-    const float* xrow = a.X + (size_t)(xr0 >> 5) * a.x_ts;
-    const unsigned xlo = (unsigned)(((xr0 & 31) + n) * 16);
-    auto issue = [&](int k, const unsigned short* src, int xg) __attribute__((always_inline)) {
-        const unsigned dst = ring_lds + (unsigned)((k % WS_NS) * SLOT + wave * WS_FRAG);
-#ifndef WS_DIAG_NODMA
-        if constexpr (MODE == 0 && NB3 <= 8) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) ws_glds(src + p * 512, voff, dst + p * 1024);
-        } else {   // (runtime loops over steps: the operands made scalar explicitly)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) w2_glds(src + p * 512, voff, dst + p * 1024);
-        }
-        if constexpr (XS) {
-            if (xg >= 0) {
-                const unsigned xdst = ring_lds + (unsigned)((k % WS_NS) * SLOT + WS_SLOT + wave * 2048);
-                const int qa = min(8 * xg + q, a.kq - 1), qb = min(8 * xg + 4 + q, a.kq - 1);
-                w2_glds(xrow, xlo + (unsigned)qa * 512u, xdst);
-                w2_glds(xrow, xlo + (unsigned)qb * 512u, xdst + 1024);
-            }
-        }
-#else
-        (void)src; (void)dst; (void)xg;
-#endif
-    };
-#pragma unroll
-    for (int k = 0; k < WS_NS - 1; ++k) issue(k, src_main2(0, k), k < G1 ? k : -1);
-    const p1f4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    bool xfin = true;
-    if constexpr (!XS) {
-        // x: k group g = quads 8g + q and 8g + 4 + q of row n (the x6q k order); quads past the input are zero
-        const float* xp = a.X + (size_t)(xr0 >> 5) * a.x_ts + ((xr0 & 31) + n) * 4;
-        float xsum = 0.f;
-#pragma unroll
-        for (int g = 0; g < G1; ++g) {
-            const int qa = 8 * g + q, qb = qa + 4;
-            const p1f4 va = live && qa < a.kq ? *(const p1f4*)(xp + (size_t)qa * 128) : zero4;
-            const p1f4 vb = live && qb < a.kq ? *(const p1f4*)(xp + (size_t)qb * 128) : zero4;
-            sx[(2 * g) * 64] = va;
-            sx[(2 * g + 1) * 64] = vb;
-            xsum += ((va[0] + va[1]) + (va[2] + va[3])) + ((vb[0] + vb[1]) + (vb[2] + vb[3]));
-        }
-        xfin = ws_wave_finite(xsum);   // (the x tile's operand splits take the finite-only form)
+    for (int k = 0; k < WS_NS - 1; ++k) {
+        R.issue(k, src_main2(0, k));
+        issue_x(k, k < G1 ? k : -1);
     }
+    bool xfin = true;
+    if constexpr (!XS) xfin = wr_xtile<G1>(sx, a.X, a.x_ts, xr0, n, q, 0, a.kq, live);
     // b1: the head's bias, or per env with z0c (t = 0)
     const float* b1src = a.z0c ? a.z0c + ((size_t)(rb * 128 < a.rows ? rb * 128 / a.z0_G : 0) * 2 + head) * 512
                                : P.b1;
@@ -304,75 +170,11 @@ wide_step_kernel(const WideArgs a) {
     // (the asm use makes hipcc wait for g_old here, not at its first use among the counted DMA waits)
     asm volatile("" :: "v"(g_old));
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // prologue DMA + x visible
-
-    int k = 0;   // pipeline steps consumed
 #ifdef WS_STAMPS
-    // diagnostic: lane 0 of every wave of workgroups 0 (dynamics) and 4 (reward) records the shader clock before each
-    // step's wait and after its barrier (global stores: they only make the counted vmcnt waits stricter)
-    unsigned long long* st = a.stamps && (bid == 0 || bid == 4) && lane == 0 ? a.stamps + (bid ? 4096 : 0) + wave * 512
-                                                                          : nullptr;
+    // diagnostic: lane 0 of every wave of workgroups 0 (dynamics) and 4 (reward)
+    if (a.stamps && (bid == 0 || bid == 4) && lane == 0) R.st = a.stamps + (bid ? 4096 : 0) + wave * 512;
 #endif
-    // step k: this wave's DMA of steps k and k + 1 has landed (vmcnt), every wave's has and every wave is done reading
-    // step k - 1's slot (barrier); then refill that slot with step k + WS_NS - 1. (No lgkmcnt(0): the only LDS reads in
-    // flight here are this wave's read-ahead of step k's first fragments, which the refill of step k - 1's slot does
-    // not touch; their consumers wait with the compiler's own counts.)
-    auto sync = [&](const unsigned short* nsrc, int nxg = -1, bool tail_bias = false) __attribute__((always_inline)) -> const char* {
-#ifdef WS_STAMPS
-        if (st && k < 256) st[2 * k] = __builtin_amdgcn_s_memtime();
-#endif
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(VM) : "memory");
-#ifdef WS_STAMPS
-        if (st && k < 256) st[2 * k + 1] = __builtin_amdgcn_s_memtime();
-#endif
-        const char* sl = ring + (k % WS_NS) * SLOT + lane * 16;
-        issue(k + WS_NS - 1, nsrc, nxg);
-        if (tail_bias && wave < 4) {
-            // the epilogue's biases into the (now dead) x tile / x area, one 1 KiB LDS-DMA by each of waves 0-3 (an
-            // extra vector-memory op only makes the following counted waits stricter; landed and visible after the
-            // sync VM / 3 steps later, still inside this chunk): b2 (waves 0, 1), then w3 (reward) or b3 (dynamics:
-            // 256 floats per wave, as many as its 16 NB3 columns need; none with WS_OUTH)
-            const float* bsrc = wave < 2 ? P.b2 + 256 * wave : head == 1 ? P.w3v + 256 * (wave - 2) : a.b3 + 256 * (wave - 2);
-            const unsigned bdst = ring_lds + (unsigned)wsm_bias<G1, MODE>() + (unsigned)(wave < 2 || head == 1 ? wave : wave + 2) * 1024;
-#ifndef WS_DIAG_NODMA
-            if (wave < 2 || head == 1 || (!OUTH && (wave - 2) * 256 < 16 * NB3)) {
-                if constexpr (MODE == 0 && NB3 <= 8) ws_glds(bsrc, voff, bdst);
-                else w2_glds(bsrc, voff, bdst);
-            }
-#else
-            (void)bsrc; (void)bdst;
-#endif
-        }
-        ++k;
-        return sl;
-    };
-    // The fragment stream is read two fragments ahead of the products (software-pipelined: the LDS latency of a
-    // fragment runs under the previous two fragments' twelve MFMAs, so a wave keeps its SIMD busy even while its
-    // partner waits at the barrier). fc[0] holds the fragment about to be consumed, fc[1] the one after; frag(sl, i)
-    // hands out fc[0] and reads the step's fragment i + 2 (the step ends at fragment last), or fragment i + 1 - last
-    // (0 or 1) of the next step (landed: see VM).
-    uint4 fc[WS_AHEAD][3];
-    auto rd = [&](uint4 (&f)[3], const char* p) __attribute__((always_inline)) {
-        f[0] = *(const uint4*)p;
-        f[1] = *(const uint4*)(p + 1024);
-        f[2] = *(const uint4*)(p + 2048);
-    };
-#pragma unroll
-    for (int d = 0; d < WS_AHEAD; ++d) rd(fc[d], ring + d * WS_FRAG + lane * 16);   // (step 0 has >= 4 fragments)
-    auto frag = [&](const char* sl, int i, uint4& w0, uint4& w1, uint4& w2, int last = WS_NW - 1)
-        __attribute__((always_inline)) {
-        w0 = fc[0][0];
-        w1 = fc[0][1];
-        w2 = fc[0][2];
-#pragma unroll
-        for (int d = 0; d + 1 < WS_AHEAD; ++d)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fc[d][p] = fc[d + 1][p];
-        rd(fc[WS_AHEAD - 1], i + WS_AHEAD <= last ? sl + (i + WS_AHEAD) * WS_FRAG
-                                                  : ring + (k % WS_NS) * SLOT + (i + WS_AHEAD - 1 - last) * WS_FRAG + lane * 16);
-        // (keeps the reads above this fragment's products: hipcc's scheduler otherwise sinks them to just before
-        // their first use to save registers)
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    R.prime();
 
     floatx4 acc[32];
 #pragma unroll
@@ -380,6 +182,21 @@ wide_step_kernel(const WideArgs a) {
 
 #pragma unroll 1
     for (int sc = 0; sc < 4; ++sc) {
+        auto sync = [&](int j, bool tail_bias) __attribute__((always_inline)) {
+            return R.sync(src_next2(sc, j), [&](int kk) __attribute__((always_inline)) {
+                issue_x(kk, xg_next2(sc, j));
+                if (tail_bias && wave < 4) {
+                    // the epilogue's biases into the (now dead) x tile / x area, one 1 KiB LDS-DMA by each of waves 0-3
+                    // (landed and visible after the sync VM / 3 steps later, still inside this chunk): b2 (waves 0, 1),
+                    // then w3 (reward) or b3 (dynamics: 256 floats per wave, as many as its 16 NB3 columns need; none
+                    // with WS_OUTH)
+                    const float* bsrc = wave < 2 ? P.b2 + 256 * wave : head == 1 ? P.w3v + 256 * (wave - 2) : a.b3 + 256 * (wave - 2);
+                    const unsigned bdst = R.lds + (unsigned)wsm_bias<G1, MODE>() + (unsigned)(wave < 2 || head == 1 ? wave : wave + 2) * 1024;
+                    if (wave < 2 || head == 1 || (!OUTH && (wave - 2) * 256 < 16 * NB3))
+                        ws_dma<MODE == 0 && NB3 <= 8>(bsrc, R.voff, bdst);
+                }
+            });
+        };
         floatx4 a1[8];
 #pragma unroll
         for (int b = 0; b < 8; ++b) a1[b] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -388,10 +205,11 @@ wide_step_kernel(const WideArgs a) {
         constexpr int UG1 = XS ? 1 : G1;
 #pragma unroll UG1
         for (int g = 0; g < G1; ++g) {
-            const char* sl = sync(src_next2(sc, g), xg_next2(sc, g));
+            const char* sl = sync(g, false);
             p1f4 x0, x1;
             bool fin = xfin;
             if constexpr (XS) {
+                const p1f4 zero4 = {0.f, 0.f, 0.f, 0.f};
                 const p1f4* xs = (const p1f4*)(sl + WS_SLOT + wave * 2048);   // (sl: slot + lane * 16)
                 x0 = xs[0];
                 x1 = xs[64];
@@ -406,7 +224,7 @@ wide_step_kernel(const WideArgs a) {
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 uint4 w0, w1, w2;
-                frag(sl, b, w0, w1, w2);
+                R.frag(sl, b, w0, w1, w2);
                 ws_prod(a1[b], w0, w1, w2, xb);
             }
         }
@@ -436,29 +254,19 @@ wide_step_kernel(const WideArgs a) {
 #pragma unroll
                 for (int jq = 0; jq < 4; ++jq) {
                     const int j2 = G1 + 8 * co + 4 * s2 + jq;
-                    const char* sl = sync(src_next2(sc, j2), xg_next2(sc, j2), sc == 3 && co == 0 && s2 == 0 && jq == 0);
+                    const char* sl = sync(j2, sc == 3 && co == 0 && s2 == 0 && jq == 0);
 #pragma unroll
                     for (int jj = 0; jj < 8; ++jj) {
                         uint4 w0, w1, w2;
-                        frag(sl, jj, w0, w1, w2);
+                        R.frag(sl, jj, w0, w1, w2);
                         ws_prod(acc[8 * jq + jj], w0, w1, w2, xb);
                     }
                 }
             }
         }
     }
-    // h2 = ELU(acc + b2), formed where it is read (layer 3's split, the reward dot): the accumulators stay in place
-    // tile t of h2: features 16t + 4q + i
-    // (epilogue lane indices re-derived from an opaque copy of the lane offset: otherwise hipcc shares 4 jj + q with the
-    // prologue's x-tile quad indices 8 g + q (+ 4) and keeps them live -- spilled -- across the main loop)
-    int l16 = (int)voff;   // lane * 16, live through the loop (the DMA's lane offset)
-    asm volatile("" : "+v"(l16));
-    const int n_ep = (l16 >> 4) & 15, q_ep = (l16 >> 8) & 3;
-    auto h2t = [&](int t) __attribute__((always_inline)) -> float4 {
-        const float4 bv = *(const float4*)(sb2 + 16 * t + 4 * q);
-        return make_float4(elu_f(acc[t][0] + bv.x), elu_f(acc[t][1] + bv.y), elu_f(acc[t][2] + bv.z),
-                           elu_f(acc[t][3] + bv.w));
-    };
+    int n_ep, q_ep;
+    wr_lane_ep(R.voff, n_ep, q_ep);
 
     if (head == 0 && OUTH) {
         // ---- WS_OUTH: h2 where z' would go (X_{t+1}'s latent columns Ap .. Ap + 511), for the folded first layer next
@@ -467,7 +275,7 @@ wide_step_kernel(const WideArgs a) {
             const int xr = xr0 + n_ep;
             float* xo = a.Xo + (size_t)(xr >> 5) * a.x_ts + (xr & 31) * 4;
 #pragma unroll
-            for (int t = 0; t < 32; ++t) *(float4*)(xo + (size_t)(a.out_q0 + 4 * t + q_ep) * 128) = h2t(t);
+            for (int t = 0; t < 32; ++t) *(float4*)(xo + (size_t)(a.out_q0 + 4 * t + q_ep) * 128) = wr_h2t(acc, sb2, t, q);
         }
     } else if (head == 0 && NB3 > 8) {
         // ---- dynamics layer 3 in NP3 passes of 8 output tiles: pass p's tiles 8p .. 8p + 7 over the 16 k groups, one
@@ -479,13 +287,13 @@ wide_step_kernel(const WideArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) a3[j] = floatx4{0.f, 0.f, 0.f, 0.f};
             auto l3group = [&](int g) __attribute__((always_inline)) {
-                const float4 ha = h2t(2 * g), hb = h2t(2 * g + 1);
+                const float4 ha = wr_h2t(acc, sb2, 2 * g, q), hb = wr_h2t(acc, sb2, 2 * g + 1, q);
                 const WSX xb = ws_opnd(ha, hb, ws_wave_finite(ws_sum8(ha, hb)));
-                sl = sync(src_tail(16 * p + g + WS_NS - 1));
+                sl = R.sync(src_tail(16 * p + g + WS_NS - 1));
 #pragma unroll
                 for (int jj = 0; jj < 8; ++jj) {
                     uint4 w0, w1, w2;
-                    frag(sl, jj, w0, w1, w2);
+                    R.frag(sl, jj, w0, w1, w2);
                     ws_prod(a3[jj], w0, w1, w2, xb);
                 }
             };
@@ -521,14 +329,14 @@ wide_step_kernel(const WideArgs a) {
         WSX xb;
         const char* sl = nullptr;
         auto l3group = [&](int g) __attribute__((always_inline)) {
-            const float4 ha = h2t(2 * g), hb = h2t(2 * g + 1);
+            const float4 ha = wr_h2t(acc, sb2, 2 * g, q), hb = wr_h2t(acc, sb2, 2 * g + 1, q);
             xb = ws_opnd(ha, hb, ws_wave_finite(ws_sum8(ha, hb)));
 #pragma unroll
             for (int jj = 0; jj < NB; ++jj) {
                 const int f = g * NB + jj;
-                if (f % WS_NW == 0) sl = sync(src_tail(f / WS_NW + WS_NS - 1));
+                if (f % WS_NW == 0) sl = R.sync(src_tail(f / WS_NW + WS_NS - 1));
                 uint4 w0, w1, w2;
-                frag(sl, f % WS_NW, w0, w1, w2);
+                R.frag(sl, f % WS_NW, w0, w1, w2);
                 ws_prod(a3[jj], w0, w1, w2, xb);
             }
         };
@@ -560,7 +368,7 @@ wide_step_kernel(const WideArgs a) {
         float s = 0.f;
 #pragma unroll
         for (int t = 0; t < 32; ++t) {
-            const float4 v = h2t(t);
+            const float4 v = wr_h2t(acc, sb2, t, q);
             const float4 wv = *(const float4*)(sw3 + 16 * t + 4 * q_ep);
             s += (v.x * wv.x + v.y * wv.y) + (v.z * wv.z + v.w * wv.w);
         }

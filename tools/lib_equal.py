@@ -1,6 +1,6 @@
 """Do two builds of the library compute the same? A fixed, seeded list of small eager calls through every planning
-entry point (TOLD on every kernel path, iCEM, the DSSM planners), once per library in a fresh process; every output
-is compared bitwise. Needs a GPU.
+entry point (TOLD on every kernel path, every instance family of the wide kernels, iCEM, the DSSM planners), once
+per library in a fresh process; every output is compared bitwise. Needs a GPU.
     python -m tdmpc_amd.build --variant parent        # in a checkout of the other commit; copy the .so next to ours
     python tools/lib_equal.py tdmpc_amd/libtdmpc_hip_parent.so tdmpc_amd/libtdmpc_hip.so [OUT_DIR]
 """
@@ -15,6 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 TOLD_PATHS = ["layered", "chain16", "chain32", "split", "chain_x6", "split_x6", "chain", "persist", "wide"]
 SMALL = dict(num_samples=64, num_elites=16, iterations=3, horizon=5)
+WIDE = dict(num_samples=128, num_elites=16, iterations=3, horizon=5)
 STEP, H = 10**6, 5   # past every schedule: the full horizon, the final mixture
 
 
@@ -57,6 +58,33 @@ def child(out):
                 tr = {}
                 a, _ = agent._plan_envs(obs[:B], False, STEP, [t0] * B, trace=tr)
                 put(f"{tag}/plan{B}{int(t0)}", a, pl.metrics[:B], pl.prev_mean_view(H, B), *tr.values())
+    # the wide kernels, every instance family: N = 128 and P = 64 at STEP (N + P = T, multiples of 16; N a multiple of
+    # 128: the t = 0 per-env-bias instances), path="wide" so that two envs reach them; max_batch 32 so that the pack
+    # builds helper.q's statistics block. The profiler's kernel name proves that they ran.
+    import ctypes as C
+    from tdmpc_amd import _lib
+    L = _lib.lib()
+
+    def kernel_of(agent, obs, prof_cfg):   # as tests/test_gpu_configs.py::_kernel_of: 4 the step launches, 6 helper.q
+        _lib.check(L.tdmpc_profile_begin(prof_cfg, -1, 0, 0, 256), "profile_begin")
+        agent._plan_envs(obs, False, STEP, [False] * len(obs))
+        n, ms, fl = C.c_int32(), C.c_double(), C.c_double()
+        _lib.check(L.tdmpc_profile_end(C.byref(n), C.byref(ms), C.byref(fl)), "profile_end")
+        return L.tdmpc_profile_kernel().decode() if n.value > 0 else ""
+    for name, task, ov in (("humanoid", "humanoid", {}), ("dog", "dog", {}), ("cheetah", "cheetah", {}),
+                           ("quadruped", "quadruped", {}), ("humanoid-l512", "humanoid", dict(latent_dim=512))):
+        cfg = make_cfg(task, **dict(WIDE, **ov))
+        sd, (obs,) = synthetic_state_dict(cfg, 7), rand(9, (2, cfg.obs_shape[0]))
+        agent = made(TDMPC(cfg, max_batch=32, rng="fused", graph=False, path="wide"), sd)
+        pl = agent.planner
+        for B, t0 in ((1, True), (1, False), (2, True)):   # cold, warm, a batch
+            torch.manual_seed(50 + B)
+            tr = {}
+            a, _ = agent._plan_envs(obs[:B], False, STEP, [t0] * B, trace=tr)
+            put(f"wide/{name}/plan{B}{int(t0)}", a, pl.metrics[:B], pl.prev_mean_view(H, B), *tr.values())
+        step_k, q_k = kernel_of(agent, obs, 4), kernel_of(agent, obs, 6)
+        assert step_k.startswith("wide_step_kernel<17, 32" if ov else "wide_step_kernel"), (name, step_k)
+        assert ov or q_k.startswith("wide_heads_kernel"), (name, q_k)   # (latent 512: no wide heads instance)
     cfg = make_cfg("humanoid", **dict(SMALL, num_elites=8))
     sd, (obs,) = synthetic_state_dict(cfg, 31, enc_norm=True), rand(4, (3, cfg.obs_shape[0]))
     for path in ("auto", "layered", "split", "chain_x6"):
