@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch  # (also loads torch's libamdhip64 first, so that the library shares its HIP runtime)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TDMPC_LIB_PATH") or os.path.join(HERE, "libtdmpc_hip.so")   # override: A/B of builds
 
@@ -163,7 +165,6 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m tdmpc_amd.build` "
                            "(hipcc --offload-arch=gfx950). The planner has no CPU fallback.")
-    import torch  # noqa: F401  -- load torch's libamdhip64 first so both share one HIP runtime
     L = C.CDLL(LIB_PATH)
     vp, i32, sz = C.c_void_p, C.c_int32, C.c_size_t
     L.tdmpc_abi_version.restype = C.c_int
@@ -243,6 +244,16 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = lib().tdmpc_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed with code {rc}: {msg}")
+
+
+def call(name: str, *args):
+    """Call the entry point `name` and raise on a nonzero return code. A tensor passes as its data_ptr(), a ctypes
+    structure by reference, None as the null pointer (0) and everything else as it is: `lib()` has set every entry
+    point's argtypes, which convert plain ints."""
+    rc = getattr(_LIB or lib(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else
+                                       C.byref(a) if isinstance(a, C.Structure) else a for a in args])
+    if rc:
+        check(rc, name)
 
 
 def dims_from_cfg(cfg, max_batch: int = 1, max_horizon=None, max_iterations=None, enc_norm: bool = False) -> Dims:

@@ -13,9 +13,7 @@ plan horizon; the envs of one call must agree on the horizon (the kernels take o
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import deque
-from copy import deepcopy
 
 import numpy as np
 import torch
@@ -23,7 +21,7 @@ import torch
 from . import _lib
 from .config import linear_schedule
 from .dssm import DSSM, check_dssm_cfg, float_tensors
-from .tdmpc import Checkpointed, HipPlanner
+from .tdmpc import Agent, HipPlanner, pack_weights
 
 
 def _schedule_ends(schdl):
@@ -58,128 +56,52 @@ class DrnnPlanner(HipPlanner):
         self.ddims = _lib.drnn_dims_from_cfg(cfg, max_batch=max_batch, num_pi=pmax)
         return self.ddims.base
 
-    def _query_sizes(self):
-        sz = _lib.Sizes()
-        _lib.check(self.L.tdmpc_drnn_sizes_for(C.byref(self.ddims), C.byref(sz)), "tdmpc_drnn_sizes_for")
-        return sz
+    entry, sizes_abi = "tdmpc_drnn_plan", "tdmpc_drnn_sizes_for"
+
+    def abi_dims(self):
+        return self.ddims
 
     def set_num_pi(self, P: int):
         self.ddims.base.num_pi = int(P)
         self.P, self.T = int(P), self.N + int(P)
         self._ref_adv = self._ref_adv_by_p.setdefault(int(P), {})
 
-    # ------------------------------------------------------------------ weights
     def pack(self, model: DSSM):
-        """Pack the DSSM's floating-point tensors (state_dict order) when any of them changed."""
-        if self._packed_key is not None and self._packed_model is model:
-            key = tuple((p.data_ptr(), p._version) for p in self._packed_params)
-            if key == self._packed_key:
-                return
-        params = float_tensors(model.state_dict())
-        if self._packed_model is not None and self._packed_model is not model:
-            self.L.tdmpc_pack_forget(C.c_void_p(self.packed.data_ptr()))
-        self._packed_model, self._packed_params = model, params
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        n = self.L.tdmpc_drnn_num_param_tensors(C.byref(self.ddims))
-        if n != len(params):
-            raise ValueError(f"DSSM has {len(params)} float tensors, the packer expects {n}")
-        # device fp32 copies kept per planner, so the pointer set (the key of the library's job-table record) is the
-        # same from one repack to the next
-        stage = getattr(self, "_pack_stage", None)
-        if stage is None:
-            stage = self._pack_stage = [torch.empty(p.shape, dtype=torch.float32, device=self.device) for p in params]
-        for s, p in zip(stage, params):
-            s.copy_(p.detach())
-        arr = (C.c_void_p * n)(*[s.data_ptr() for s in stage])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self.L.tdmpc_drnn_pack_weights(C.byref(self.ddims), arr, n, C.c_void_p(self.packed.data_ptr()),
-                                                  self.packed.numel() * 4, C.c_void_p(stream)),
-                   "tdmpc_drnn_pack_weights")
-        self._packed_key = key
+        """Pack the DSSM's floating-point tensors (state_dict order) when any of them changed, always through device
+        fp32 copies kept per planner."""
+        pack_weights(self, model, lambda m: float_tensors(m.state_dict()), "tdmpc_drnn_", self.ddims, True)
 
     # ------------------------------------------------------------------ calls
-    def _ws(self):
-        return C.c_void_p(self.workspace.data_ptr()), self.workspace.numel() * 4
-
-    def launch(self, prm, obs_is_u8: bool = False, trace: dict | None = None):
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        B, H, I, K = prm.batch, prm.horizon, prm.iterations, self.dims.num_elites
-        outs = {}
-        if trace is not None:
-            outs = dict(elite=torch.zeros(B, H, K, self.A, device=self.device),
-                        score=torch.zeros(B, K, device=self.device),
-                        value=torch.zeros(B, I, self.T, device=self.device),
-                        mean=torch.zeros(B, I, H, self.A, device=self.device),
-                        std=torch.zeros(B, I, H, self.A, device=self.device))
-            trace.update(outs)
-        g = outs.get
-        vp = C.c_void_p
-        ws, wsb = self._ws()
-        rc = self.L.tdmpc_drnn_plan(C.byref(self.ddims), C.byref(prm), vp(self.packed.data_ptr()),
-                                    vp(self.obs_buf.data_ptr()), vp(self.hidden_buf.data_ptr()),
-                                    vp(self.noise_flat.data_ptr()), vp(self.u.data_ptr()),
-                                    vp(self.prev_mean_flat.data_ptr()), vp(self.action.data_ptr()),
-                                    vp(self.metrics.data_ptr()), vp(self.z_in.data_ptr()),
-                                    vp(_lib.ptr(g("elite"))), vp(_lib.ptr(g("score"))), vp(_lib.ptr(g("value"))),
-                                    vp(_lib.ptr(g("mean"))), vp(_lib.ptr(g("std"))), ws, wsb, vp(stream))
-        _lib.check(rc, "tdmpc_drnn_plan")
+    def _plan_io(self, obs_is_u8):
+        return self.hidden_buf, (self.z_in,)
 
     def next(self, z, a, h, h_out=None):
         """DSSM.next for rows of (z [R, L], a [R, A], h [R, Hd]) -> (z' [R, L], h' [R, Hd], reward [R])."""
         dev = self.device
-        z = z.to(dev, torch.float32).contiguous()
-        a = a.to(dev, torch.float32).contiguous()
-        h = h.to(dev, torch.float32).contiguous()
+        z, a, h = (t.to(dev, torch.float32).contiguous() for t in (z, a, h))
         R = z.shape[0]
         zo = torch.empty(R, self.dims.latent_dim, device=dev)
         ho = torch.empty(R, self.hidden_dim, device=dev) if h_out is None else h_out
         ro = torch.empty(R, device=dev)
-        vp = C.c_void_p
-        ws, wsb = self._ws()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.L.tdmpc_drnn_next(C.byref(self.ddims), vp(self.packed.data_ptr()), vp(z.data_ptr()), vp(a.data_ptr()),
-                                    vp(h.data_ptr()), R, vp(zo.data_ptr()), vp(ho.data_ptr()), vp(ro.data_ptr()),
-                                    ws, wsb, vp(stream))
-        _lib.check(rc, "tdmpc_drnn_next")
+        _lib.call("tdmpc_drnn_next", self.ddims, self.packed, z, a, h, R, zo, ho, ro, *self._ws(), self._stream())
         return zo, ho, ro
 
     def estimate_value(self, z0, h0, actions, eps_term, H: int):
         """TdMpcSimDssm.estimate_value for B envs: z0 [B, L], h0 [B, Hd], actions [B, H, T, A], eps_term [B, T, A]
         -> (value [B, T], reward at t = H-1 [B, T])."""
-        B = z0.shape[0]
-        prm = self.params(H, 1, B, False, True, 0.05)
-        dev = self.device
-        z0, h0, actions, eps_term = (t.to(dev, torch.float32).contiguous() for t in (z0, h0, actions, eps_term))
-        value = torch.empty(B, self.T, device=dev)
-        rlast = torch.empty(B, self.T, device=dev)
-        vp = C.c_void_p
-        ws, wsb = self._ws()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.L.tdmpc_drnn_estimate_value(C.byref(self.ddims), C.byref(prm), vp(self.packed.data_ptr()),
-                                              vp(z0.data_ptr()), vp(h0.data_ptr()), vp(actions.data_ptr()),
-                                              vp(eps_term.data_ptr()), self.T, vp(value.data_ptr()),
-                                              vp(rlast.data_ptr()), ws, wsb, vp(stream))
-        _lib.check(rc, "tdmpc_drnn_estimate_value")
+        B, dev = z0.shape[0], self.device
+        value, rlast = torch.empty(B, self.T, device=dev), torch.empty(B, self.T, device=dev)
+        self._call("tdmpc_drnn_estimate_value", H, 0.05, (z0, h0, actions, eps_term), self.T, value, rlast)
         return value, rlast
 
     def pi_rollout(self, z0, h0, eps_pi, H: int):
         """The policy pre-rollout for B envs: z0 [B, L], h0 [B, Hd], eps_pi [B, H, P, A] -> pi_actions [B, H, P, A]."""
-        B = z0.shape[0]
-        prm = self.params(H, 1, B, False, True, 0.05)
-        dev = self.device
-        z0, h0, eps_pi = (t.to(dev, torch.float32).contiguous() for t in (z0, h0, eps_pi))
-        out = torch.empty(B, H, self.P, self.A, device=dev)
-        vp = C.c_void_p
-        ws, wsb = self._ws()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.L.tdmpc_drnn_pi_rollout(C.byref(self.ddims), C.byref(prm), vp(self.packed.data_ptr()),
-                                          vp(z0.data_ptr()), vp(h0.data_ptr()), vp(eps_pi.data_ptr()),
-                                          vp(out.data_ptr()), ws, wsb, vp(stream))
-        _lib.check(rc, "tdmpc_drnn_pi_rollout")
+        out = torch.empty(z0.shape[0], H, self.P, self.A, device=self.device)
+        self._call("tdmpc_drnn_pi_rollout", H, 0.05, (z0, h0, eps_pi), out)
         return out
 
 
-class TdMpcDrnn(Checkpointed):
+class TdMpcDrnn(Agent):
     """Drop-in for the reference `TdMpcSimDssm` planning interface (tdmpc_similarity_drnn.py:87-267)."""
 
     MAX_GRAPHS = 8   # captured plans kept per agent (one per (horizon, iterations, batch, num_pi, eval_mode))
@@ -187,20 +109,9 @@ class TdMpcDrnn(Checkpointed):
 
     def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", graph: bool = True):
         check_dssm_cfg(cfg)
-        self.cfg = cfg
-        self.device = torch.device(cfg.device)
-        self.std = linear_schedule(cfg.std_schedule, 0)                              # :93
+        self._init_agent(cfg, DSSM, rng, graph)                                      # :93, :95
         self.mixture_coef = linear_schedule(cfg.regularization_schedule, 0)          # :94
-        self.model = DSSM(cfg).to(self.device)                                       # :95
-        self.model_target = deepcopy(self.model)
-        self.model.eval()
-        self.model_target.eval()
-        if rng not in ("reference", "fused"):
-            raise ValueError(rng)
-        self.rng = rng
-        self.graph = graph
         self.planner = DrnnPlanner(cfg, max_batch=max_batch, device=self.device)
-        self.max_batch = max_batch
         wl = int(getattr(cfg, "warmup_len", 0))
         self._memories = [deque(maxlen=wl) for _ in range(max_batch)]               # :109, one per env
         self._plan_H = np.ones(max_batch, dtype=np.int64)                            # :108, one per env
@@ -226,10 +137,8 @@ class TdMpcDrnn(Checkpointed):
     def plan(self, obs, hidden, eval_mode=False, step=None, t0=True, noise=None, trace=None):
         """:184-267. hidden: the caller's GRU state [1, Hd] (or [Hd]); the memory of the last warmup_len
         (latent, action) pairs is replayed from it before planning. Returns (action [A], the three metrics)."""
-        cfg = self.cfg
-        if step < cfg.seed_steps and not eval_mode:
-            return (torch.empty(cfg.action_dim, dtype=torch.float32, device=self.device).uniform_(-1, 1),
-                    dict(self.METRICS0))
+        if self._seed_step(step, eval_mode):
+            return self._seed_return()
         hidden = torch.as_tensor(hidden, dtype=torch.float32).reshape(1, -1)
         a, m = self._plan_envs(np.asarray(obs)[None], hidden, eval_mode, step, [t0],
                                None if noise is None else [noise], trace)
@@ -239,17 +148,12 @@ class TdMpcDrnn(Checkpointed):
     def plan_batch(self, obs, hidden, eval_mode=False, step=None, t0=True, noise=None, trace=None):
         """B environments at once: obs [B, obs_dim], hidden [B, Hd], t0 a bool or a per-env sequence. Equivalent to B
         reference agents sharing weights, the draws taken env by env in reference order."""
-        cfg = self.cfg
         obs = obs if torch.is_tensor(obs) else np.asarray(obs)
         B = obs.shape[0]
-        if step < cfg.seed_steps and not eval_mode:
-            a = torch.empty(B, cfg.action_dim, dtype=torch.float32, device=self.device)
-            for e in range(B):
-                a[e].uniform_(-1, 1)
-            return a, [dict(self.METRICS0) for _ in range(B)]
-        t0s = [t0] * B if isinstance(t0, (bool, int, np.bool_)) else list(t0)
+        if self._seed_step(step, eval_mode):
+            return self._seed_return(B)
         hidden = torch.as_tensor(hidden, dtype=torch.float32).reshape(B, -1)
-        return self._plan_envs(obs, hidden, eval_mode, step, t0s, noise, trace)
+        return self._plan_envs(obs, hidden, eval_mode, step, self._per_env(t0, B), noise, trace)
 
     # ------------------------------------------------------------------ internals
     def _replay_memory(self, hidden, B):
@@ -271,12 +175,9 @@ class TdMpcDrnn(Checkpointed):
     def _plan_envs(self, obs, hidden, eval_mode, step, t0s, noise=None, trace=None):
         cfg, pl = self.cfg, self.planner
         B = obs.shape[0]
-        if B > pl.max_batch:
-            raise ValueError(f"batch {B} > max_batch {pl.max_batch}")
-        if hidden.shape != (B, pl.hidden_dim):
-            raise ValueError(f"hidden must be [{B}, {pl.hidden_dim}], not {tuple(hidden.shape)}")
+        self._check_call(B, hidden)
         # :193-197: the schedule moves an env's plan horizon only at its episode start
-        horizon = int(min(cfg.horizon, linear_schedule(cfg.horizon_schedule, step)))
+        horizon = self.horizon(step)
         for e in range(B):
             if horizon != self._plan_H[e] and t0s[e]:
                 self._plan_H[e] = horizon
@@ -289,36 +190,12 @@ class TdMpcDrnn(Checkpointed):
             raise ValueError(f"{P} policy trajectories exceed the planner's buffers ({pl.pmax})")
         pl.set_num_pi(P)
         I = int(cfg.iterations)
-        warm = []
-        for e in range(B):
-            w = (not t0s[e]) and bool(self._has_prev[e])
-            if w and self._prev_H[e] != H:
-                raise RuntimeError(f"shape mismatch: prev_mean horizon {self._prev_H[e]} vs {H}")
-            warm.append(w)
+        warm = self._warm(t0s, H)
         pl.pack(self.model)
         pl.hidden_buf[:B].copy_(self._replay_memory(hidden, B))
-        host = not torch.is_tensor(obs) or obs.device.type == "cpu"
-        if pl._h2d_done is not None:
-            pl._h2d_done.synchronize()
-        if host:
-            pl._h_obs[:B] = np.asarray(obs, dtype=np.float32).reshape(B, -1)
-        else:
-            pl.obs_buf[:B].copy_(obs.to(self.device, torch.float32).view(B, -1))
-        pl.set_call_state(self.std, warm)
-        if noise is not None:
-            for e, nb in enumerate(noise):
-                pl.load_noise(e, H, I, nb.eps_pi, nb.eps_cem, nb.eps_term, nb.eps_act)
-                pl._h_u[e] = float(nb.u)
-        elif self.rng == "reference":
-            for e in range(B):
-                pl._h_u[e] = np.random.random_sample()   # np.random.choice's uniform (:254)
-        one_launch = noise is None and self.rng == "reference"
-        if one_launch:
-            pl.stage_reference_state(B, H, I, eval_mode)
-        lo = 0 if host else pl._u_off
-        pl._stage_d[lo:].copy_(pl._stage_h[lo:], non_blocking=True)
-        if pl._h2d_done is not None:
-            pl._h2d_done.record()
+        reference = self.rng == "reference"
+        one_launch = noise is None and reference
+        pl.stage_call(obs, B, H, I, eval_mode, self.std, warm, noise, reference, one_launch)
 
         def device_work():
             if noise is None:
@@ -329,33 +206,14 @@ class TdMpcDrnn(Checkpointed):
                     pl.u[:B].uniform_()
             pl.launch(pl.device_state_params(pl.params(H, I, B, warm[0], eval_mode, self.std)), False, trace)
 
-        if self.graph and noise is None and trace is None:
-            key = (H, I, B, P, bool(eval_mode), self.rng)
-            g = pl._graphs.get(key)
-            if g is None:
-                # a ramping regularization_schedule gives a new P (a new graph) per step: keep the latest few
-                while len(pl._graphs) >= self.MAX_GRAPHS:
-                    pl._graphs.pop(next(iter(pl._graphs)))
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    device_work()
-                pl._graphs[key] = g
-            g.replay()
-        else:
-            device_work()
+        # a ramping regularization_schedule gives a new P (a new graph) per step: keep the latest few
+        captured = self.graph and noise is None and trace is None
+        pl.run(device_work, (H, I, B, P, bool(eval_mode), self.rng) if captured else None, self.MAX_GRAPHS)
         self._has_prev[:B] = True
         self._prev_H[:B] = H
-        if pl._h2d_done is not None:   # status + metrics: one copy into pinned memory, as TDMPC does
-            pl._pin_ms[:4 + 2 * B].copy_(pl._ms_dev[:4 + 2 * B], non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
-            ms = pl._pin_ms
-        else:
-            ms = pl._ms_dev[:4 + 2 * B].cpu()
-        pl.raise_status(int(ms[:1].view(torch.int32)[0]))
-        m = ms[4:4 + 2 * B].view(B, 2).double().tolist()
+        m = self._metrics(B)
         actions = pl.action[:B].clone()
         z_in = pl.z_in[:B].clone()
         for e in range(B):   # :261: the latent and the (noised) action, for the next call's replay
             self._memories[e].append((z_in[e], actions[e]))
-        return actions, [{"intrinsic_reward_mean": 0.0, "external_reward_mean": float(r), "current_std": float(s)}
-                         for r, s in m]
+        return actions, m

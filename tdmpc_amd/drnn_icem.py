@@ -21,9 +21,6 @@ with one normal_, the spectrum normals with another and turns them into every co
 """
 from __future__ import annotations
 
-import ctypes as C
-from copy import deepcopy
-
 import numpy as np
 import torch
 
@@ -32,8 +29,9 @@ from .colored_noise import irfft_matrices, powerlaw_psd_gaussian, spectrum_rows
 from .config import linear_schedule
 from .drnn import DrnnPlanner
 from .dssm import DSSM, check_dssm_cfg
-from .icem import icem_counts, icem_layout, icem_load, icem_params, icem_trace_values
-from .tdmpc import Checkpointed
+from .icem import (IcemBuffers, icem_counts, icem_draw_reference, icem_layout, icem_load, icem_params,
+                   icem_trace_values)
+from .tdmpc import Agent
 
 
 def colored_noise_params(L, A, batch, env_stride, normals_env, jobs, betas):
@@ -64,64 +62,43 @@ def colored_noise_params(L, A, batch, env_stride, normals_env, jobs, betas):
 
 
 def colored_noise(L_lib, params, normals, noise, stream=None):
-    """One tdmpc_drnn_colored_noise launch: normals (flat float32 device tensor) -> blocks of `noise` (flat)."""
+    """One tdmpc_drnn_colored_noise launch: normals (flat float32 device tensor) -> blocks of `noise` (flat). L_lib:
+    the loaded library (`_lib.lib()`), which `_lib.call` reaches on its own; kept in the signature for its callers."""
     if stream is None:
         stream = torch.cuda.current_stream(noise.device).cuda_stream
-    rc = L_lib.tdmpc_drnn_colored_noise(C.byref(params), C.c_void_p(normals.data_ptr()), normals.numel(),
-                                        C.c_void_p(noise.data_ptr()), noise.numel(), C.c_void_p(stream))
-    _lib.check(rc, "tdmpc_drnn_colored_noise")
+    _lib.call("tdmpc_drnn_colored_noise", params, normals, normals.numel(), noise, noise.numel(), stream)
 
 
-class IcemDrnnPlanner(DrnnPlanner):
+class IcemDrnnPlanner(IcemBuffers, DrnnPlanner):
     """DrnnPlanner with the iCEM workspace (N + K + num_pi rows per env) and noise stream bound; `ddims.base.num_pi`
     stays at the schedule's largest value (the calls pass their own counts in tdmpc_icem_params)."""
 
-    def _query_sizes(self):
-        sz = _lib.Sizes()
-        _lib.check(self.L.tdmpc_drnn_icem_sizes_for(C.byref(self.ddims), C.byref(sz)), "tdmpc_drnn_icem_sizes_for")
-        return sz
+    entry, sizes_abi = "tdmpc_drnn_plan_icem", "tdmpc_drnn_icem_sizes_for"
 
 
-class TdIcemDrnn(Checkpointed):
+class TdIcemDrnn(Agent):
     """Drop-in for the reference `TdICemSimDssm` planning interface (tdmpc_icem_similarity_drnn.py:81-272)."""
 
     MAX_GRAPHS = 8   # captured plans kept per agent
-    METRICS0 = {"external_reward_mean": 0.0, "current_std": 0.0}
+    RNGS = ("reference", "device")
+    HIDDEN = True
 
     def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", graph: bool = True):
         check_dssm_cfg(cfg)
-        if rng not in ("reference", "device"):
-            raise ValueError("rng: 'reference' or 'device'")
         if not 1 <= int(cfg.iterations) <= 16:
             raise ValueError("iCEM: 1..16 iterations")
-        self.cfg = cfg
-        self.rng = rng
-        self.graph = graph
-        self.device = torch.device(cfg.device)
-        self.std = linear_schedule(cfg.std_schedule, 0)                       # :87
+        self._init_agent(cfg, DSSM, rng, graph)                               # :87, :89
         self.mixture_coef = linear_schedule(cfg.regularization_schedule, 0)   # :88
-        self.model = DSSM(cfg).to(self.device)                                # :89
-        self.model_target = deepcopy(self.model)
-        self.model.eval()
-        self.model_target.eval()
         self.plan_horizon = 1                                                 # :98
-        self.max_batch = max_batch
         pl = self.planner = IcemDrnnPlanner(cfg, max_batch=max_batch, device=self.device)
         dev = self.device
         A, K, N, H = cfg.action_dim, cfg.num_elites, cfg.num_samples, cfg.horizon
-        self.P_max = pl.pmax
-        self.E_max = int(cfg.fraction_elites_reused * K)
+        self.P_max, self.E_max, self.elites = pl.pmax, pl.E_max, pl.elites
         self.Tw = N + K + self.P_max
-        self.elites = torch.zeros(max_batch, H, K, A, dtype=torch.float32, device=dev)
         self.hidden_out = torch.zeros(max_batch, pl.hidden_dim, dtype=torch.float32, device=dev)
-        # spectrum normals of one call (rng 'device') and the host-drawn coloured blocks (rng 'reference'), per env
-        self._col_max = cfg.iterations * H * N * A + H * self.E_max * A
-        F_max = H // 2 + 1
-        self._normals = torch.zeros(max_batch * 2 * F_max * (cfg.iterations * N + self.E_max) * A,
+        # spectrum normals of one call (rng 'device')
+        self._normals = torch.zeros(max_batch * 2 * (H // 2 + 1) * (cfg.iterations * N + self.E_max) * A,
                                     dtype=torch.float32, device=dev)
-        self._stage = torch.empty(max_batch * self._col_max, dtype=torch.float32, device=dev)
-        self._pinned = torch.empty(max_batch * self._col_max, dtype=torch.float32, pin_memory=dev.type == "cuda")
-        self._h2d_done = None
         self._noise_params = {}
         self._has_prev = False
         self._has_elites = False
@@ -183,45 +160,25 @@ class TdIcemDrnn(Checkpointed):
         pl.u[:B].uniform_()
 
     def _draw_reference(self, e, H, cts, off, reuse, eval_mode):
-        """Env e's stream in the reference's draw order on torch's (device) and numpy's global generators. The two
-        generators are independent, so numpy's draws (the coloured blocks, then the pick's uniform) run first on the
-        host and travel in one pinned copy; torch's follow in order."""
-        cfg, pl = self.cfg, self.planner
-        A, S, dev = cfg.action_dim, off["total"], self.device
-        buf = pl.noise_flat[e * S:(e + 1) * S]
-        blocks = self._colored_blocks(H, cts, off, reuse)
+        """Env e's stream in the reference's order (icem_draw_reference): every sample block and the reuse tail are
+        numpy's coloured sequences when noise_beta > 0, torch's white draws otherwise."""
+        cfg, A, dev = self.cfg, self.cfg.action_dim, self.device
         colored = cfg.noise_beta > 0
-        if colored:
-            host = [powerlaw_psd_gaussian(cfg.noise_beta, (n, A, H)).astype(np.float32).transpose(2, 0, 1).reshape(-1)
-                    for n, _ in blocks]
-            host = np.concatenate(host) if host else np.zeros(0, np.float32)
-        u = float(np.random.random_sample())
-        if colored and host.size:
-            if self._h2d_done is not None:
-                self._h2d_done.synchronize()   # the previous copy has left the pinned buffer
-            lo = e * self._col_max
-            stage = self._pinned[lo:lo + host.size]
-            stage.numpy()[:] = host
-            dst = self._stage[lo:lo + host.size]
-            dst.copy_(stage, non_blocking=True)
-            self._h2d_done = torch.cuda.Event()
-            self._h2d_done.record()
-            o = 0
-            for n, so in blocks:
-                buf[so:so + H * n * A].copy_(dst[o:o + H * n * A])
-                o += H * n * A
-        P0 = cts[0][1]
-        for t in range(H):
-            buf[t * P0 * A:(t + 1) * P0 * A].view(P0, A).normal_()
-        for i, (n, p, ne) in enumerate(cts):
+
+        def draw_host():
             if not colored:
-                buf[off["samp"][i]:off["samp"][i] + H * n * A].copy_(torch.randn(H, n, A, device=dev).view(-1))
-                if i == 0 and reuse:
-                    buf[off["reuse"]:off["reuse"] + H * ne * A].copy_(torch.randn(H, ne, A, device=dev).view(-1))
-            buf[off["term"][i]:off["term"][i] + (n + ne + p) * A].view(n + ne + p, A).normal_()
-        if not eval_mode:
-            buf[off["act"]:off["act"] + A].copy_(torch.randn(A, device=dev))
-        return u
+                return None, None
+            ns = [n for n, _ in self._colored_blocks(H, cts, off, reuse)]
+            host = [powerlaw_psd_gaussian(cfg.noise_beta, (n, A, H)).astype(np.float32).transpose(2, 0, 1).reshape(-1)
+                    for n in ns]
+            return ns, np.concatenate(host) if host else np.zeros(0, np.float32)
+
+        def compose(buf, i, n, ne, cols):
+            for cnt, o in [(n, off["samp"][i])] + ([(ne, off["reuse"])] if i == 0 and reuse else []):
+                blk = next(cols) if colored else torch.randn(H, cnt, A, device=dev)
+                buf[o:o + H * cnt * A].copy_(blk.view(-1))
+
+        return icem_draw_reference(self.planner, e, H, cts, off, eval_mode, draw_host, compose, False)
 
     def _load(self, e, H, cts, off, reuse, nz):
         S = off["total"]
@@ -231,10 +188,8 @@ class TdIcemDrnn(Checkpointed):
     @torch.no_grad()
     def plan(self, obs, hidden, eval_mode=False, step=None, t0=True, noise=None, trace=None):
         """:169-272 -> (action [A], hidden [1, Hd], metrics); at seed steps (uniform action, None, zero metrics)."""
-        cfg = self.cfg
-        if step < cfg.seed_steps and not eval_mode:
-            return (torch.empty(cfg.action_dim, dtype=torch.float32, device=self.device).uniform_(-1, 1), None,
-                    dict(self.METRICS0))
+        if self._seed_step(step, eval_mode):
+            return self._seed_return()
         obs = torch.as_tensor(np.asarray(obs), dtype=torch.float32).view(1, -1)
         hidden = torch.as_tensor(hidden, dtype=torch.float32).reshape(1, -1)
         a, h, m = self._plan_envs(obs, hidden, eval_mode, step, t0, None if noise is None else [noise], trace)
@@ -244,41 +199,19 @@ class TdIcemDrnn(Checkpointed):
     def plan_batch(self, obs, hidden, eval_mode=False, step=None, t0=True, noise=None, trace=None):
         """B environments at the same step / t0: obs [B, obs_dim], hidden [B, Hd] -> (actions [B, A], hidden [B, Hd],
         metrics list). Equivalent to B reference agents sharing weights, the draws taken env by env."""
-        cfg = self.cfg
         obs = torch.as_tensor(np.asarray(obs) if not torch.is_tensor(obs) else obs, dtype=torch.float32)
         B = obs.shape[0]
-        if step < cfg.seed_steps and not eval_mode:
-            a = torch.empty(B, cfg.action_dim, dtype=torch.float32, device=self.device)
-            for e in range(B):
-                a[e].uniform_(-1, 1)
-            return a, None, [dict(self.METRICS0) for _ in range(B)]
+        if self._seed_step(step, eval_mode):
+            return self._seed_return(B)
         hidden = torch.as_tensor(hidden, dtype=torch.float32).reshape(B, -1)
         return self._plan_envs(obs.view(B, -1), hidden, eval_mode, step, bool(t0), noise, trace)
-
-    def _launch(self, p, outs):
-        pl = self.planner
-        vp = C.c_void_p
-        g = outs.get
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = pl.L.tdmpc_drnn_plan_icem(
-            C.byref(pl.ddims), C.byref(p), vp(pl.packed.data_ptr()), vp(pl.obs_buf.data_ptr()),
-            vp(pl.hidden_buf.data_ptr()), vp(pl.noise_flat.data_ptr()), vp(pl.u.data_ptr()),
-            vp(pl.prev_mean_flat.data_ptr()), vp(self.elites.data_ptr()), vp(pl.action.data_ptr()),
-            vp(pl.metrics.data_ptr()), vp(self.hidden_out.data_ptr()), vp(pl.z_in.data_ptr()),
-            vp(_lib.ptr(g("value"))), vp(_lib.ptr(g("mean"))), vp(_lib.ptr(g("std"))),
-            vp(pl.workspace.data_ptr()), pl.workspace.numel() * 4, vp(stream))
-        _lib.check(rc, "tdmpc_drnn_plan_icem")
 
     def _plan_envs(self, obs, hidden, eval_mode, step, t0, noise, trace):
         cfg, pl = self.cfg, self.planner
         B = obs.shape[0]
-        if B > pl.max_batch:
-            raise ValueError(f"batch {B} > max_batch {pl.max_batch}")
-        if hidden.shape != (B, pl.hidden_dim):
-            raise ValueError(f"hidden must be [{B}, {pl.hidden_dim}], not {tuple(hidden.shape)}")
-        horizon = int(min(cfg.horizon, linear_schedule(cfg.horizon_schedule, step)))   # :179-182
-        if horizon != self.plan_horizon and t0:
-            self.plan_horizon = horizon
+        self._check_call(B, hidden)
+        if t0:   # :179-182: the schedule moves the plan horizon only at an episode start
+            self.plan_horizon = self.horizon(step)
         H = self.plan_horizon
         self.mixture_coef = linear_schedule(cfg.regularization_schedule, step)
         cts = self.counts(self.mixture_coef, self._has_elites, t0)
@@ -316,33 +249,22 @@ class TdIcemDrnn(Checkpointed):
             I, A, dev = cfg.iterations, cfg.action_dim, self.device
             outs = dict(value=torch.zeros(B, I, self.Tw, device=dev), mean=torch.zeros(B, I, H, A, device=dev),
                         std=torch.zeros(B, I, H, A, device=dev))
-        device_rng = noise is None and self.rng == "device"
+        g = outs.get
 
         def device_work():
-            if device_rng:
+            if noise is None and self.rng == "device":
                 self._draw_device(B, H, cts, off, reuse)
-            self._launch(p, outs)
+            _lib.call("tdmpc_drnn_plan_icem", pl.ddims, p, pl.packed, pl.obs_buf, pl.hidden_buf, pl.noise_flat, pl.u,
+                      pl.prev_mean_flat, pl.elites, pl.action, pl.metrics, self.hidden_out, pl.z_in, g("value"),
+                      g("mean"), g("std"), *pl._ws(), pl._stream())
 
-        if self.graph and noise is None and trace is None:
-            key = (H, B, tuple(cts), reuse, warm, bool(eval_mode), float(self.std), self.rng)
-            ent = pl._graphs.get(key)
-            if ent is None:
-                while len(pl._graphs) >= self.MAX_GRAPHS:
-                    pl._graphs.pop(next(iter(pl._graphs)))
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    device_work()
-                ent = pl._graphs[key] = (g, p)   # (p holds nothing the graph reads after capture; kept for inspection)
-            ent[0].replay()
-        else:
-            device_work()
+        captured = self.graph and noise is None and trace is None
+        key = (H, B, tuple(cts), reuse, warm, bool(eval_mode), float(self.std), self.rng)
+        pl.run(device_work, key if captured else None, self.MAX_GRAPHS)
         if trace is not None:
             trace.update(value=icem_trace_values(outs["value"], cts),
                          mean=outs["mean"], std=outs["std"], counts=cts, z_in=pl.z_in[:B].clone())
         self._has_prev = True
         self._has_elites = True
-        ms = pl._ms_dev[:4 + 2 * B].cpu()
-        pl.raise_status(int(ms[:1].view(torch.int32)[0]))
-        m = ms[4:4 + 2 * B].view(B, 2).double().tolist()
-        return (pl.action[:B].clone(), self.hidden_out[:B].clone(),
-                [{"external_reward_mean": float(r), "current_std": float(s)} for r, s in m])
+        m = self._metrics(B)
+        return pl.action[:B].clone(), self.hidden_out[:B].clone(), m

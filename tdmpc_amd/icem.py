@@ -23,16 +23,13 @@ same distributions, no host work. `plan(..., noise=IcemNoise)` takes explicit dr
 """
 from __future__ import annotations
 
-import ctypes as C
-from copy import deepcopy
-
 import numpy as np
 import torch
 
 from . import _lib
 from .colored_noise import BatchedColoredNoise, _scales as _spectrum
 from .config import linear_schedule
-from .tdmpc import Checkpointed, _discount_pows, pack_told
+from .tdmpc import Agent, HipPlanner, _discount_pows
 from .told import TOLD
 
 
@@ -115,65 +112,107 @@ def icem_trace_values(value, cts):
     return [value[:, i, :n + e + pp] for i, (n, pp, e) in enumerate(cts)]
 
 
-class TdICEM(Checkpointed):
+def icem_draw_reference(pl, e, H, cts, off, eval_mode, draw_host, compose, act_in_place):
+    """Env e's stream in the reference's draw order on torch's (device) and numpy's global generators. The two
+    generators are independent, so numpy's draws run first on the host -- draw_host() -> (row counts n of the coloured
+    [H, n, A] blocks in draw order, their float32 values or None), then the pick's uniform, which is returned -- and
+    travel in ONE pinned async copy; torch's follow in order: the pre-rollout's normals, per iteration whatever
+    compose(buf, i, n, ne, cols) draws while it fills the sample block and the reuse tail (cols: an iterator over the
+    device copies of the coloured blocks) and the terminal policy noise, then the action noise."""
+    A, S = pl.A, off["total"]
+    buf = pl.noise_flat[e * S:(e + 1) * S]
+    ns, host = draw_host()
+    u = float(np.random.random_sample())
+    cols = []
+    if host is not None and host.size:
+        dst, o = pl.stage_colored(host), 0
+        for n in ns:
+            cols.append(dst[o:o + H * n * A].view(H, n, A))
+            o += H * n * A
+    cols = iter(cols)
+    P0 = cts[0][1]
+    for t in range(H):
+        buf[t * P0 * A:(t + 1) * P0 * A].view(P0, A).normal_()
+    for i, (n, p, ne) in enumerate(cts):
+        compose(buf, i, n, ne, cols)
+        buf[off["term"][i]:off["term"][i] + (n + ne + p) * A].view(n + ne + p, A).normal_()
+    if not eval_mode:
+        act = buf[off["act"]:off["act"] + A]
+        if act_in_place:
+            act.normal_()
+        else:
+            act.copy_(torch.randn(A, device=pl.device))
+    return u
+
+
+class IcemBuffers:
+    """What both iCEM planners hold beside their base planner's buffers: the elites kept from call to call and the
+    hand-over of the host-drawn coloured blocks (rng 'reference')."""
+
+    def __init__(self, cfg, **kw):
+        super().__init__(cfg, **kw)
+        A, K, N, H, dev = cfg.action_dim, cfg.num_elites, cfg.num_samples, cfg.horizon, self.device
+        self.E_max = int(cfg.fraction_elites_reused * K)
+        self.elites = torch.zeros(self.max_batch, H, K, A, dtype=torch.float32, device=dev)
+        self.col_max = cfg.iterations * H * N * A + H * self.E_max * A   # coloured floats of one env and call
+        self._col_d = torch.empty(self.col_max, dtype=torch.float32, device=dev)
+        self._col_h = torch.empty(self.col_max, dtype=torch.float32, pin_memory=dev.type == "cuda")
+        self._col_done = None
+
+    def stage_colored(self, host):
+        """One env's host-drawn coloured floats -> their device copy, through the pinned block (one async copy)."""
+        if self._col_done is not None:
+            self._col_done.synchronize()   # the previous copy has left the pinned buffer
+        stage = self._col_h[:host.size]
+        stage.numpy()[:] = host
+        dst = self._col_d[:host.size]
+        dst.copy_(stage, non_blocking=True)
+        self._col_done = torch.cuda.Event()
+        self._col_done.record()
+        return dst
+
+
+class IcemPlanner(IcemBuffers, HipPlanner):
+    """HipPlanner with the iCEM workspace (N + K + num_pi rows per env; num_pi: the regularization_schedule's largest
+    value, the calls pass their own counts in tdmpc_icem_params) and a noise stream sized here: tdmpc_icem_sizes_for
+    reports none, the stream's layout being the caller's."""
+
+    entry, sizes_abi = "tdmpc_plan_icem", "tdmpc_icem_sizes_for"
+    # TdICEM launches eagerly and then waits for the plan: there the pinned copy + stream synchronize came out at
+    # 1.90 or 1.97-2.05 ms per one-env plan() depending on the core the process sat on, the blocking copy at 1.91-1.95
+    pin_read_back = False
+
+    def _make_dims(self, cfg, max_batch):
+        rs = str(cfg.regularization_schedule)
+        mix_max = max(linear_schedule(rs, 0), linear_schedule(rs, 10**12))
+        self.pmax = max(1, int(mix_max * cfg.num_samples))
+        d = _lib.dims_from_cfg(cfg, max_batch=max_batch, enc_norm=bool(getattr(cfg, "normalize", False)))
+        d.num_pi = self.pmax
+        return d
+
+    def _noise_floats(self, sz):
+        cfg = self.cfg
+        A, N, H = cfg.action_dim, cfg.num_samples, cfg.horizon
+        E = int(cfg.fraction_elites_reused * cfg.num_elites)
+        # per-env stream upper bound: pre-rollout + per iteration (samples + terminal) + reuse tail + action
+        return H * self.pmax * A + cfg.iterations * (H * N * A + (N + E + self.pmax) * A) + H * E * A + A
+
+
+class TdICEM(Agent):
+    RNGS = ("reference", "device")
+
     def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", path: str = "auto"):
         if getattr(cfg, "modality", "state") != "state":
             raise NotImplementedError("iCEM drop-in: state observations (the pixel DSSM encoder is rlpyt's)")
         enc_norm = bool(getattr(cfg, "normalize", False))
         if enc_norm and getattr(cfg, "norm_type", "ln") != "ln":
             raise NotImplementedError("iCEM drop-in: the LayerNorm state encoder (norm_type 'ln')")
-        if rng not in ("reference", "device"):
-            raise ValueError("rng: 'reference' or 'device'")
-        self.rng = rng
-        if path not in _lib.PATHS:
-            raise ValueError(f"path must be one of {sorted(_lib.PATHS)}")
-        self.path = path
-        self.cfg = cfg
-        self.device = torch.device(cfg.device)
-        self.std = linear_schedule(cfg.std_schedule, 0)                       # :84
+        self._init_agent(cfg, lambda c: TOLD(c, enc_norm=enc_norm), rng)        # :84, :86-87
         self.mixture_coef = linear_schedule(cfg.regularization_schedule, 0)   # :85
-        self.model = TOLD(cfg, enc_norm=enc_norm).to(self.device)
-        self.model_target = deepcopy(self.model)
-        self.model.eval()
-        self.model_target.eval()
         self.plan_horizon = 1                                                  # :93
-        self.max_batch = max_batch
-        A, K, N, H = cfg.action_dim, cfg.num_elites, cfg.num_samples, cfg.horizon
-        rs = str(cfg.regularization_schedule)
-        mix_max = max(linear_schedule(rs, 0), linear_schedule(rs, 10**12))
-        self.P_max = max(1, int(mix_max * N))
-        d = _lib.dims_from_cfg(cfg, max_batch=max_batch, enc_norm=enc_norm)
-        d.num_pi = self.P_max
-        self.dims = d
-        self.L = _lib.lib()
-        sz = _lib.Sizes()
-        _lib.check(self.L.tdmpc_icem_sizes_for(C.byref(d), C.byref(sz)), "tdmpc_icem_sizes_for")
-        dev = self.device
-        self.packed = torch.zeros(sz.packed_weight_bytes // 4, dtype=torch.float32, device=dev)   # (gaps stay 0)
-        self.L.tdmpc_pack_forget(C.c_void_p(self.packed.data_ptr()))   # (the address may be a freed buffer's)
-        self.workspace = torch.empty(sz.workspace_bytes // 4, dtype=torch.float32, device=dev)
-        self.E_max = int(cfg.fraction_elites_reused * K)
-        T_max = N + self.E_max + self.P_max
-        # per-env stream upper bound: pre-rollout + per iteration (samples + terminal) + reuse tail + action
-        self.stream_max = H * self.P_max * A + cfg.iterations * (H * N * A + T_max * A) + H * self.E_max * A + A
-        self.noise = torch.zeros(max_batch * self.stream_max, dtype=torch.float32, device=dev)
-        self.u = torch.zeros(max_batch, dtype=torch.float64, device=dev)
-        self.prev_mean_flat = torch.zeros(max_batch * H * A, dtype=torch.float32, device=dev)
-        self.elites = torch.zeros(max_batch, H, K, A, dtype=torch.float32, device=dev)
-        self.action = torch.zeros(max_batch, A, dtype=torch.float32, device=dev)
-        # [status word | 3 pad words | metrics [max_batch, 2]]: a call's sticky device status (tdmpc_icem_params.status:
-        # TDMPC_STATUS_PACK_STALE) comes down with its metrics in one copy
-        self._ms_dev = torch.zeros(4 + 2 * max_batch, dtype=torch.float32, device=dev)
-        self.status = self._ms_dev[:1].view(torch.int32)
-        self.metrics = self._ms_dev[4:].view(max_batch, 2)
-        self.obs_buf = torch.zeros(max_batch, cfg.obs_shape[0], dtype=torch.float32, device=dev)
-        col_max = cfg.iterations * H * N * A + H * self.E_max * A   # coloured floats of one env and call
-        self._stage = torch.empty(col_max, dtype=torch.float32, device=dev)
-        self._pinned = torch.empty(col_max, dtype=torch.float32, pin_memory=dev.type == "cuda")
-        self._h2d_done = None
+        pl = self.planner = IcemPlanner(cfg, max_batch=max_batch, device=self.device, path=path)
+        self.P_max, self.E_max, self.elites = pl.pmax, pl.E_max, pl.elites
         self._dev_plans = {}
-        self._packed_key = self._packed_model = None
-        self._packed_params = []
         self._has_prev = False
         self._has_elites = False
         self._elite_H = 0
@@ -183,7 +222,7 @@ class TdICEM(Checkpointed):
     def _prev_mean(self):
         if not self._has_prev:
             raise AttributeError("_prev_mean")
-        return self.prev_mean_flat[:self.plan_horizon * self.cfg.action_dim].view(self.plan_horizon, -1)
+        return self.planner.prev_mean_view(self.plan_horizon, 1)[0]
 
     @property
     def _elite_actions(self):
@@ -277,112 +316,66 @@ class TdICEM(Checkpointed):
     def _draw_device(self, B, H, cts, off, reuse):
         """rng 'device' for B envs: the B streams white in one draw, every coloured third / reuse tail overwritten
         from one batched spectrum draw per sample length, the picks' uniforms: ~8 launches per call."""
-        self.noise[:B * off["total"]].normal_()
+        noise = self.planner.noise_flat
+        noise[:B * off["total"]].normal_()
         for gen, pos in self._device_plan(H, cts, off, reuse, B):
-            self.noise[pos] = gen.draw()
-        self.u[:B].uniform_()
+            noise[pos] = gen.draw()
+        self.planner.u[:B].uniform_()
 
     def _draw(self, e, H, cts, off, reuse, eval_mode):
-        """Env e's stream in the reference's draw order on torch's (device) and numpy's global generators.
-        The two generators are independent, so the numpy draws (coloured thirds, reused-elite tail, the pick's
-        uniform) run first on the host and travel in ONE pinned async copy; the torch draws follow in order."""
-        cfg, A = self.cfg, self.cfg.action_dim
-        S = off["total"]
-        buf = self.noise[e * S:(e + 1) * S]
-        dev = self.device
+        """Env e's stream in the reference's order (icem_draw_reference): numpy draws the pink and brown thirds and
+        the reused elites' tail, torch the white third (and a white tail when noise_beta is 0)."""
+        cfg, A, dev = self.cfg, self.cfg.action_dim, self.device
         specs = self._colored_specs(H, cts, reuse)
-        host = self._colored_host(specs, H)
-        u = float(np.random.random_sample())
-        if self._h2d_done is not None:
-            self._h2d_done.synchronize()   # the previous call's copy has left the pinned buffer
-        stage = self._pinned[:host.size]
-        stage.numpy()[:] = host
-        dst = self._stage[:host.size]
-        dst.copy_(stage, non_blocking=True)
-        self._h2d_done = torch.cuda.Event()
-        self._h2d_done.record()
-        col, o = [], 0
-        for b, n, L, _, _ in specs:
-            col.append(dst[o:o + H * n * A].view(H, n, A))
-            o += H * n * A
-        P0 = cts[0][1]
-        for t in range(H):
-            buf[t * P0 * A:(t + 1) * P0 * A].view(P0, A).normal_()
-        k = 0
-        for i, (n, p, ne) in enumerate(cts):
-            n0, n1, n2 = _thirds(n)
+
+        def compose(buf, i, n, ne, cols):
+            n0, n1, _ = _thirds(n)
             samp = buf[off["samp"][i]:off["samp"][i] + H * n * A].view(H, n, A)
             samp[:, :n0].copy_(torch.randn(H, n0, A, device=dev))
-            samp[:, n0:n0 + n1].copy_(col[k])
-            samp[:, n0 + n1:].copy_(col[k + 1])
-            k += 2
+            samp[:, n0:n0 + n1].copy_(next(cols))
+            samp[:, n0 + n1:].copy_(next(cols))
             if i == 0 and reuse:
                 r = buf[off["reuse"]:off["reuse"] + H * ne * A].view(H, ne, A)
-                if cfg.noise_beta > 0:
-                    r.copy_(col[k])
-                    k += 1
-                else:
-                    r.copy_(torch.randn(H, ne, A, device=dev))
-            buf[off["term"][i]:off["term"][i] + (n + ne + p) * A].view(n + ne + p, A).normal_()
-        if not eval_mode:
-            buf[off["act"]:off["act"] + A].normal_()
-        return u
+                r.copy_(next(cols) if cfg.noise_beta > 0 else torch.randn(H, ne, A, device=dev))
+
+        return icem_draw_reference(self.planner, e, H, cts, off, eval_mode,
+                                   lambda: ([sp[1] for sp in specs], self._colored_host(specs, H)), compose, True)
 
     def _load(self, e, H, cts, off, reuse, nz):
         S = off["total"]
-        return icem_load(self.noise[e * S:(e + 1) * S], self.cfg.action_dim, H, cts, off, reuse, nz)
+        return icem_load(self.planner.noise_flat[e * S:(e + 1) * S], self.cfg.action_dim, H, cts, off, reuse, nz)
 
     @torch.no_grad()
     def plan(self, obs, eval_mode=False, step=None, t0=True, noise=None, trace=None):
         """tdmpc_icem_similarity_mlp.py:160-265 -> (action tensor [A], metrics dict)."""
-        cfg = self.cfg
-        metrics = {"external_reward_mean": 0.0, "current_std": 0.0}
-        if step < cfg.seed_steps and not eval_mode:
-            return torch.empty(cfg.action_dim, dtype=torch.float32, device=self.device).uniform_(-1, 1), metrics
+        if self._seed_step(step, eval_mode):
+            return self._seed_return()
         obs = torch.as_tensor(np.asarray(obs), dtype=torch.float32).view(1, -1)
-        a, m = self._plan_envs(obs, eval_mode, step, t0, [noise] if noise is not None else None, trace)
-        ms = self._ms_dev[:6].cpu()
-        self._raise_status(int(ms[:1].view(torch.int32)))
-        m = ms[4:6].double().numpy()
-        metrics.update({"external_reward_mean": float(m[0]), "current_std": float(m[1])})
-        return a[0].clone(), metrics
+        a, _ = self._plan_envs(obs, eval_mode, step, t0, [noise] if noise is not None else None, trace)
+        return a[0].clone(), self._metrics(1)[0]
 
     @torch.no_grad()
     def plan_batch(self, obs, eval_mode=False, step=None, t0=True, sync_metrics=True):
         """B independent iCEM plans in one call (vectorised envs, all at the same step / t0): obs [B, obs_dim] ->
         (actions [B, A], metrics). Env e's result equals a single-env plan() on its own noise stream
-        (tests/test_icem.py::test_gpu_icem_batched_equals_single). Seed steps are not batched."""
-        if step < self.cfg.seed_steps and not eval_mode:
+        (tests/test_icem.py::test_gpu_icem_batched_equals_single). Seed steps are not batched. sync_metrics=False
+        returns the metrics tensor [B, 2] without a host sync: a device failure then shows at check_status() only."""
+        if self._seed_step(step, eval_mode):
             raise ValueError("plan_batch: seed steps draw uniform actions; call plan() per env")
         obs = torch.as_tensor(obs, dtype=torch.float32)
         a, m = self._plan_envs(obs.view(obs.shape[0], -1), eval_mode, step, t0, None, None)
-        if not sync_metrics:
-            return a, m
-        B = obs.shape[0]
-        ms = self._ms_dev[:4 + 2 * B].cpu()
-        self._raise_status(int(ms[:1].view(torch.int32)))
-        return a, [{"external_reward_mean": float(r), "current_std": float(sd)}
-                   for r, sd in ms[4:].view(B, 2).double().numpy()]
+        return a, (self._metrics(obs.shape[0]) if sync_metrics else m)
 
     def check_status(self):
         """Synchronising check of the sticky device status word (for plan_batch(sync_metrics=False) callers)."""
-        self._raise_status(int(self.status.item()))
-
-    def _raise_status(self, st: int):
-        if st:
-            self.status.zero_()
-            raise RuntimeError(f"tdmpc_plan_icem failed on the device (status {st}): "
-                               + _lib.status_text(st) + "; its actions are NaN")
+        self.planner.check_status()
 
     def _plan_envs(self, obs, eval_mode, step, t0, noise, trace):
-        cfg = self.cfg
+        cfg, pl = self.cfg, self.planner
         B = obs.shape[0]
-        if B > self.max_batch:
-            raise ValueError(f"batch {B} > max_batch {self.max_batch}")
-        horizon = int(min(cfg.horizon, linear_schedule(cfg.horizon_schedule, step)))
-        extend = False
-        if horizon != self.plan_horizon and t0:
-            self.plan_horizon, extend = horizon, True
+        self._check_call(B)
+        if t0:   # :172-175: the schedule moves the plan horizon only at an episode start
+            self.plan_horizon = self.horizon(step)
         H = self.plan_horizon
         self.mixture_coef = linear_schedule(cfg.regularization_schedule, step)
         cts = self.counts(self.mixture_coef, self._has_elites)
@@ -397,18 +390,18 @@ class TdICEM(Checkpointed):
         if reuse and self._elite_H not in (H, H - 1):
             raise RuntimeError("elite horizon mismatch")   # the reference's torch.cat would fail here
         off = self._layout(H, cts, reuse)
-        pack_told(self, self.model)
-        self.obs_buf[:B].copy_(obs.to(self.device))
+        pl.pack(self.model)
+        pl.obs_buf[:B].copy_(obs.to(self.device))
         if noise is not None:
             for e, nz in enumerate(noise):
-                self.u[e:e + 1].fill_(self._load(e, H, cts, off, reuse, nz))
+                pl.u[e:e + 1].fill_(self._load(e, H, cts, off, reuse, nz))
         elif self.rng == "device":
             self._draw_device(B, H, cts, off, reuse)
         else:
             us = [self._draw(e, H, cts, off, reuse, eval_mode) for e in range(B)]
-            self.u[:B].copy_(torch.tensor(us, dtype=torch.float64))
-        p = icem_params(cfg, B, H, cts, off, reuse, (not t0) and self._has_prev, eval_mode, self.std, self.status,
-                        self.path, self._elite_H if reuse else H)
+            pl.u[:B].copy_(torch.tensor(us, dtype=torch.float64))
+        p = icem_params(cfg, B, H, cts, off, reuse, (not t0) and self._has_prev, eval_mode, self.std, pl.status,
+                        pl.path, self._elite_H if reuse else H)
         dev = self.device
         value_out = mean_out = std_out = None
         if trace is not None:
@@ -416,15 +409,8 @@ class TdICEM(Checkpointed):
             value_out = torch.zeros(B, cfg.iterations, Tw, device=dev)
             mean_out = torch.zeros(B, cfg.iterations, H, cfg.action_dim, device=dev)
             std_out = torch.zeros_like(mean_out)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.L.tdmpc_plan_icem(
-            C.byref(self.dims), C.byref(p), C.c_void_p(self.packed.data_ptr()), C.c_void_p(self.obs_buf.data_ptr()),
-            0, C.c_void_p(self.noise.data_ptr()), C.c_void_p(self.u.data_ptr()),
-            C.c_void_p(self.prev_mean_flat.data_ptr()), C.c_void_p(self.elites.data_ptr()),
-            C.c_void_p(self.action.data_ptr()), C.c_void_p(self.metrics.data_ptr()),
-            C.c_void_p(_lib.ptr(value_out)), C.c_void_p(_lib.ptr(mean_out)), C.c_void_p(_lib.ptr(std_out)),
-            C.c_void_p(self.workspace.data_ptr()), self.workspace.numel() * 4, C.c_void_p(stream))
-        _lib.check(rc, "tdmpc_plan_icem")
+        _lib.call("tdmpc_plan_icem", pl.dims, p, pl.packed, pl.obs_buf, 0, pl.noise_flat, pl.u, pl.prev_mean_flat,
+                  pl.elites, pl.action, pl.metrics, value_out, mean_out, std_out, *pl._ws(), pl._stream())
         if trace is not None:
             trace.update(value=[v[0] for v in icem_trace_values(value_out, cts)],
                          mean=mean_out[0], std=std_out[0], counts=cts,
@@ -432,4 +418,4 @@ class TdICEM(Checkpointed):
         self._has_prev = True
         self._has_elites = True
         self._elite_H = H
-        return self.action[:B], self.metrics[:B]
+        return pl.action[:B], pl.metrics[:B]

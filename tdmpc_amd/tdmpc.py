@@ -66,45 +66,115 @@ class Checkpointed:
         load_checkpoint(fp, self.model, self.model_target, self.device)
 
 
-def pack_told(pl, model):
-    """Pack `model`'s parameters (reference state_dict order) into pl.packed through tdmpc_pack_weights when any
-    of them changed since the last call (pl: an object with L, dims, device, packed and the _packed_* cache)."""
+class Agent(Checkpointed):
+    """What the four planning agents share: the constructor preamble, the seed-step return, the argument checks and
+    the metrics of a synchronising call. `planner` is the agent's HipPlanner."""
+
+    METRICS0 = {"external_reward_mean": 0.0, "current_std": 0.0}
+    RNGS = ("reference", "fused")
+    HIDDEN = False   # plan() also returns the GRU state
+
+    def _init_agent(self, cfg, model, rng, graph=False):
+        if rng not in self.RNGS:
+            raise ValueError(f"rng must be one of {self.RNGS}, not {rng!r}")
+        self.cfg, self.rng, self.graph = cfg, rng, graph
+        self.device = torch.device(cfg.device)
+        self.std = linear_schedule(cfg.std_schedule, 0)
+        self.model = model(cfg).to(self.device)
+        self.model_target = deepcopy(self.model)
+        self.model.eval()
+        self.model_target.eval()
+
+    def horizon(self, step):
+        return int(min(self.cfg.horizon, linear_schedule(self.cfg.horizon_schedule, step)))
+
+    def _seed_step(self, step, eval_mode):
+        return step < self.cfg.seed_steps and not eval_mode
+
+    def _seed_return(self, B=None):
+        """The reference's return at a seed step (uniform actions, zero metrics, no GRU state) for one env, or for B
+        envs drawn env by env."""
+        A, dev = self.cfg.action_dim, self.device
+        if B is None:
+            a, m = torch.empty(A, dtype=torch.float32, device=dev).uniform_(-1, 1), dict(self.METRICS0)
+        else:
+            a, m = torch.empty(B, A, dtype=torch.float32, device=dev), [dict(self.METRICS0) for _ in range(B)]
+            for e in range(B):
+                a[e].uniform_(-1, 1)
+        return (a, None, m) if self.HIDDEN else (a, m)
+
+    @staticmethod
+    def _per_env(t0, B):
+        return [t0] * B if isinstance(t0, (bool, int, np.bool_)) else list(t0)
+
+    def _check_call(self, B, hidden=None):
+        pl = self.planner
+        if B > pl.max_batch:
+            raise ValueError(f"batch {B} > max_batch {pl.max_batch}")
+        if hidden is not None and hidden.shape != (B, pl.hidden_dim):
+            raise ValueError(f"hidden must be [{B}, {pl.hidden_dim}], not {tuple(hidden.shape)}")
+
+    def _warm(self, t0s, H):
+        """The CEM agents (per-env `_has_prev`, `_prev_H`), per env: warm-start from the previous plan's mean (not at t0, and only once there is one)."""
+        warm = []
+        for e, t0 in enumerate(t0s):
+            w = (not t0) and bool(self._has_prev[e])
+            if w and self._prev_H[e] != H:
+                # the reference's `mean[:-1] = self._prev_mean[1:]` raises on a horizon change
+                raise RuntimeError(f"shape mismatch: prev_mean horizon {self._prev_H[e]} vs {H}")
+            warm.append(w)
+        return warm
+
+    def _metrics(self, B):
+        """The synchronising end of a call (HipPlanner.read_back) as the reference's metrics dicts."""
+        return [dict(self.METRICS0, external_reward_mean=float(r), current_std=float(s))
+                for r, s in self.planner.read_back(B)]
+
+
+def pack_weights(pl, model, tensors, abi, dims, stage_all):
+    """Pack `tensors(model)` into pl.packed through `<abi>pack_weights` when any of them changed since the last call
+    (pl: an object with L, device, packed and the _packed_* cache; dims: the structure the two `abi` functions take).
+    stage_all: copy every tensor into a device fp32 staging tensor kept per planner; otherwise only a source that is
+    not the model's own device fp32 tensor is staged. Either way the pointer set -- the key of the library's device
+    job-table cache -- stays the same from one repack to the next."""
     if pl._packed_key is not None and pl._packed_model is model:
-        key = tuple((p.data_ptr(), p._version) for p in pl._packed_params)
-        if key == pl._packed_key:
+        if tuple((p.data_ptr(), p._version) for p in pl._packed_params) == pl._packed_key:
             return
-    params = list(model.state_dict().values())
+    params = tensors(model)
     if pl._packed_model is not None and pl._packed_model is not model:
         # another model object: re-key the buffer's job table (a graph captured over the old model's pack -- the
         # learner's update -- then fails loudly if replayed, TDMPC_STATUS_PACK_STALE, instead of packing this one)
-        pl.L.tdmpc_pack_forget(C.c_void_p(pl.packed.data_ptr()))
+        pl.L.tdmpc_pack_forget(pl.packed.data_ptr())
     pl._packed_model, pl._packed_params = model, params
     key = tuple((p.data_ptr(), p._version) for p in params)
-    params = [p.detach().to(pl.device, torch.float32).contiguous() for p in params]
-    # a source that is not the model's own device fp32 tensor is copied into a staging tensor kept per planner, so the
-    # pointer set -- the key of the library's device job-table cache -- stays the same from one repack to the next
-    stage = getattr(pl, "_pack_stage", None)
-    if stage is None or len(stage) != len(params):
-        stage = pl._pack_stage = [None] * len(params)
-    for i, (q, p) in enumerate(zip(params, pl._packed_params)):
-        if q.data_ptr() != p.data_ptr():
-            if stage[i] is None or stage[i].shape != q.shape:
-                stage[i] = torch.empty_like(q)
-            stage[i].copy_(q)
-            params[i] = stage[i]
-    n = pl.L.tdmpc_num_param_tensors(C.byref(pl.dims))
+    n = getattr(pl.L, abi + "num_param_tensors")(dims)
     if n != len(params):
-        raise ValueError(f"TOLD has {len(params)} tensors, the packer expects {n}")
-    arr = (C.c_void_p * n)(*[p.data_ptr() for p in params])
-    stream = torch.cuda.current_stream(pl.device).cuda_stream
-    _lib.check(pl.L.tdmpc_pack_weights(C.byref(pl.dims), arr, n, C.c_void_p(pl.packed.data_ptr()),
-                                        pl.packed.numel() * 4, C.c_void_p(stream)), "tdmpc_pack_weights")
-    pl._keep = params  # keep source tensors alive until the stream has consumed them
+        raise ValueError(f"{type(model).__name__} has {len(params)} float tensors, the packer expects {n}")
+    stage = pl._pack_stage
+    if len(stage) != n:
+        stage = pl._pack_stage = [None] * n
+    src = []
+    for i, p in enumerate(params):
+        q = p.detach() if stage_all else p.detach().to(pl.device, torch.float32).contiguous()
+        if stage_all or q.data_ptr() != p.data_ptr():
+            if stage[i] is None or stage[i].shape != q.shape:
+                stage[i] = torch.empty(q.shape, dtype=torch.float32, device=pl.device)
+            stage[i].copy_(q)
+            q = stage[i]
+        src.append(q)
+    arr = (C.c_void_p * n)(*[q.data_ptr() for q in src])
+    _lib.call(abi + "pack_weights", dims, arr, n, pl.packed, pl.packed.numel() * 4, pl._stream())
+    pl._keep = src  # keep source tensors alive until the stream has consumed them
     pl._packed_key = key
     # the pointer array stays valid for repack_live() while the packed tensors ARE the model's (no dtype / device
     # / layout copy was made)
-    live = all(q.data_ptr() == p.data_ptr() for q, p in zip(params, pl._packed_params))
+    live = all(q.data_ptr() == p.data_ptr() for q, p in zip(src, params))
     pl._ptr_arr = (arr, n) if live else None
+
+
+def pack_told(pl, model):
+    """Pack TOLD's parameters (reference state_dict order), reading the model's own device fp32 tensors in place."""
+    pack_weights(pl, model, lambda m: list(m.state_dict().values()), "tdmpc_", pl.dims, False)
 
 
 def repack_live(pl, model) -> bool:
@@ -115,9 +185,7 @@ def repack_live(pl, model) -> bool:
     if pl._packed_model is not model or getattr(pl, "_ptr_arr", None) is None:
         return False
     arr, n = pl._ptr_arr
-    stream = torch.cuda.current_stream(pl.device).cuda_stream
-    _lib.check(pl.L.tdmpc_pack_weights(C.byref(pl.dims), arr, n, C.c_void_p(pl.packed.data_ptr()),
-                                        pl.packed.numel() * 4, C.c_void_p(stream)), "tdmpc_pack_weights")
+    _lib.call("tdmpc_pack_weights", pl.dims, arr, n, pl.packed, pl.packed.numel() * 4, pl._stream())
     return True
 
 
@@ -138,7 +206,7 @@ class HipPlanner:
         # zeroed once: tdmpc_pack_weights writes every tensor's region (padding included) but not the alignment gaps
         # between them, which padded vector reads may touch
         self.packed = torch.zeros(sz.packed_weight_bytes // 4, dtype=torch.float32, device=dev)
-        self.L.tdmpc_pack_forget(C.c_void_p(self.packed.data_ptr()))   # (the address may be a freed buffer's)
+        self.L.tdmpc_pack_forget(self.packed.data_ptr())   # (the address may be a freed buffer's)
         self.workspace = torch.empty(sz.workspace_bytes // 4, dtype=torch.float32, device=dev)
         d = self.dims
         self.N, self.P, self.A = d.num_samples, d.num_pi, d.action_dim
@@ -146,7 +214,7 @@ class HipPlanner:
         self.max_batch = max_batch
         # Env streams are packed with the CALL's per-env size (depends on H and I), so the flat buffers are
         # re-viewed per call (`noise_view`, `prev_mean_view`); sized for the maximum.
-        self.noise_flat = torch.zeros(max_batch * sz.noise_floats_per_env, dtype=torch.float32, device=dev)
+        self.noise_flat = torch.zeros(max_batch * self._noise_floats(sz), dtype=torch.float32, device=dev)
         self.prev_mean_flat = torch.zeros(max_batch * d.max_horizon * self.A, dtype=torch.float32, device=dev)
         self.action = torch.zeros(max_batch, self.A, dtype=torch.float32, device=dev)
         # one device block [status word | 3 pad words | metrics [max_batch, 2]] so a call's status and metrics come
@@ -185,6 +253,7 @@ class HipPlanner:
         self._packed_key = None
         self._packed_model = None
         self._packed_params = []
+        self._pack_stage = []
         self._ptr_arr = None
         self._graphs = {}
         # the metrics come down through pinned memory too (a pageable copy blocks the host)
@@ -205,14 +274,32 @@ class HipPlanner:
         self._st_pending = [False, False]
         self._st_k = 0
 
-    # (hooks of the planners built on this one: tdmpc_amd/drnn.py)
+    # (hooks of the planners built on this one: tdmpc_amd/icem.py, drnn.py, drnn_icem.py)
+    entry = "tdmpc_plan"        # the plan entry point, named when a call fails on the device
+    pin_read_back = True        # read_back() through the pinned block (a pageable copy blocks the host)
+    sizes_abi = "tdmpc_sizes_for"
+
     def _make_dims(self, cfg, max_batch):
         return _lib.dims_from_cfg(cfg, max_batch=max_batch)
 
+    def abi_dims(self):
+        return self.dims
+
     def _query_sizes(self):
         sz = _lib.Sizes()
-        _lib.check(self.L.tdmpc_sizes_for(C.byref(self.dims), C.byref(sz)), "tdmpc_sizes_for")
+        _lib.call(self.sizes_abi, self.abi_dims(), sz)
         return sz
+
+    def _noise_floats(self, sz):
+        """Floats of one env's noise stream, for the largest call."""
+        return sz.noise_floats_per_env
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _ws(self):
+        """(workspace, its bytes): the last two buffer arguments of every planning entry point."""
+        return self.workspace, self.workspace.numel() * 4
 
     # ------------------------------------------------------------------ weights
     def pack(self, model: TOLD):
@@ -267,10 +354,8 @@ class HipPlanner:
     def _reference_normals(self, B, H, I, eval_mode, seed, offset, gen_state):
         buf = self.noise_view(H, I, B)
         adv = C.c_uint64(0)
-        rc = self.L.tdmpc_reference_normals(C.byref(self.dims), C.c_void_p(buf.data_ptr()), B, buf.stride(0), H, I,
-                                            int(eval_mode), seed, offset, gen_state, self._grid_cap, C.byref(adv),
-                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _lib.check(rc, "tdmpc_reference_normals")
+        _lib.call("tdmpc_reference_normals", self.dims, buf, B, buf.stride(0), H, I, int(eval_mode), seed, offset,
+                  gen_state, self._grid_cap, C.byref(adv), self._stream())
         key = (B, H, I, bool(eval_mode))
         if self._ref_adv.setdefault(key, adv.value) != adv.value:
             raise RuntimeError(f"reference draws: counter advance {adv.value} != staged {self._ref_adv[key]}")
@@ -289,7 +374,7 @@ class HipPlanner:
         """Capturable form: the kernel reads {seed, offset} from `gen_state` when it runs; `stage_reference_state`
         fills it (through the staging copy) before every launch or replay."""
         self._gen()
-        self._reference_normals(B, H, I, eval_mode, 0, 0, C.c_void_p(self.gen_state.data_ptr()))
+        self._reference_normals(B, H, I, eval_mode, 0, 0, self.gen_state)
 
     def stage_reference_state(self, B: int, H: int, I: int, eval_mode: bool):
         """Host side of one call's reference-order draws: the generator's seed and offset into the staging block,
@@ -366,12 +451,27 @@ class HipPlanner:
         prm.status = self.status.data_ptr()
         return prm
 
-    def raise_status(self, st: int):
+    def raise_status(self, st: int, what: str | None = None):
         """Raise for a nonzero device status (and clear it): the plan's outputs are NaN, never return them."""
         if st:
             self.status.zero_()
-            raise RuntimeError(f"tdmpc_plan failed on the device (status {st}): {_lib.status_text(st)}. "
-                               "Its action is NaN.")
+            raise RuntimeError(f"{what or self.entry} failed on the device (status {st}): {_lib.status_text(st)}. "
+                               "Its actions are NaN.")
+
+    def read_back(self, B: int):
+        """The synchronising end of a call: [status | metrics] of B envs in one copy (through the pinned block where
+        there is one and the planner asks for it, `pin_read_back`), a raise on a nonzero status, and the B (reward
+        mean, std) pairs. Covers every earlier non-synchronising call too: the word is sticky."""
+        self._st_pending = [False, False]
+        n = 4 + 2 * B
+        if self._h2d_done is not None and self.pin_read_back:
+            self._pin_ms[:n].copy_(self._ms_dev[:n], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            ms = self._pin_ms
+        else:
+            ms = self._ms_dev[:n].cpu()
+        self.raise_status(int(ms[:1].view(torch.int32)[0]))
+        return ms[4:n].view(B, 2).tolist()
 
     def check_status(self):
         """Synchronising check of the sticky status word (for callers that plan with sync_metrics=False)."""
@@ -404,9 +504,12 @@ class HipPlanner:
             self._st_pending = [False, False]
             self.raise_status(st)
 
-    def launch(self, prm, obs_is_u8: bool, trace: dict | None = None):
-        L = self.L
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+    def _plan_io(self, obs_is_u8):
+        """What tdmpc_plan takes after the observations, and its outputs after the metrics (DrnnPlanner: the GRU
+        state; the encoder's latent)."""
+        return int(obs_is_u8), ()
+
+    def launch(self, prm, obs_is_u8: bool = False, trace: dict | None = None):
         B, H, I, K = prm.batch, prm.horizon, prm.iterations, self.dims.num_elites
         outs = {}
         if trace is not None:
@@ -417,54 +520,32 @@ class HipPlanner:
                         std=torch.zeros(B, I, H, self.A, device=self.device))
             trace.update(outs)
         g = outs.get
-        rc = L.tdmpc_plan(C.byref(self.dims), C.byref(prm), C.c_void_p(self.packed.data_ptr()),
-                          C.c_void_p(self.obs_buf.data_ptr()), int(obs_is_u8), C.c_void_p(self.noise_flat.data_ptr()),
-                          C.c_void_p(self.u.data_ptr()), C.c_void_p(self.prev_mean_flat.data_ptr()),
-                          C.c_void_p(self.action.data_ptr()), C.c_void_p(self.metrics.data_ptr()),
-                          C.c_void_p(_lib.ptr(g("elite"))), C.c_void_p(_lib.ptr(g("score"))),
-                          C.c_void_p(_lib.ptr(g("value"))), C.c_void_p(_lib.ptr(g("mean"))),
-                          C.c_void_p(_lib.ptr(g("std"))), C.c_void_p(self.workspace.data_ptr()),
-                          self.workspace.numel() * 4, C.c_void_p(stream))
-        _lib.check(rc, "tdmpc_plan")
+        second, more = self._plan_io(obs_is_u8)
+        _lib.call(self.entry, self.abi_dims(), prm, self.packed, self.obs_buf, second, self.noise_flat, self.u,
+                  self.prev_mean_flat, self.action, self.metrics, *more, g("elite"), g("score"), g("value"), g("mean"),
+                  g("std"), *self._ws(), self._stream())
 
+    def _call(self, name, H, std_floor, ins, *rest):
+        """`name`(dims, params of an H-step call for ins[0]'s B envs, packed, *ins as device fp32, *rest, workspace,
+        stream): the shape of every entry point below."""
+        prm = self.params(H, 1, ins[0].shape[0], False, True, std_floor)
+        ins = [None if t is None else t.to(self.device, torch.float32).contiguous() for t in ins]
+        _lib.call(name, self.abi_dims(), prm, self.packed, *ins, *rest, *self._ws(), self._stream())
 
     def estimate_value(self, z0, actions, eps_term, H: int, std_floor: float = 0.05):
         """TDMPC.estimate_value (tdmpc.py:83-92) through the C ABI for B envs: z0 [B, L], actions
         [B, H, T, A], eps_term [B, T, A] -> (value [B, T], reward at t=H-1 [B, T], z_H [B, T, L])."""
-        B = z0.shape[0]
-        prm = self.params(H, 1, B, False, True, std_floor)
-        dev = self.device
-        z0 = z0.to(dev, torch.float32).contiguous()
-        actions = actions.to(dev, torch.float32).contiguous()
-        eps_term = eps_term.to(dev, torch.float32).contiguous()
-        value = torch.empty(B, self.T, device=dev)
-        rlast = torch.empty(B, self.T, device=dev)
+        B, dev = z0.shape[0], self.device
+        value, rlast = torch.empty(B, self.T, device=dev), torch.empty(B, self.T, device=dev)
         zl = torch.empty(B, self.T, self.dims.latent_dim, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.L.tdmpc_estimate_value(C.byref(self.dims), C.byref(prm), C.c_void_p(self.packed.data_ptr()),
-                                         C.c_void_p(z0.data_ptr()), C.c_void_p(actions.data_ptr()),
-                                         C.c_void_p(eps_term.data_ptr()), self.T, C.c_void_p(value.data_ptr()),
-                                         C.c_void_p(rlast.data_ptr()), C.c_void_p(zl.data_ptr()),
-                                         C.c_void_p(self.workspace.data_ptr()), self.workspace.numel() * 4,
-                                         C.c_void_p(stream))
-        _lib.check(rc, "tdmpc_estimate_value")
+        self._call("tdmpc_estimate_value", H, std_floor, (z0, actions, eps_term), self.T, value, rlast, zl)
         return value, rlast, zl
 
     def pi_rollout(self, z0, eps_pi, H: int):
         """The policy pre-rollout of TDMPC.plan (tdmpc.py:113-118) through the C ABI for B envs: z0 [B, L],
         eps_pi [B, H, P, A] (TruncatedNormal eps of the H pi calls) -> pi_actions [B, H, P, A]."""
-        B = z0.shape[0]
-        prm = self.params(H, 1, B, False, True, 0.05)
-        dev = self.device
-        z0 = z0.to(dev, torch.float32).contiguous()
-        eps_pi = eps_pi.to(dev, torch.float32).contiguous()
-        out = torch.empty(B, H, self.P, self.A, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.L.tdmpc_pi_rollout(C.byref(self.dims), C.byref(prm), C.c_void_p(self.packed.data_ptr()),
-                                     C.c_void_p(z0.data_ptr()), C.c_void_p(eps_pi.data_ptr()),
-                                     C.c_void_p(out.data_ptr()), C.c_void_p(self.workspace.data_ptr()),
-                                     self.workspace.numel() * 4, C.c_void_p(stream))
-        _lib.check(rc, "tdmpc_pi_rollout")
+        out = torch.empty(z0.shape[0], H, self.P, self.A, device=self.device)
+        self._call("tdmpc_pi_rollout", H, 0.05, (z0, eps_pi), out)
         return out
 
     def cem_iter(self, z0, pi_actions, eps_cem, eps_term, mean, std, H: int, std_floor: float = 0.05):
@@ -472,14 +553,7 @@ class HipPlanner:
         pi_actions [B, H, P, A] (or None when P == 0), eps_cem [B, H, N, A], eps_term [B, T, A]; mean/std
         [B, H, A] are updated in place. Returns (elite_actions [B, H, K, A], score [B, K], value [B, T],
         reward_mean [B])."""
-        B = z0.shape[0]
-        K = self.dims.num_elites
-        prm = self.params(H, 1, B, False, True, std_floor)
-        dev = self.device
-        z0 = z0.to(dev, torch.float32).contiguous()
-        pa = None if pi_actions is None else pi_actions.to(dev, torch.float32).contiguous()
-        eps_cem = eps_cem.to(dev, torch.float32).contiguous()
-        eps_term = eps_term.to(dev, torch.float32).contiguous()
+        B, K, dev = z0.shape[0], self.dims.num_elites, self.device
         for t in (mean, std):
             if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, H, self.A):
                 raise ValueError("mean/std must be contiguous fp32 [B, H, A] device tensors")
@@ -487,46 +561,83 @@ class HipPlanner:
         score = torch.empty(B, K, device=dev)
         value = torch.empty(B, self.T, device=dev)
         rmean = torch.empty(B, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        vp = C.c_void_p
-        rc = self.L.tdmpc_cem_iter(C.byref(self.dims), C.byref(prm), vp(self.packed.data_ptr()), vp(z0.data_ptr()),
-                                   vp(_lib.ptr(pa)), vp(eps_cem.data_ptr()), vp(eps_term.data_ptr()),
-                                   vp(mean.data_ptr()), vp(std.data_ptr()), vp(elite.data_ptr()),
-                                   vp(score.data_ptr()), vp(value.data_ptr()), vp(rmean.data_ptr()),
-                                   vp(self.workspace.data_ptr()), self.workspace.numel() * 4, vp(stream))
-        _lib.check(rc, "tdmpc_cem_iter")
+        self._call("tdmpc_cem_iter", H, std_floor, (z0, pi_actions, eps_cem, eps_term), mean, std, elite, score,
+                   value, rmean)
         return elite, score, value, rmean
 
     def encode(self, obs):
         """TOLD.h for a batch of observations through the C ABI -> z0 [B, L]."""
         B = obs.shape[0]
-        dev = self.device
         is_u8 = obs.dtype == torch.uint8
-        obs = obs.to(dev).contiguous()
-        z0 = torch.empty(B, self.dims.latent_dim, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.L.tdmpc_encode(C.byref(self.dims), C.c_void_p(self.packed.data_ptr()), C.c_void_p(obs.data_ptr()),
-                                 int(is_u8), B, C.c_void_p(self.workspace.data_ptr()), C.c_void_p(z0.data_ptr()),
-                                 C.c_void_p(stream))
-        _lib.check(rc, "tdmpc_encode")
+        obs = obs.to(self.device).contiguous()
+        z0 = torch.empty(B, self.dims.latent_dim, device=self.device)
+        _lib.call("tdmpc_encode", self.dims, self.packed, obs, int(is_u8), B, self.workspace, z0, self._stream())
         return z0
 
+    # ------------------------------------------------------------------ one call, start to end
+    def stage_call(self, obs, B, H, I, eval_mode, std, warm, noise, reference, one_launch, copy_in_graph=False):
+        """Host side of one plan call, sent up as ONE copy: the observations (host ones; device ones are copied in
+        place), the explicit noise or numpy's elite-choice uniforms (`reference`), the generator state of the
+        reference-order draws (`one_launch`). The copy goes ahead of the device work, and an event marks the staging
+        block reusable as soon as it is done, so the host stages the next call under this plan; with copy_in_graph the
+        caller replays the copy as its graph's first node instead (`copy_up`). Returns the copy's first byte."""
+        cfg = self.cfg
+        host = not torch.is_tensor(obs) or obs.device.type == "cpu"
+        if self._h2d_done is not None:
+            self._h2d_done.synchronize()   # the previous call's staging copy has drained
+        if host:
+            self._h_obs[:B] = np.asarray(obs).reshape(B, -1)
+        elif cfg.modality == "pixels":
+            self.obs_buf[:B].copy_(obs.to(self.device, torch.uint8).view(B, *cfg.obs_shape))
+        else:
+            self.obs_buf[:B].copy_(obs.to(self.device, torch.float32).view(B, -1))
+        self.set_call_state(std, warm)
+        if noise is not None:
+            for e, nb in enumerate(noise):
+                self.load_noise(e, H, I, nb.eps_pi, nb.eps_cem, nb.eps_term, nb.eps_act)
+                self._h_u[e] = float(nb.u)
+        elif reference:
+            # np.random.choice's uniform, drawn on the host from numpy's global generator (tdmpc.py:153)
+            for e in range(B):
+                self._h_u[e] = np.random.random_sample()
+        if one_launch:
+            self.stage_reference_state(B, H, I, eval_mode)
+        lo = 0 if host else self._u_off
+        if not copy_in_graph:
+            self.copy_up(lo)
+            self.staged()
+        return lo
 
-class TDMPC(Checkpointed):
+    def copy_up(self, lo):
+        self._stage_d[lo:].copy_(self._stage_h[lo:], non_blocking=True)
+
+    def staged(self):
+        """After the staging copy is enqueued: the event that marks the pinned block reusable."""
+        if self._h2d_done is not None:
+            self._h2d_done.record()
+
+    def run(self, device_work, key=None, cap=None):
+        """Run device_work: eagerly (key None), or replayed from the graph kept under `key`, captured on a miss. No
+        eager warm-up: the library has no lazy initialisation left after pack(), and an eager run would advance the
+        planner state (prev_mean) before the captured replay. cap: the most graphs kept (the oldest goes first)."""
+        if key is None:
+            return device_work()
+        g = self._graphs.get(key)
+        if g is None:
+            while cap and len(self._graphs) >= cap:
+                self._graphs.pop(next(iter(self._graphs)))
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                device_work()
+            self._graphs[key] = g
+        g.replay()
+
+
+class TDMPC(Agent):
     """Drop-in for the reference `TDMPC` planning interface (tdmpc.py:53-163)."""
 
     def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", graph: bool = True, path: str = "auto"):
-        self.cfg = cfg
-        self.device = torch.device(cfg.device)
-        self.std = linear_schedule(cfg.std_schedule, 0)      # tdmpc.py:59
-        self.model = TOLD(cfg).to(self.device)               # tdmpc.py:60
-        self.model_target = deepcopy(self.model)             # tdmpc.py:61
-        self.model.eval()
-        self.model_target.eval()
-        if rng not in ("reference", "fused"):
-            raise ValueError(rng)
-        self.rng = rng
-        self.graph = graph
+        self._init_agent(cfg, TOLD, rng, graph)               # tdmpc.py:59-61
         self.planner = HipPlanner(cfg, max_batch=max_batch, device=self.device, path=path)
         from .learner import RandomShiftsAug
         self.aug = RandomShiftsAug(cfg)                       # tdmpc.py:64
@@ -586,14 +697,10 @@ class TDMPC(Checkpointed):
     @torch.no_grad()
     def plan(self, obs, eval_mode=False, step=None, t0=True):
         """tdmpc.py:94-163. Returns (action tensor [A] on self.device, {'external_reward_mean', 'current_std'})."""
-        cfg = self.cfg
-        plan_metrics = {"external_reward_mean": 0.0, "current_std": 0.0}
-        if step < cfg.seed_steps and not eval_mode:
-            return (torch.empty(cfg.action_dim, dtype=torch.float32, device=self.device).uniform_(-1, 1),
-                    plan_metrics)
+        if self._seed_step(step, eval_mode):
+            return self._seed_return()
         a, m = self._plan_envs(np.asarray(obs)[None], eval_mode, step, [t0], clone=True)
-        plan_metrics.update(m[0])
-        return a[0], plan_metrics
+        return a[0], m[0]
 
     @torch.no_grad()
     def plan_batch(self, obs, eval_mode=False, step=None, t0=True, sync_metrics=True):
@@ -605,119 +712,57 @@ class TDMPC(Checkpointed):
         persistent one-env plan giving up at a hand-off) then surfaces late: that call's actions are NaN, and the
         raise comes at the next-but-one call (or at check_status()) -- the NaN actions of the failing call and of
         the call after it may already have been returned by then."""
-        cfg = self.cfg
         obs = obs if torch.is_tensor(obs) else np.asarray(obs)
         B = obs.shape[0]
-        if step < cfg.seed_steps and not eval_mode:
-            a = torch.empty(B, cfg.action_dim, dtype=torch.float32, device=self.device)
-            for e in range(B):
-                a[e].uniform_(-1, 1)
-            if not sync_metrics:
-                return a, torch.zeros(B, 2, dtype=torch.float32, device=self.device)
-            return a, [{"external_reward_mean": 0.0, "current_std": 0.0} for _ in range(B)]
-        t0s = [t0] * B if isinstance(t0, (bool, int, np.bool_)) else list(t0)
-        return self._plan_envs(obs, eval_mode, step, t0s, sync_metrics)
+        if self._seed_step(step, eval_mode):
+            a, m = self._seed_return(B)
+            return a, (m if sync_metrics else torch.zeros(B, 2, dtype=torch.float32, device=self.device))
+        return self._plan_envs(obs, eval_mode, step, self._per_env(t0, B), sync_metrics)
 
     # ------------------------------------------------------------------ internals
-    def horizon(self, step):
-        return int(min(self.cfg.horizon, linear_schedule(self.cfg.horizon_schedule, step)))
-
     def _plan_envs(self, obs, eval_mode, step, t0s, sync_metrics=True, trace=None, noise=None, clone=False):
         """noise: optional list (one per env) of objects with eps_pi / eps_cem / eps_term / u / eps_act
         (e.g. oracle NoiseBundles) used instead of drawing. clone: return a copy of the actions (enqueued right
         after the plan, before the metrics sync, so its launch is off the host's critical path)."""
         cfg, pl = self.cfg, self.planner
         B = obs.shape[0]
-        if B > pl.max_batch:
-            raise ValueError(f"batch {B} > max_batch {pl.max_batch}")
+        self._check_call(B)
         pl.deferred_status()
         H = self.horizon(step)
         I = int(cfg.iterations)
-        warm = []
-        for e in range(B):
-            w = (not t0s[e]) and bool(self._has_prev[e])
-            if w and self._prev_H[e] != H:
-                # the reference's `mean[:-1] = self._prev_mean[1:]` raises on a horizon change
-                raise RuntimeError(f"shape mismatch: prev_mean horizon {self._prev_H[e]} vs {H}")
-            warm.append(w)
+        warm = self._warm(t0s, H)
         pl.pack(self.model)
-        host = not torch.is_tensor(obs) or obs.device.type == "cpu"
-        if pl._h2d_done is not None:
-            pl._h2d_done.synchronize()   # the previous call's staging copy has drained
-        if host:
-            pl._h_obs[:B] = np.asarray(obs).reshape(B, -1)
-        elif cfg.modality == "pixels":
-            pl.obs_buf[:B].copy_(obs.to(self.device, torch.uint8).view(B, *cfg.obs_shape))
-        else:
-            pl.obs_buf[:B].copy_(obs.to(self.device, torch.float32).view(B, -1))
-        obs_u8 = cfg.modality == "pixels"
-        pl.set_call_state(self.std, warm)
-        if noise is not None:
-            for e, nb in enumerate(noise):
-                pl.load_noise(e, H, I, nb.eps_pi, nb.eps_cem, nb.eps_term, nb.eps_act)
-                pl._h_u[e] = float(nb.u)
-        elif self.rng == "reference":
-            # np.random.choice's uniform, drawn on the host from numpy's global generator (tdmpc.py:153)
-            for e in range(B):
-                pl._h_u[e] = np.random.random_sample()
-        one_launch = noise is None and self.rng == "reference" and pl.ref_draws == "device"
-        if one_launch:
-            pl.stage_reference_state(B, H, I, eval_mode)
-        # one copy up: observations (host ones), uniforms, generator state. A synchronising call (the drop-in
-        # plan()) replays it as the captured graph's first node (a memcpy node from the pinned staging block: one
-        # launch fewer on the host's critical path); otherwise it goes ahead of the replay, and an event marks the
-        # staging block reusable as soon as the copy is done, so the host stages the next call under this plan
-        lo = 0 if host else pl._u_off
-        copy_in_graph = self.graph and sync_metrics and noise is None and trace is None
-        if not copy_in_graph:
-            pl._stage_d[lo:].copy_(pl._stage_h[lo:], non_blocking=True)
-            if pl._h2d_done is not None:
-                pl._h2d_done.record()
+        reference = self.rng == "reference"
+        one_launch = noise is None and reference and pl.ref_draws == "device"
+        captured = self.graph and noise is None and trace is None
+        # A synchronising call (the drop-in plan()) replays the staging copy as the captured graph's first node (a
+        # memcpy node from the pinned staging block: one launch fewer on the host's critical path)
+        copy_in_graph = captured and sync_metrics
+        lo = pl.stage_call(obs, B, H, I, eval_mode, self.std, warm, noise, reference, one_launch, copy_in_graph)
 
         def device_work():
             if copy_in_graph:
-                pl._stage_d[lo:].copy_(pl._stage_h[lo:], non_blocking=True)
+                pl.copy_up(lo)
             if noise is None:
                 if one_launch:
                     pl.launch_reference_draws(B, H, I, eval_mode)
-                elif self.rng == "reference":
+                elif reference:
                     for e in range(B):
                         pl.draw_reference_torch(e, H, I, eval_mode)
                 else:
                     pl.noise_view(H, I, B).normal_()
                     pl.u[:B].uniform_()
-            pl.launch(pl.device_state_params(pl.params(H, I, B, warm[0], eval_mode, self.std)), obs_u8, trace)
+            pl.launch(pl.device_state_params(pl.params(H, I, B, warm[0], eval_mode, self.std)),
+                      cfg.modality == "pixels", trace)
 
-        if self.graph and noise is None and trace is None:
-            # (self.std and the warm flags live on the device)
-            key = (H, I, B, bool(eval_mode), self.rng, one_launch, copy_in_graph, lo)
-            g = pl._graphs.get(key)
-            if g is None:
-                # No eager warm-up: the library has no lazy initialisation left after pack(), and an eager
-                # run would advance the planner state (prev_mean) before the captured replay.
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    device_work()
-                pl._graphs[key] = g
-            g.replay()
-            if copy_in_graph and pl._h2d_done is not None:
-                pl._h2d_done.record()
-        else:
-            device_work()
+        # (self.std and the warm flags live on the device, so one graph serves every value of them)
+        pl.run(device_work, (H, I, B, bool(eval_mode), self.rng, one_launch, copy_in_graph, lo) if captured else None)
+        if copy_in_graph:
+            pl.staged()
         self._has_prev[:B] = True
         self._prev_H[:B] = H
         actions = pl.action[:B].clone() if clone else pl.action[:B]
         if not sync_metrics:
             pl.post_status()   # raised by the call after next (deferred_status) or by check_status()
             return actions, pl.metrics[:B]
-        pl._st_pending = [False, False]   # (the synchronous read below covers every earlier call: the word is sticky)
-        if pl._h2d_done is not None:
-            pl._pin_ms[:4 + 2 * B].copy_(pl._ms_dev[:4 + 2 * B], non_blocking=True)   # status + metrics: one copy
-            torch.cuda.current_stream(self.device).synchronize()
-            m = pl._pin_ms[4:4 + 2 * B].view(B, 2).tolist()
-            st = int(pl._pin_ms[:1].view(torch.int32)[0])
-        else:
-            m = pl.metrics[:B].double().cpu().tolist()
-            st = int(pl.status[0])
-        pl.raise_status(st)
-        return actions, [{"external_reward_mean": float(r), "current_std": float(s)} for r, s in m]
+        return actions, self._metrics(B)

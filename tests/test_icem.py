@@ -123,15 +123,15 @@ def test_gpu_icem_draw_order(reuse, extend):
         np.random.seed(8)
         nz = icem_ref.draw_icem_noise(cfg, st, step, True, ev, device="cuda")
         after_ref = (torch.randn(4, device="cuda"), np.random.random_sample())
-        agent.noise.zero_()
+        agent.planner.noise_flat.zero_()
         agent._load(0, H, cts, off, reuse, nz)
-        want = agent.noise[:S].clone()
+        want = agent.planner.noise_flat[:S].clone()
         torch.manual_seed(7)
         np.random.seed(8)
-        agent.noise.zero_()
+        agent.planner.noise_flat.zero_()
         u = agent._draw(0, H, cts, off, reuse, ev)
         assert u == nz.u
-        assert torch.equal(agent.noise[:S], want)
+        assert torch.equal(agent.planner.noise_flat[:S], want)
         # both generators are left where the reference's draws leave them
         assert torch.equal(torch.randn(4, device="cuda"), after_ref[0])
         assert np.random.random_sample() == after_ref[1]
@@ -267,7 +267,7 @@ def test_gpu_icem_batch32_matches_oracle():
         ga, gm = ga.cpu().numpy(), gm.cpu().numpy()
         vall = gtr["value_all"].cpu().numpy()
         H = agent.plan_horizon
-        pm = agent.prev_mean_flat[:B * H * cfg.action_dim].view(B, H, -1).cpu().numpy()
+        pm = agent.planner.prev_mean_flat[:B * H * cfg.action_dim].view(B, H, -1).cpu().numpy()
         el = agent.elites[:B, :agent._elite_H].cpu().numpy()
         for e in range(B):
             rtr = {}

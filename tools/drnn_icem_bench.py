@@ -81,7 +81,6 @@ def main():
     from tdmpc_amd.icem import TdICEM
     from tdmpc_amd.told import synthetic_state_dict
     cfg = bench_cfg()
-    L = _lib.lib()
     sd = synthetic_dssm_state_dict(cfg, 0)
     out = {"shape": "humanoid L100 A21 Hd128 M512, N=512/1.25 K=64 E=16 H=5 I=6, noise_beta 2.5",
            "device": torch.cuda.get_device_name(0), "envs": {}}
@@ -107,11 +106,11 @@ def main():
         torch.cuda.synchronize()
         steps = {}
         for rows in sorted({B * (n + e) for n, _, e in cts} | {B * cts[0][1]}):
-            _lib.check(L.tdmpc_drnn_profile_begin(rows, 4096), "profile_begin")
+            _lib.call("tdmpc_drnn_profile_begin", rows, 4096)
             for _ in range(4):
                 agent.plan_batch(obs, hidden, step=step, t0=False)
             n, tms, fl = C.c_int32(), C.c_double(), C.c_double()
-            _lib.check(L.tdmpc_drnn_profile_end(C.byref(n), C.byref(tms), C.byref(fl)), "profile_end")
+            _lib.call("tdmpc_drnn_profile_end", C.byref(n), C.byref(tms), C.byref(fl))
             if n.value:
                 steps[str(rows)] = {"launches_per_plan": n.value // 4, "us_per_launch": round(tms.value / n.value * 1e3, 2),
                                     "tflops_algorithmic": round(fl.value / tms.value / 1e9, 2)}

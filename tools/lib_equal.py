@@ -1,8 +1,11 @@
-"""Do two builds of the library compute the same? A fixed, seeded list of small eager calls through every planning
+"""Do two builds of the library, or two trees of the Python layer, compute the same? A fixed, seeded list of small eager calls through every planning
 entry point (TOLD on every kernel path, every instance family of the wide kernels, iCEM, the DSSM planners), once
 per library in a fresh process; every output is compared bitwise. Needs a GPU.
     python -m tdmpc_amd.build --variant parent        # in a checkout of the other commit; copy the .so next to ours
     python tools/lib_equal.py tdmpc_amd/libtdmpc_hip_parent.so tdmpc_amd/libtdmpc_hip.so [OUT_DIR]
+Or two source trees on one library: in each tree, `python tools/lib_equal.py --child OUT.npz` (with TDMPC_LIB_PATH set
+to the one library), then
+    python tools/lib_equal.py --compare A.npz B.npz [ARRAY_COUNT]
 """
 import os
 import subprocess
@@ -89,11 +92,12 @@ def child(out):
     sd, (obs,) = synthetic_state_dict(cfg, 31, enc_norm=True), rand(4, (3, cfg.obs_shape[0]))
     for path in ("auto", "layered", "split", "chain_x6"):
         agent = made(TdICEM(cfg, max_batch=3, rng="device", path=path), sd)
+        pl = agent.planner
         for k, (B, t0) in enumerate(((1, True), (1, False), (3, False))):   # cold, warm with elite reuse, a batch
             torch.manual_seed(20 + k)
             tr = {}
             a, _ = agent._plan_envs(obs[:B], False, STEP, t0, None, tr)
-            put(f"icem/{path}/{k}", a, agent.metrics[:B], agent.elites, agent.prev_mean_flat, *tr.values())
+            put(f"icem/{path}/{k}", a, pl.metrics[:B], pl.elites, pl.prev_mean_flat, *tr.values())
     for task in ("humanoid", "cheetah"):
         cfg = make_cfg(task, hidden_dim=128, norm_cell=True, plan2expl=False, warmup_len=0,
                        regularization_schedule="0.5", **SMALL)
@@ -118,14 +122,27 @@ def child(out):
             torch.manual_seed(40 + k)
             tr = {}
             a, h, _ = icem.plan_batch(obs[:B], h0[:B], step=STEP, t0=t0, trace=tr)
-            put(f"{tag}/icem{k}", a, h, icem.elites, icem.planner.prev_mean_flat, *tr.values())
+            put(f"{tag}/icem{k}", a, h, icem.planner.elites, icem.planner.prev_mean_flat, *tr.values())
     torch.cuda.synchronize()
     np.savez(out, **res)
+
+
+def compare(fa, fb, count=None):
+    """Exit status 0 when the two dumps hold the same arrays (and `count` of them, when given), bitwise."""
+    a, b = np.load(fa), np.load(fb)
+    bad = sorted(set(a.files) ^ set(b.files)) + [   # bitwise: equal shapes and bytes (so NaN equals the same NaN)
+        k for k in a.files if k in b.files and (a[k].shape != b[k].shape or a[k].tobytes() != b[k].tobytes())]
+    if count is not None and len(a.files) != count:
+        bad.append(f"{len(a.files)} arrays, not {count}")
+    print(f"{len(a.files)} arrays, differing: {bad}" if bad else f"{len(a.files)} arrays equal")
+    return 1 if bad else 0
 
 
 if __name__ == "__main__":
     if sys.argv[1] == "--child":
         sys.exit(child(sys.argv[2]))
+    if sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3], int(sys.argv[4]) if len(sys.argv) > 4 else None))
     out = sys.argv[3] if len(sys.argv) > 3 else tempfile.mkdtemp(prefix="lib_equal_")
     os.makedirs(out, exist_ok=True)
     files = [os.path.join(out, f"lib{i}.npz") for i in (0, 1)]
@@ -134,8 +151,4 @@ if __name__ == "__main__":
                             env=dict(os.environ, TDMPC_LIB_PATH=os.path.abspath(lib)), cwd=REPO).returncode
         if rc:
             sys.exit(f"{lib}: exit status {rc}")
-    a, b = (np.load(f) for f in files)
-    bad = sorted(set(a.files) ^ set(b.files)) + [   # bitwise: equal shapes and bytes (so NaN equals the same NaN)
-        k for k in a.files if k in b.files and (a[k].shape != b[k].shape or a[k].tobytes() != b[k].tobytes())]
-    print(f"{len(a.files)} arrays, differing: {bad}" if bad else f"{len(a.files)} arrays equal")
-    sys.exit(1 if bad else 0)
+    sys.exit(compare(*files))
