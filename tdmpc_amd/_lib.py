@@ -33,8 +33,13 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_drnn_version", "tdmpc_drnn_sizes_for", "tdmpc_drnn_num_param_tensors", "tdmpc_drnn_pack_weights",
             "tdmpc_drnn_debug_pack_check", "tdmpc_drnn_next", "tdmpc_drnn_estimate_value", "tdmpc_drnn_pi_rollout", "tdmpc_drnn_plan",
             "tdmpc_drnn_profile_begin", "tdmpc_drnn_profile_end",
-            "tdmpc_drnn_icem_sizes_for", "tdmpc_drnn_plan_icem", "tdmpc_drnn_colored_noise")
+            "tdmpc_drnn_icem_sizes_for", "tdmpc_drnn_plan_icem", "tdmpc_drnn_colored_noise",
+            # include/tdmpc_drnn_learner.h
+            "tdmpc_drnn_train_version", "tdmpc_drnn_train_sizes_for", "tdmpc_drnn_next_fwd", "tdmpc_drnn_next_bwd",
+            "tdmpc_drnn_simloss_fwd", "tdmpc_drnn_simloss_bwd")
 DRNN_VERSION = 2
+DRNN_TRAIN_VERSION = 1
+DT_NEXT_TENSORS, DT_LOSS_TENSORS, DT_MAX_ROWS = 22, 8, 4096   # include/tdmpc_drnn_learner.h
 NOISE_MAX_JOBS, NOISE_MAX_SPECTRA = 17, 4
 
 
@@ -149,6 +154,10 @@ class LgGsrc(C.Structure):      # tdmpc_lg_gsrc
                [(n, C.c_int32) for n in ("rows", "cols", "ld", "nslices")]
 
 
+class DrnnTrainSizes(C.Structure):   # tdmpc_drnn_train_sizes (include/tdmpc_drnn_learner.h)
+    _fields_ = [(n, C.c_size_t) for n in ("next_saved_floats", "loss_saved_floats", "workspace_floats")]
+
+
 class Sizes(C.Structure):
     _fields_ = [("packed_weight_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t),
                 ("noise_floats_per_env", C.c_size_t)]
@@ -231,6 +240,12 @@ def lib():
     L.tdmpc_drnn_colored_noise.argtypes = [C.POINTER(ColoredNoiseParams), vp, sz, vp, sz, vp]
     L.tdmpc_drnn_profile_begin.argtypes = [i32, i32]
     L.tdmpc_drnn_profile_end.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    pv = C.POINTER(vp)
+    L.tdmpc_drnn_train_sizes_for.argtypes = [dd, i32, C.POINTER(DrnnTrainSizes)]
+    L.tdmpc_drnn_next_fwd.argtypes = [dd, pv, i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, sz, vp]
+    L.tdmpc_drnn_next_bwd.argtypes = [dd, pv, i32, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, pv, vp, sz, vp]
+    L.tdmpc_drnn_simloss_fwd.argtypes = [dd, pv, i32, vp, vp, i32, vp, vp, sz, vp, sz, vp]
+    L.tdmpc_drnn_simloss_bwd.argtypes = [dd, pv, i32, vp, vp, i32, vp, sz, vp, vp, pv, vp, sz, vp]
     for name in EXPORTED:
         if not hasattr(L, name) and not (name.startswith("tdmpc_debug_") and os.environ.get("TDMPC_LIB_PATH")):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")

@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, "csrc", "tdmpc_kernels.hip"), os.path.join(HERE, "csrc", "replay_kernels.hip"),
         os.path.join(HERE, "csrc", "learner_conv.hip"),
-        os.path.join(HERE, "csrc", "learner_kernels.hip"), os.path.join(HERE, "csrc", "learner_engine.hip")]
+        os.path.join(HERE, "csrc", "learner_kernels.hip"), os.path.join(HERE, "csrc", "learner_engine.hip"),
+        os.path.join(HERE, "csrc", "drnn_learner.hip")]
 OUT = os.path.join(HERE, "libtdmpc_hip.so")
 ARCH = os.environ.get("TDMPC_OFFLOAD_ARCH", "gfx950")
 
@@ -29,7 +30,8 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
     """The library (every source compiled in parallel, then linked); a variant (-DNAME defines, diagnostics or an A/B
     of a kernel knob) goes to libtdmpc_hip_<variant>.so, loaded with TDMPC_LIB_PATH."""
     deps = SRCS + [os.path.join(HERE, "csrc", f) for f in ("plan1.inc", "wide_ring.inc", "wide_step.inc", "wide_heads.inc", "drnn.inc", "pack.inc")] + \
-        [os.path.join(REPO, "include", h) for h in ("tdmpc_hip.h", "tdmpc_replay.h", "tdmpc_learner.h", "tdmpc_drnn.h")]
+        [os.path.join(REPO, "include", h) for h in ("tdmpc_hip.h", "tdmpc_replay.h", "tdmpc_learner.h", "tdmpc_drnn.h",
+                                                   "tdmpc_drnn_learner.h")]
     out = OUT if not variant else os.path.join(HERE, f"libtdmpc_hip_{variant}.so")
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
         return out

@@ -1,0 +1,873 @@
+// drnn_learner.hip -- the DSSM learner's two differentiable parts for MI355X (gfx950): DSSM.next in train mode and
+// similarity_loss, forward and backward (include/tdmpc_drnn_learner.h).
+//
+// Reference: DSSM.next (tdmpc_similarity_drnn.py:57-60) = DGruDyna (models/gru_dyna.py:11-29: NormGRUCell,
+// models/rnns.py:8-29, then prior_mlp = helper.mlp_norm with BatchNorm1d) + the reward MLP, under model.train();
+// similarity_loss (tdmpc_similarity_drnn.py / tdmpc_icem_similarity_drnn.py: _predictor, F.normalize, 2 - 2 cos).
+//
+// The products are grouped tdmpc_lg_gemm launches (learner_engine.hip) on the exact f32 MFMA, reading the model's own
+// fp32 parameter tensors: the two gate products ([z | a] as two K segments of one job), prior_mlp.0 / _reward.0,
+// prior_mlp.3 / _reward.2, their dX, and every dW with the bias as the ones column. The kernels here cover the rest:
+//   * dt_gate_fwd / dt_gate_bwd: one wave per row of Hd <= 256 features -- three LayerNorms (eps 1e-3), sigmoid,
+//     sigmoid, tanh, the blend; the backward also writes the LayerNorm-affine gradients as per-workgroup partials;
+//   * dt_bn_stat / dt_bn_fwd / dt_bn_bwd_stat / dt_bn_bwd: BatchNorm1d on batch statistics over 512 columns (+ ELU):
+//     per 128-row chunk a (mean, M2) or (sum dY, sum dY xhat) partial per column, combined in chunk order;
+//   * dt_cos_fwd / dt_cos_bwd: F.normalize on both sides and 2 - 2 cos, one wave per row;
+//   * dt_finish (column sums of partials in order), dt_unpack (a [out][in + 1] weight-gradient product -> dW, db).
+// Every reduction runs in a fixed order: wave butterflies, LDS sums over waves in wave order, partials in index order.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "../../include/tdmpc_drnn_learner.h"
+#include "../../include/tdmpc_learner.h"
+
+namespace tdmpc_internal {
+void set_error(const char* msg);
+}
+
+namespace {
+
+constexpr int M = 512;          // mlp_dim
+constexpr int CHUNK = 128;      // rows per BatchNorm partial
+constexpr int GROWS = 32;       // rows per workgroup of dt_gate_bwd (one LayerNorm-affine partial each)
+constexpr float LN_EPS = 1e-3f, BN_EPS = 1e-5f, BN_MOM = 0.1f, NORM_EPS = 1e-12f;
+
+// tensor table indices (tdmpc_drnn_learner.h)
+enum { P0W = 0, P0B, P1G, P1B, P1RM, P1RV, P3W, P3B, WIH, WHH, LRG, LRB, LUG, LUB, LNG, LNB, R0W, R0B, R2W, R2B, R4W,
+       R4B };
+
+__device__ __forceinline__ float wsum(float v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : expm1f(x); }
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+
+// Row LayerNorm over Hd features held 4 per lane (feature lane + 64 i, valid where ok[i]): xhat and 1 / std.
+__device__ __forceinline__ float ln_row(const float (&x)[4], const bool (&ok)[4], int Hd, float (&xh)[4]) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s += ok[i] ? x[i] : 0.f;
+    const float mean = wsum(s) / (float)Hd;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q += ok[i] ? (x[i] - mean) * (x[i] - mean) : 0.f;
+    const float rstd = 1.f / sqrtf(wsum(q) / (float)Hd + LN_EPS);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xh[i] = (x[i] - mean) * rstd;
+    return rstd;
+}
+
+struct GateArgs {
+    const float* gi; const float* gh; const float* h;      // [R,3Hd], [R,3Hd], [R,Hd]
+    const float* g[3]; const float* b[3];                  // ln_reset / ln_update / ln_newval
+    float* gate; float* lnx; float* lnr; float* hn; float* h_out;
+    // backward
+    const float* dhn; float* dgi; float* dgh; float* dhd; float* part;
+    int rows, Hd;
+};
+
+// NormGRUCell.forward (models/rnns.py:19-29), one wave per row, four rows per workgroup.
+__global__ void __launch_bounds__(256) dt_gate_fwd(const GateArgs a) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6), Hd = a.Hd;
+    if (row >= a.rows) return;
+    const size_t r3 = (size_t)row * 3 * Hd, r1 = (size_t)row * Hd;
+    bool ok[4];
+    float sr[4], su[4], ghn[4], gin[4], hp[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        ok[i] = c < Hd;
+        const int cc = ok[i] ? c : 0;
+        sr[i] = a.gi[r3 + cc] + a.gh[r3 + cc];
+        su[i] = a.gi[r3 + Hd + cc] + a.gh[r3 + Hd + cc];
+        gin[i] = a.gi[r3 + 2 * Hd + cc];
+        ghn[i] = a.gh[r3 + 2 * Hd + cc];
+        hp[i] = a.h[r1 + cc];
+    }
+    float xr[4], xu[4], xn[4], rs[4], sn[4];
+    const float rstd_r = ln_row(sr, ok, Hd, xr);
+    const float rstd_u = ln_row(su, ok, Hd, xu);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int cc = ok[i] ? lane + 64 * i : 0;
+        rs[i] = sigmoid_f(xr[i] * a.g[0][cc] + a.b[0][cc]);
+        sn[i] = gin[i] + rs[i] * ghn[i];
+    }
+    const float rstd_n = ln_row(sn, ok, Hd, xn);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        if (!ok[i]) continue;
+        const float u = sigmoid_f(xu[i] * a.g[1][c] + a.b[1][c]);
+        const float n = tanhf(xn[i] * a.g[2][c] + a.b[2][c]);
+        const float hn = u * n + (1.f - u) * hp[i];
+        a.gate[r3 + c] = rs[i];
+        a.gate[r3 + Hd + c] = u;
+        a.gate[r3 + 2 * Hd + c] = n;
+        a.lnx[r3 + c] = xr[i];
+        a.lnx[r3 + Hd + c] = xu[i];
+        a.lnx[r3 + 2 * Hd + c] = xn[i];
+        a.hn[r1 + c] = hn;
+        a.h_out[r1 + c] = hn;
+    }
+    if (lane < 4) a.lnr[(size_t)row * 4 + lane] = lane == 0 ? rstd_r : lane == 1 ? rstd_u : lane == 2 ? rstd_n : 0.f;
+}
+
+// LayerNorm backward of one row: dy (w.r.t. the affine output) -> dx (w.r.t. the input); dg / db accumulate the affine
+// gradients of this lane's features.
+__device__ __forceinline__ void ln_row_bwd(const float (&dy)[4], const float (&xh)[4], const float (&g)[4],
+                                           const bool (&ok)[4], float rstd, int Hd, float (&dx)[4], float (&dg)[4],
+                                           float (&db)[4]) {
+    float s1 = 0.f, s2 = 0.f, d[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        d[i] = ok[i] ? dy[i] * g[i] : 0.f;
+        s1 += d[i];
+        s2 += ok[i] ? d[i] * xh[i] : 0.f;
+        dg[i] += ok[i] ? dy[i] * xh[i] : 0.f;
+        db[i] += ok[i] ? dy[i] : 0.f;
+    }
+    const float m1 = wsum(s1) / (float)Hd, m2 = wsum(s2) / (float)Hd;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dx[i] = rstd * (d[i] - m1 - xh[i] * m2);
+}
+
+// Backward of the cell: dhn [R,Hd] = dL/dh' -> dgi, dgh [R,3Hd] (w.r.t. weight_ih / weight_hh's outputs), dhd [R,Hd]
+// (the direct (1 - update) path to h) and part [nwg][6][Hd]: the workgroup's sums over its GROWS rows of the three
+// LayerNorms' (dweight, dbias). Wave w takes rows base + w, base + w + 4, ...; the four waves add in wave order.
+__global__ void __launch_bounds__(256) dt_gate_bwd(const GateArgs a) {
+    __shared__ float red[4][6][256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, Hd = a.Hd;
+    bool ok[4];
+    float g[3][4], acc[6][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        ok[i] = c < Hd;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[k][i] = a.g[k][ok[i] ? c : 0];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc[k][i] = 0.f;
+    }
+    for (int q = wave; q < GROWS; q += 4) {
+        const int row = blockIdx.x * GROWS + q;
+        if (row >= a.rows) break;   // (wave-uniform)
+        const size_t r3 = (size_t)row * 3 * Hd, r1 = (size_t)row * Hd;
+        const float rstd_r = a.lnr[(size_t)row * 4], rstd_u = a.lnr[(size_t)row * 4 + 1],
+                    rstd_n = a.lnr[(size_t)row * 4 + 2];
+        float r[4], u[4], n[4], xr[4], xu[4], xn[4], ghn[4], dH[4], hp[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int cc = ok[i] ? lane + 64 * i : 0;
+            r[i] = a.gate[r3 + cc];
+            u[i] = a.gate[r3 + Hd + cc];
+            n[i] = a.gate[r3 + 2 * Hd + cc];
+            xr[i] = a.lnx[r3 + cc];
+            xu[i] = a.lnx[r3 + Hd + cc];
+            xn[i] = a.lnx[r3 + 2 * Hd + cc];
+            ghn[i] = a.gh[r3 + 2 * Hd + cc];
+            dH[i] = a.dhn[r1 + cc];
+            hp[i] = a.h[r1 + cc];
+        }
+        float dyn[4], dyu[4], dyr[4], dsn[4], dsu[4], dsr[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            dyn[i] = dH[i] * u[i] * (1.f - n[i] * n[i]);
+            dyu[i] = dH[i] * (n[i] - hp[i]) * u[i] * (1.f - u[i]);
+        }
+        ln_row_bwd(dyn, xn, g[2], ok, rstd_n, Hd, dsn, acc[4], acc[5]);
+        ln_row_bwd(dyu, xu, g[1], ok, rstd_u, Hd, dsu, acc[2], acc[3]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dyr[i] = dsn[i] * ghn[i] * r[i] * (1.f - r[i]);
+        ln_row_bwd(dyr, xr, g[0], ok, rstd_r, Hd, dsr, acc[0], acc[1]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = lane + 64 * i;
+            if (!ok[i]) continue;
+            a.dgi[r3 + c] = dsr[i];
+            a.dgh[r3 + c] = dsr[i];
+            a.dgi[r3 + Hd + c] = dsu[i];
+            a.dgh[r3 + Hd + c] = dsu[i];
+            a.dgi[r3 + 2 * Hd + c] = dsn[i];
+            a.dgh[r3 + 2 * Hd + c] = dsn[i] * r[i];
+            a.dhd[r1 + c] = dH[i] * (1.f - u[i]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[wave][k][lane + 64 * i] = acc[k][i];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 6 * Hd; e += 256) {
+        const int k = e / Hd, c = e % Hd;
+        a.part[((size_t)blockIdx.x * 6 + k) * Hd + c] = ((red[0][k][c] + red[1][k][c]) + red[2][k][c]) + red[3][k][c];
+    }
+}
+
+// out[k][c] = sum over p < nparts (in order) of part[p][k][c], k < nvec, c < C; out[k] are separate tensors.
+struct FinishArgs {
+    const float* part; float* out[8];
+    int nparts, nvec, C;
+};
+__global__ void __launch_bounds__(256) dt_finish(const FinishArgs a) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.nvec * a.C) return;
+    float s = 0.f;
+    for (int p = 0; p < a.nparts; ++p) s += a.part[(size_t)p * a.nvec * a.C + e];
+    a.out[e / a.C][e % a.C] = s;
+}
+
+// ---- BatchNorm1d on batch statistics over C columns (+ ELU). Geometry of all four kernels: grid (C / 64, chunks),
+// 256 threads = 64 columns x 4 row phases; thread (tx, ty) takes rows chunk * CHUNK + ty, + 4, ... of column
+// 64 blockIdx.x + tx, and the four row phases add through LDS in phase order.
+struct BnArgs {
+    const float* x;          // fwd: the Linear's output [R,C]; bwd: dL/d(ELU output) [R,C]
+    const float* g; const float* b; float* rmean; float* rvar;
+    float* xhat; float* rstd; float* e;     // saved [R,C], [C], [R,C] (bwd reads them)
+    float* part;             // [chunks][2][C]
+    float* dx; float* dg; float* db;        // bwd outputs: [R,C] (may be x), [C], [C]
+    int rows, C;
+};
+
+__device__ __forceinline__ float phase_sum(float (&red)[4][64], float v, int tx, int ty) {
+    __syncthreads();
+    red[ty][tx] = v;
+    __syncthreads();
+    return ((red[0][tx] + red[1][tx]) + red[2][tx]) + red[3][tx];
+}
+
+// part[chunk][0][c] = the chunk's column mean, part[chunk][1][c] = its sum of squared deviations from that mean.
+__global__ void __launch_bounds__(256) dt_bn_stat(const BnArgs a) {
+    __shared__ float red[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, c = blockIdx.x * 64 + tx, C = a.C;
+    const int r0 = blockIdx.y * CHUNK, r1 = min(a.rows, r0 + CHUNK);
+    float s = 0.f;
+    for (int r = r0 + ty; r < r1; r += 4) s += a.x[(size_t)r * C + c];
+    const float mean = phase_sum(red, s, tx, ty) / (float)(r1 - r0);
+    float q = 0.f;
+    for (int r = r0 + ty; r < r1; r += 4) {
+        const float d = a.x[(size_t)r * C + c] - mean;
+        q += d * d;
+    }
+    const float m2 = phase_sum(red, q, tx, ty);
+    if (ty == 0) {
+        a.part[((size_t)blockIdx.y * 2) * C + c] = mean;
+        a.part[((size_t)blockIdx.y * 2 + 1) * C + c] = m2;
+    }
+}
+
+// The chunks' (mean, M2) combined in chunk order (Chan et al.'s pairwise update): the column's mean and M2 over R rows.
+__device__ __forceinline__ void bn_combine(const float* part, int rows, int C, int c, float& mean, float& m2) {
+    float n = 0.f;
+    mean = 0.f;
+    m2 = 0.f;
+    for (int p = 0; p * CHUNK < rows; ++p) {
+        const float nb = (float)(min(rows, (p + 1) * CHUNK) - p * CHUNK);
+        const float mb = part[((size_t)p * 2) * C + c], qb = part[((size_t)p * 2 + 1) * C + c];
+        const float d = mb - mean, nt = n + nb;
+        mean += d * (nb / nt);
+        m2 += qb + d * d * (n * nb / nt);
+        n = nt;
+    }
+}
+
+// xhat = (x - mean) / sqrt(biased var + eps), e = ELU(g xhat + b); chunk 0 also writes the columns' 1 / std and moves
+// the running statistics (momentum 0.1, the unbiased variance M2 / (R - 1), as nn.BatchNorm1d).
+__global__ void __launch_bounds__(256) dt_bn_fwd(const BnArgs a) {
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, c = blockIdx.x * 64 + tx, C = a.C;
+    const int r0 = blockIdx.y * CHUNK, r1 = min(a.rows, r0 + CHUNK);
+    float mean, m2;
+    bn_combine(a.part, a.rows, C, c, mean, m2);
+    const float rstd = 1.f / sqrtf(m2 / (float)a.rows + BN_EPS);
+    const float g = a.g[c], b = a.b[c];
+    for (int r = r0 + ty; r < r1; r += 4) {
+        const float xh = (a.x[(size_t)r * C + c] - mean) * rstd;
+        a.xhat[(size_t)r * C + c] = xh;
+        a.e[(size_t)r * C + c] = elu_f(xh * g + b);
+    }
+    if (blockIdx.y == 0 && ty == 0) {
+        a.rstd[c] = rstd;
+        a.rmean[c] = (1.f - BN_MOM) * a.rmean[c] + BN_MOM * mean;
+        a.rvar[c] = (1.f - BN_MOM) * a.rvar[c] + BN_MOM * (m2 / (float)(a.rows - 1));
+    }
+}
+
+// dY = x ELU'(e) (the gradient at the BatchNorm's output); part[chunk][0][c] = sum dY, [1] = sum dY xhat.
+__global__ void __launch_bounds__(256) dt_bn_bwd_stat(const BnArgs a) {
+    __shared__ float red[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, c = blockIdx.x * 64 + tx, C = a.C;
+    const int r0 = blockIdx.y * CHUNK, r1 = min(a.rows, r0 + CHUNK);
+    float s1 = 0.f, s2 = 0.f;
+    for (int r = r0 + ty; r < r1; r += 4) {
+        const size_t i = (size_t)r * C + c;
+        const float e = a.e[i], dy = a.x[i] * (e > 0.f ? 1.f : e + 1.f);
+        s1 += dy;
+        s2 += dy * a.xhat[i];
+    }
+    s1 = phase_sum(red, s1, tx, ty);
+    s2 = phase_sum(red, s2, tx, ty);
+    if (ty == 0) {
+        a.part[((size_t)blockIdx.y * 2) * C + c] = s1;
+        a.part[((size_t)blockIdx.y * 2 + 1) * C + c] = s2;
+    }
+}
+
+// dx = g rstd (dY - mean(dY) - xhat mean(dY xhat)); chunk 0 also writes dg = sum dY xhat and db = sum dY.
+__global__ void __launch_bounds__(256) dt_bn_bwd(const BnArgs a) {
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, c = blockIdx.x * 64 + tx, C = a.C;
+    const int r0 = blockIdx.y * CHUNK, r1 = min(a.rows, r0 + CHUNK);
+    float s1 = 0.f, s2 = 0.f;
+    for (int p = 0; p * CHUNK < a.rows; ++p) {
+        s1 += a.part[((size_t)p * 2) * C + c];
+        s2 += a.part[((size_t)p * 2 + 1) * C + c];
+    }
+    const float k = a.g[c] * a.rstd[c], m1 = s1 / (float)a.rows, m2 = s2 / (float)a.rows;
+    for (int r = r0 + ty; r < r1; r += 4) {
+        const size_t i = (size_t)r * C + c;
+        const float e = a.e[i], dy = a.x[i] * (e > 0.f ? 1.f : e + 1.f);
+        a.dx[i] = k * (dy - m1 - a.xhat[i] * m2);
+    }
+    if (blockIdx.y == 0 && ty == 0) {
+        a.dg[c] = s2;
+        a.db[c] = s1;
+    }
+}
+
+// ---- 2 - 2 <normalize(p), normalize(k)> per row of L <= 256 features, one wave per row.
+__device__ __forceinline__ void cos_row(const float* p, const float* k, int L, int lane, float (&pv)[4], float (&kv)[4],
+                                        float& pp, float& kk, float& pk) {
+    float a = 0.f, b = 0.f, c = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = lane + 64 * i;
+        pv[i] = j < L ? p[j] : 0.f;
+        kv[i] = j < L ? k[j] : 0.f;
+        a += pv[i] * pv[i];
+        b += kv[i] * kv[i];
+        c += pv[i] * kv[i];
+    }
+    pp = wsum(a);
+    kk = wsum(b);
+    pk = wsum(c);
+}
+
+__global__ void __launch_bounds__(256) dt_cos_fwd(const float* pred, const float* keys, float* loss, int rows, int L) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float pv[4], kv[4], pp, kk, pk;
+    cos_row(pred + (size_t)row * L, keys + (size_t)row * L, L, lane, pv, kv, pp, kk, pk);
+    const float np = fmaxf(sqrtf(pp), NORM_EPS), nk = fmaxf(sqrtf(kk), NORM_EPS);
+    if (lane == 0) loss[row] = 2.f - 2.f * (pk / (np * nk));
+}
+
+// dpred = -2 dloss (khat - phat <phat, khat>) / ||p|| (a row with ||p|| below the clamp: -2 dloss khat / 1e-12).
+__global__ void __launch_bounds__(256) dt_cos_bwd(const float* pred, const float* keys, const float* dloss,
+                                                  float* dpred, int rows, int L) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float pv[4], kv[4], pp, kk, pk;
+    cos_row(pred + (size_t)row * L, keys + (size_t)row * L, L, lane, pv, kv, pp, kk, pk);
+    const float n0 = sqrtf(pp), np = fmaxf(n0, NORM_EPS), nk = fmaxf(sqrtf(kk), NORM_EPS);
+    const float cs = n0 >= NORM_EPS ? pk / (np * nk) : 0.f, s = -2.f * dloss[row] / np;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = lane + 64 * i;
+        if (j < L) dpred[(size_t)row * L + j] = s * (kv[i] / nk - (pv[i] / np) * cs);
+    }
+}
+
+// A weight-gradient product with the ones column, src [out][in + 1] -> dw [out][in], db [out].
+struct UnpackJob { const float* src; float* dw; float* db; int out, in; };
+struct UnpackArgs { UnpackJob job[8]; };
+__global__ void __launch_bounds__(256) dt_unpack(const UnpackArgs a) {
+    const UnpackJob& j = a.job[blockIdx.y];
+    const int n = j.out * (j.in + 1);
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+        const int r = e / (j.in + 1), c = e % (j.in + 1);
+        const float v = j.src[e];
+        if (c < j.in) j.dw[(size_t)r * j.in + c] = v;
+        else j.db[r] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+
+int bad(const char* fmt, long a = 0, long b = 0) {
+    char msg[256];
+    snprintf(msg, sizeof msg, fmt, a, b);
+    tdmpc_internal::set_error(msg);
+    return TDMPC_E_DIMS;
+}
+
+int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    char msg[256];
+    snprintf(msg, sizeof msg, "drnn_learner %s: %s", what, hipGetErrorString(e));
+    tdmpc_internal::set_error(msg);
+    return TDMPC_E_HIP;
+}
+
+struct Shape { int L, A, Hd, R; };
+
+int check_shape(const tdmpc_drnn_dims* d, int rows, Shape& s) {
+    if (!d) return bad("drnn_learner: dims is null");
+    const tdmpc_dims& b = d->base;
+    if (b.modality != 0) return bad("drnn_learner: state observations only (modality %ld)", b.modality);
+    if (b.mlp_dim != M) return bad("drnn_learner: mlp_dim %ld is not supported (512 only)", b.mlp_dim);
+    if (d->hidden_dim < 32 || d->hidden_dim > 256 || d->hidden_dim % 32)
+        return bad("drnn_learner: hidden_dim %ld is not a multiple of 32 in [32, 256]", d->hidden_dim);
+    if (b.latent_dim < 1 || b.latent_dim > 256) return bad("drnn_learner: latent_dim %ld is not in [1, 256]", b.latent_dim);
+    if (b.action_dim < 1) return bad("drnn_learner: action_dim %ld", b.action_dim);
+    if (rows < 2 || rows > TDMPC_DT_MAX_ROWS)
+        return bad("drnn_learner: rows %ld is not in [2, %ld] (train-mode BatchNorm needs two rows)", rows,
+                   TDMPC_DT_MAX_ROWS);
+    s = Shape{b.latent_dim, b.action_dim, d->hidden_dim, rows};
+    return 0;
+}
+
+// A bump allocator over a float buffer (every region a multiple of 4 floats: 16-B aligned operands for the GEMM).
+struct Bump {
+    float* base; size_t off = 0;
+    explicit Bump(float* b) : base(b) {}
+    float* take(size_t n) {
+        float* p = base ? base + off : nullptr;
+        off += (n + 3) & ~(size_t)3;
+        return p;
+    }
+};
+
+int chunks(int R) { return (R + CHUNK - 1) / CHUNK; }
+int gate_wgs(int R) { return (R + GROWS - 1) / GROWS; }
+
+struct NextSaved { float *gh, *gate, *lnx, *lnr, *hn, *bnx, *bnr, *e, *q1, *q2; size_t total; };
+NextSaved next_saved(const Shape& s, float* base) {
+    Bump b(base);
+    NextSaved v;
+    const size_t R = s.R;
+    v.gh = b.take(R * 3 * s.Hd);
+    v.gate = b.take(R * 3 * s.Hd);
+    v.lnx = b.take(R * 3 * s.Hd);
+    v.lnr = b.take(R * 4);
+    v.hn = b.take(R * s.Hd);
+    v.bnx = b.take(R * M);
+    v.bnr = b.take(M);
+    v.e = b.take(R * M);
+    v.q1 = b.take(R * M);
+    v.q2 = b.take(R * M);
+    v.total = b.off;
+    return v;
+}
+
+struct LossSaved { float *bnx, *bnr, *e, *pred; size_t total; };
+LossSaved loss_saved(const Shape& s, float* base) {
+    Bump b(base);
+    LossSaved v;
+    const size_t R = s.R;
+    v.bnx = b.take(R * M);
+    v.bnr = b.take(M);
+    v.e = b.take(R * M);
+    v.pred = b.take(R * s.L);
+    v.total = b.off;
+    return v;
+}
+
+struct NextFwdWs { float *gi, *p1, *part; size_t total; };
+NextFwdWs next_fwd_ws(const Shape& s, float* base) {
+    Bump b(base);
+    NextFwdWs v;
+    v.gi = b.take((size_t)s.R * 3 * s.Hd);
+    v.p1 = b.take((size_t)s.R * M);
+    v.part = b.take((size_t)chunks(s.R) * 2 * M);
+    v.total = b.off;
+    return v;
+}
+
+struct NextBwdWs {
+    float *zz, *zr, *dq2, *de, *dq1, *dhn, *dgi, *dgh, *dhd, *lnpart, *bnpart, *wp0, *wp3, *wr0, *wr2, *wr4;
+    size_t total;
+};
+NextBwdWs next_bwd_ws(const Shape& s, float* base) {
+    Bump b(base);
+    NextBwdWs v;
+    const size_t R = s.R;
+    v.zz = b.take(R * s.L);
+    v.zr = b.take(R);
+    v.dq2 = b.take(R * M);
+    v.de = b.take(R * M);
+    v.dq1 = b.take(R * M);
+    v.dhn = b.take(R * s.Hd);
+    v.dgi = b.take(R * 3 * s.Hd);
+    v.dgh = b.take(R * 3 * s.Hd);
+    v.dhd = b.take(R * s.Hd);
+    v.lnpart = b.take((size_t)gate_wgs(s.R) * 6 * s.Hd);
+    v.bnpart = b.take((size_t)chunks(s.R) * 2 * M);
+    v.wp0 = b.take((size_t)M * (s.Hd + 1));
+    v.wp3 = b.take((size_t)s.L * (M + 1));
+    v.wr0 = b.take((size_t)M * (s.Hd + 1));
+    v.wr2 = b.take((size_t)M * (M + 1));
+    v.wr4 = b.take(M + 1);
+    v.total = b.off;
+    return v;
+}
+
+struct LossFwdWs { float *p1, *part; size_t total; };
+LossFwdWs loss_fwd_ws(const Shape& s, float* base) {
+    Bump b(base);
+    LossFwdWs v;
+    v.p1 = b.take((size_t)s.R * M);
+    v.part = b.take((size_t)chunks(s.R) * 2 * M);
+    v.total = b.off;
+    return v;
+}
+
+struct LossBwdWs { float *dpred, *de, *part, *w3, *w0; size_t total; };
+LossBwdWs loss_bwd_ws(const Shape& s, float* base) {
+    Bump b(base);
+    LossBwdWs v;
+    v.dpred = b.take((size_t)s.R * s.L);
+    v.de = b.take((size_t)s.R * M);
+    v.part = b.take((size_t)chunks(s.R) * 2 * M);
+    v.w3 = b.take((size_t)s.L * (M + 1));
+    v.w0 = b.take((size_t)M * (s.L + 1));
+    v.total = b.off;
+    return v;
+}
+
+// ---- tdmpc_lg_gemm jobs
+tdmpc_lg_seg seg(const float* a, int lda, const float* b, int ldb, int k, int amode, int bmode, int ones = -1) {
+    tdmpc_lg_seg s;
+    memset(&s, 0, sizeof s);
+    s.a = a; s.b = b; s.lda = lda; s.ldb = ldb; s.k = k; s.amode = amode; s.bmode = bmode; s.ones_col = ones;
+    return s;
+}
+
+tdmpc_lg_job job(int m, int n, float* c, int ldc, const tdmpc_lg_seg& s0) {
+    tdmpc_lg_job j;
+    memset(&j, 0, sizeof j);
+    j.seg[0] = s0;
+    j.nseg = 1; j.m = m; j.n = n; j.c = c; j.ldc = ldc; j.splits = 1; j.epi = TDMPC_LG_EPI_NONE;
+    return j;
+}
+
+// Y [R,N] = X [R,K] W [N,K]^T (+ bias)
+tdmpc_lg_job linear(int R, int N, int K, const float* x, const float* w, const float* bias, float* y) {
+    tdmpc_lg_job j = job(R, N, y, N, seg(x, K, w, K, K, 0, 0));
+    j.bias = bias;
+    return j;
+}
+// dX [R,K] = dY [R,N] W [N,K], columns [c0, c0 + n) of W (row stride ldw)
+tdmpc_lg_job dinput(int R, int n, int N, const float* dy, const float* w, int ldw, float* dx) {
+    return job(R, n, dx, n, seg(dy, N, w, ldw, N, 0, 1));
+}
+// dW [N,n] (row stride ldc) = dY [R,N]^T X [R,n]; ones: the bias column n (then ldc = n + 1 columns are written)
+tdmpc_lg_job dweight(int R, int N, int n, const float* dy, const float* x, float* dw, int ldc, bool ones) {
+    return job(N, ones ? n + 1 : n, dw, ldc, seg(dy, N, x, n, R, 1, 1, ones ? n : -1));
+}
+tdmpc_lg_job with_elu_bwd(tdmpc_lg_job j, const float* y) {
+    j.epi = TDMPC_LG_EPI_ELU_BWD;
+    j.aux = y;
+    j.ldaux = j.n;
+    return j;
+}
+
+// One grouped launch on the exact f32 MFMA: 64 x 64 register tiles once the largest job fills the chip with them.
+int gemm(const tdmpc_lg_job* jobs, int n, void* stream) {
+    long big = 0;
+    for (int q = 0; q < n; ++q) big = std::max(big, (long)((jobs[q].m + 63) / 64) * ((jobs[q].n + 63) / 64));
+    return tdmpc_lg_gemm(jobs, n, (big >= 256 ? 2 : 1) | TDMPC_LG_TILE_EXACT, stream);
+}
+
+int bn_forward(BnArgs a, hipStream_t st) {
+    const dim3 g(a.C / 64, chunks(a.rows));
+    hipLaunchKernelGGL(dt_bn_stat, g, dim3(256), 0, st, a);
+    if (int rc = launched("bn_stat")) return rc;
+    hipLaunchKernelGGL(dt_bn_fwd, g, dim3(256), 0, st, a);
+    return launched("bn_fwd");
+}
+
+int bn_backward(BnArgs a, hipStream_t st) {
+    const dim3 g(a.C / 64, chunks(a.rows));
+    hipLaunchKernelGGL(dt_bn_bwd_stat, g, dim3(256), 0, st, a);
+    if (int rc = launched("bn_bwd_stat")) return rc;
+    hipLaunchKernelGGL(dt_bn_bwd, g, dim3(256), 0, st, a);
+    return launched("bn_bwd");
+}
+
+int unpack(const UnpackArgs& u, int n, hipStream_t st) {
+    hipLaunchKernelGGL(dt_unpack, dim3(64, n), dim3(256), 0, st, u);
+    return launched("unpack");
+}
+
+int need(const void* p, const char* name) {
+    if (p) return 0;
+    char msg[128];
+    snprintf(msg, sizeof msg, "drnn_learner: %s is null", name);
+    tdmpc_internal::set_error(msg);
+    return TDMPC_E_DIMS;
+}
+
+int need_table(float* const* t, int n, int want, const char* name, bool stats) {
+    if (int rc = need(t, name)) return rc;
+    if (n != want) return bad("drnn_learner: %ld tensors given, %ld expected", n, want);
+    for (int i = 0; i < want; ++i)
+        if (!t[i] && (stats || (i != P1RM && i != P1RV))) return bad("drnn_learner: tensor %ld of a table is null", i);
+    return 0;
+}
+
+int size_err(const char* what, size_t have, size_t want) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "drnn_learner: %s holds %zu floats, %zu needed", what, have, want);
+    tdmpc_internal::set_error(msg);
+    return TDMPC_E_SIZE;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tdmpc_drnn_train_version(void) { return TDMPC_DRNN_TRAIN_VERSION; }
+
+int tdmpc_drnn_train_sizes_for(const tdmpc_drnn_dims* dims, int32_t rows, tdmpc_drnn_train_sizes* out) {
+    Shape s;
+    if (int rc = check_shape(dims, rows, s)) return rc;
+    if (int rc = need(out, "out")) return rc;
+    out->next_saved_floats = next_saved(s, nullptr).total;
+    out->loss_saved_floats = loss_saved(s, nullptr).total;
+    out->workspace_floats = std::max(std::max(next_fwd_ws(s, nullptr).total, next_bwd_ws(s, nullptr).total),
+                                     std::max(loss_fwd_ws(s, nullptr).total, loss_bwd_ws(s, nullptr).total));
+    return 0;
+}
+
+int tdmpc_drnn_next_fwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_tensors, const float* z,
+                        const float* a, const float* h, int32_t rows, float* z_out, float* h_out, float* r_out,
+                        float* saved, size_t saved_floats, float* workspace, size_t workspace_floats, void* stream) {
+    Shape s;
+    if (int rc = check_shape(dims, rows, s)) return rc;
+    if (int rc = need_table(T, n_tensors, TDMPC_DT_NEXT_TENSORS, "tensors", true)) return rc;
+    const void* ptrs[] = {z, a, h, z_out, h_out, r_out, saved, workspace};
+    const char* names[] = {"z", "a", "h", "z_out", "h_out", "r_out", "saved", "workspace"};
+    for (int i = 0; i < 8; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const NextSaved S = next_saved(s, saved);
+    const NextFwdWs W = next_fwd_ws(s, workspace);
+    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L, A = s.A, Hd = s.Hd;
+
+    tdmpc_lg_job j[2];
+    // the gate products: [z | a] weight_ih^T as two K segments, h weight_hh^T
+    j[0] = job(R, 3 * Hd, W.gi, 3 * Hd, seg(z, L, T[WIH], L + A, L, 0, 0));
+    j[0].seg[1] = seg(a, A, T[WIH] + L, L + A, A, 0, 0);
+    j[0].nseg = 2;
+    j[1] = linear(R, 3 * Hd, Hd, h, T[WHH], nullptr, S.gh);
+    if (int rc = gemm(j, 2, stream)) return rc;
+
+    GateArgs g;
+    memset(&g, 0, sizeof g);
+    g.gi = W.gi; g.gh = S.gh; g.h = h;
+    for (int k = 0; k < 3; ++k) { g.g[k] = T[LRG + 2 * k]; g.b[k] = T[LRB + 2 * k]; }
+    g.gate = S.gate; g.lnx = S.lnx; g.lnr = S.lnr; g.hn = S.hn; g.h_out = h_out;
+    g.rows = R; g.Hd = Hd;
+    hipLaunchKernelGGL(dt_gate_fwd, dim3((R + 3) / 4), dim3(256), 0, st, g);
+    if (int rc = launched("gate_fwd")) return rc;
+
+    j[0] = linear(R, M, Hd, S.hn, T[P0W], T[P0B], W.p1);
+    j[1] = linear(R, M, Hd, S.hn, T[R0W], T[R0B], S.q1);
+    j[1].epi = TDMPC_LG_EPI_ELU;
+    if (int rc = gemm(j, 2, stream)) return rc;
+
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.p1; b.g = T[P1G]; b.b = T[P1B]; b.rmean = T[P1RM]; b.rvar = T[P1RV];
+    b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part; b.rows = R; b.C = M;
+    if (int rc = bn_forward(b, st)) return rc;
+
+    j[0] = linear(R, L, M, S.e, T[P3W], T[P3B], z_out);
+    j[1] = linear(R, M, M, S.q1, T[R2W], T[R2B], S.q2);
+    j[1].epi = TDMPC_LG_EPI_ELU;
+    if (int rc = gemm(j, 2, stream)) return rc;
+
+    j[0] = linear(R, 1, M, S.q2, T[R4W], T[R4B], r_out);
+    return gemm(j, 1, stream);
+}
+
+int tdmpc_drnn_next_bwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_tensors, const float* z,
+                        const float* a, const float* h, int32_t rows, const float* saved, size_t saved_floats,
+                        const float* dz_out, const float* dh_out, const float* dr_out, float* dz, float* da, float* dh,
+                        float* const* G, float* workspace, size_t workspace_floats, void* stream) {
+    Shape s;
+    if (int rc = check_shape(dims, rows, s)) return rc;
+    if (int rc = need_table(T, n_tensors, TDMPC_DT_NEXT_TENSORS, "tensors", true)) return rc;
+    if (int rc = need_table(G, n_tensors, TDMPC_DT_NEXT_TENSORS, "grads", false)) return rc;
+    const void* ptrs[] = {z, a, h, saved, workspace};
+    const char* names[] = {"z", "a", "h", "saved", "workspace"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const NextSaved S = next_saved(s, const_cast<float*>(saved));
+    const NextBwdWs W = next_bwd_ws(s, workspace);
+    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L, A = s.A, Hd = s.Hd;
+
+    // an absent upstream gradient is a zero one
+    if (!dz_out) {
+        if (hipMemsetAsync(W.zz, 0, (size_t)R * L * sizeof(float), st) != hipSuccess) return launched("memset");
+        dz_out = W.zz;
+    }
+    if (!dr_out) {
+        if (hipMemsetAsync(W.zr, 0, (size_t)R * sizeof(float), st) != hipSuccess) return launched("memset");
+        dr_out = W.zr;
+    }
+
+    tdmpc_lg_job j[12];
+    // dq2 = (dr w4) ELU'(q2); de = dz' W3
+    j[0] = with_elu_bwd(dinput(R, M, 1, dr_out, T[R4W], M, W.dq2), S.q2);
+    j[1] = dinput(R, M, L, dz_out, T[P3W], M, W.de);
+    if (int rc = gemm(j, 2, stream)) return rc;
+
+    // prior_mlp.2 / .1 backward: de becomes the gradient at prior_mlp.0's output
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.de; b.g = T[P1G]; b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.bnpart;
+    b.dx = W.de; b.dg = G[P1G]; b.db = G[P1B]; b.rows = R; b.C = M;
+    if (int rc = bn_backward(b, st)) return rc;
+
+    j[0] = with_elu_bwd(dinput(R, M, M, W.dq2, T[R2W], M, W.dq1), S.q1);
+    if (int rc = gemm(j, 1, stream)) return rc;
+
+    // dL/dh' = dh'(upstream) + dp1 W_p0 + dq1 W_r0
+    j[0] = dinput(R, Hd, M, W.de, T[P0W], Hd, W.dhn);
+    j[0].seg[1] = seg(W.dq1, M, T[R0W], Hd, M, 0, 1);
+    j[0].nseg = 2;
+    if (dh_out) { j[0].res = dh_out; j[0].ldres = Hd; }
+    if (int rc = gemm(j, 1, stream)) return rc;
+
+    GateArgs g;
+    memset(&g, 0, sizeof g);
+    g.gh = S.gh; g.h = h;
+    for (int k = 0; k < 3; ++k) g.g[k] = T[LRG + 2 * k];
+    g.gate = S.gate; g.lnx = S.lnx; g.lnr = S.lnr;
+    g.dhn = W.dhn; g.dgi = W.dgi; g.dgh = W.dgh; g.dhd = W.dhd; g.part = W.lnpart;
+    g.rows = R; g.Hd = Hd;
+    hipLaunchKernelGGL(dt_gate_bwd, dim3(gate_wgs(R)), dim3(256), 0, st, g);
+    if (int rc = launched("gate_bwd")) return rc;
+    FinishArgs f;
+    memset(&f, 0, sizeof f);
+    f.part = W.lnpart; f.nparts = gate_wgs(R); f.nvec = 6; f.C = Hd;
+    for (int k = 0; k < 6; ++k) f.out[k] = G[LRG + k];
+    hipLaunchKernelGGL(dt_finish, dim3((6 * Hd + 255) / 256), dim3(256), 0, st, f);
+    if (int rc = launched("finish")) return rc;
+
+    // the input gradients and every weight gradient, one launch
+    int n = 0;
+    if (dz) j[n++] = dinput(R, L, 3 * Hd, W.dgi, T[WIH], L + A, dz);
+    if (da) j[n++] = dinput(R, A, 3 * Hd, W.dgi, T[WIH] + L, L + A, da);
+    if (dh) {
+        j[n] = dinput(R, Hd, 3 * Hd, W.dgh, T[WHH], Hd, dh);
+        j[n].res = W.dhd;
+        j[n++].ldres = Hd;
+    }
+    j[n++] = dweight(R, 3 * Hd, L, W.dgi, z, G[WIH], L + A, false);
+    j[n++] = dweight(R, 3 * Hd, A, W.dgi, a, G[WIH] + L, L + A, false);
+    j[n++] = dweight(R, 3 * Hd, Hd, W.dgh, h, G[WHH], Hd, false);
+    j[n++] = dweight(R, M, Hd, W.de, S.hn, W.wp0, Hd + 1, true);
+    j[n++] = dweight(R, L, M, dz_out, S.e, W.wp3, M + 1, true);
+    j[n++] = dweight(R, M, Hd, W.dq1, S.hn, W.wr0, Hd + 1, true);
+    j[n++] = dweight(R, M, M, W.dq2, S.q1, W.wr2, M + 1, true);
+    j[n++] = dweight(R, 1, M, dr_out, S.q2, W.wr4, M + 1, true);
+    if (int rc = gemm(j, n, stream)) return rc;
+
+    UnpackArgs u;
+    memset(&u, 0, sizeof u);
+    u.job[0] = UnpackJob{W.wp0, G[P0W], G[P0B], M, Hd};
+    u.job[1] = UnpackJob{W.wp3, G[P3W], G[P3B], L, M};
+    u.job[2] = UnpackJob{W.wr0, G[R0W], G[R0B], M, Hd};
+    u.job[3] = UnpackJob{W.wr2, G[R2W], G[R2B], M, M};
+    u.job[4] = UnpackJob{W.wr4, G[R4W], G[R4B], 1, M};
+    return unpack(u, 5, st);
+}
+
+int tdmpc_drnn_simloss_fwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_tensors, const float* queries,
+                           const float* keys, int32_t rows, float* loss, float* saved, size_t saved_floats,
+                           float* workspace, size_t workspace_floats, void* stream) {
+    Shape s;
+    if (int rc = check_shape(dims, rows, s)) return rc;
+    if (int rc = need_table(T, n_tensors, TDMPC_DT_LOSS_TENSORS, "tensors", true)) return rc;
+    const void* ptrs[] = {queries, keys, loss, saved, workspace};
+    const char* names[] = {"queries", "keys", "loss", "saved", "workspace"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const LossSaved S = loss_saved(s, saved);
+    const LossFwdWs W = loss_fwd_ws(s, workspace);
+    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L;
+
+    tdmpc_lg_job j = linear(R, M, L, queries, T[P0W], T[P0B], W.p1);
+    if (int rc = gemm(&j, 1, stream)) return rc;
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.p1; b.g = T[P1G]; b.b = T[P1B]; b.rmean = T[P1RM]; b.rvar = T[P1RV];
+    b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part; b.rows = R; b.C = M;
+    if (int rc = bn_forward(b, st)) return rc;
+    j = linear(R, L, M, S.e, T[P3W], T[P3B], S.pred);
+    if (int rc = gemm(&j, 1, stream)) return rc;
+    hipLaunchKernelGGL(dt_cos_fwd, dim3((R + 3) / 4), dim3(256), 0, st, S.pred, keys, loss, R, L);
+    return launched("cos_fwd");
+}
+
+int tdmpc_drnn_simloss_bwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_tensors, const float* queries,
+                           const float* keys, int32_t rows, const float* saved, size_t saved_floats,
+                           const float* dloss, float* dqueries, float* const* G, float* workspace,
+                           size_t workspace_floats, void* stream) {
+    Shape s;
+    if (int rc = check_shape(dims, rows, s)) return rc;
+    if (int rc = need_table(T, n_tensors, TDMPC_DT_LOSS_TENSORS, "tensors", true)) return rc;
+    if (int rc = need_table(G, n_tensors, TDMPC_DT_LOSS_TENSORS, "grads", false)) return rc;
+    const void* ptrs[] = {queries, keys, saved, dloss, workspace};
+    const char* names[] = {"queries", "keys", "saved", "dloss", "workspace"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const LossSaved S = loss_saved(s, const_cast<float*>(saved));
+    const LossBwdWs W = loss_bwd_ws(s, workspace);
+    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L;
+
+    hipLaunchKernelGGL(dt_cos_bwd, dim3((R + 3) / 4), dim3(256), 0, st, S.pred, keys, dloss, W.dpred, R, L);
+    if (int rc = launched("cos_bwd")) return rc;
+    tdmpc_lg_job j[3];
+    j[0] = dinput(R, M, L, W.dpred, T[P3W], M, W.de);
+    if (int rc = gemm(j, 1, stream)) return rc;
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.de; b.g = T[P1G]; b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part;
+    b.dx = W.de; b.dg = G[P1G]; b.db = G[P1B]; b.rows = R; b.C = M;
+    if (int rc = bn_backward(b, st)) return rc;
+    int n = 0;
+    if (dqueries) j[n++] = dinput(R, L, M, W.de, T[P0W], L, dqueries);
+    j[n++] = dweight(R, L, M, W.dpred, S.e, W.w3, M + 1, true);
+    j[n++] = dweight(R, M, L, W.de, queries, W.w0, L + 1, true);
+    if (int rc = gemm(j, n, stream)) return rc;
+    UnpackArgs u;
+    memset(&u, 0, sizeof u);
+    u.job[0] = UnpackJob{W.w3, G[P3W], G[P3B], L, M};
+    u.job[1] = UnpackJob{W.w0, G[P0W], G[P0B], M, L};
+    return unpack(u, 2, st);
+}
+
+}  // extern "C"

@@ -1,0 +1,220 @@
+"""The DSSM learner's two differentiable parts on HIP: `DSSM.next` in train mode and `similarity_loss`.
+
+`DssmTrainStep(model, max_rows)` wraps the passes of include/tdmpc_drnn_learner.h (csrc/drnn_learner.hip) as
+`torch.autograd.Function`s over a `tdmpc_amd.dssm.DSSM` on the GPU, so a DSSM update written in PyTorch runs its
+recurrent step and its similarity loss on the hand-written kernels while autograd chains the steps through time:
+
+    step = DssmTrainStep(model, max_rows=512)
+    z1, h1, r1 = step.next(z0, a0, h0)          # DSSM.next under model.train(): batch-statistics BatchNorm
+    loss = step.similarity_loss(z1, keys).mean() + r1.sum()
+    loss.backward()                             # .grad of the 20 + 6 parameter tensors, as from the eager modules
+
+The kernels read the model's own fp32 parameter tensors (no packed copy: they change every optimiser step), update the
+BatchNorms' running statistics in place as `nn.BatchNorm1d` does, and run every reduction in a fixed order. Each live
+`next` call (one whose backward has not run yet) holds one saved-activation buffer of the pool; the pool has
+`max_steps` of them (default `cfg.horizon + 1`) and `max_losses` for the loss (default 2).
+
+There is no eager fall-back: a missing library or an unsupported shape raises. This is not the `update` engine: no
+optimiser, no replay, no TD targets.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import DrnnTrainSizes, call, drnn_dims_from_cfg, ptr
+
+NEXT_PARAMS = tuple(f"_dynamics.prior_mlp.{k}" for k in ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight",
+                                                         "3.bias")) + \
+    tuple(f"_dynamics.gru_cell.{k}" for k in ("weight_ih.weight", "weight_hh.weight", "ln_reset.weight",
+                                              "ln_reset.bias", "ln_update.weight", "ln_update.bias",
+                                              "ln_newval.weight", "ln_newval.bias")) + \
+    tuple(f"_reward.{k}" for k in ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias"))
+LOSS_PARAMS = tuple(f"_predictor.{k}" for k in ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight", "3.bias"))
+_STATS_AT = 4   # running_mean / running_var follow the BatchNorm's weight and bias in state_dict order
+
+
+def _table(params, stats):
+    """The C pointer table: the parameters with the BatchNorm's running statistics at slots 4 and 5."""
+    ts = list(params[:_STATS_AT]) + list(stats) + list(params[_STATS_AT:])
+    return (C.c_void_p * len(ts))(*[ptr(t) for t in ts]), len(ts)
+
+
+class _Slot:
+    """One saved-activation buffer of a pool, handed back when the backward has run or the graph is dropped."""
+    live = False
+
+    def __init__(self, pool, what):
+        if not pool.free:
+            raise RuntimeError(
+                f"DssmTrainStep: more than {len(pool.bufs)} {what} calls are live (forward done, backward pending); "
+                f"construct it with a larger {pool.knob}")
+        self.pool, self.idx = pool, pool.free.pop()
+        self.buf = pool.bufs[self.idx]
+        self.live = True
+
+    def release(self):
+        if self.live:
+            self.live = False
+            self.pool.free.append(self.idx)
+
+    def __del__(self):
+        self.release()
+
+
+class _Pool:
+    def __init__(self, n, floats, device, knob):
+        self.bufs = [torch.empty(floats, dtype=torch.float32, device=device) for _ in range(n)]
+        self.free = list(range(n))[::-1]
+        self.knob = knob
+
+
+def _f32c(t):
+    return None if t is None else t.detach().to(torch.float32).contiguous()
+
+
+class _NextFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, step, z, a, h, *params):
+        z, a, h = _f32c(z), _f32c(a), _f32c(h)
+        R = z.shape[0]
+        slot = _Slot(step._next_pool, "next")
+        zo, ho, ro = z.new_empty(R, step.L), z.new_empty(R, step.Hd), z.new_empty(R)
+        tab, n = _table(params, step._next_stats)
+        try:
+            call("tdmpc_drnn_next_fwd", step.dims, tab, n, z, a, h, R, zo, ho, ro, slot.buf, slot.buf.numel(),
+                 step._ws, step._ws.numel(), torch.cuda.current_stream().cuda_stream)
+        except Exception:
+            slot.release()
+            raise
+        ctx.step, ctx.slot = step, slot
+        ctx.save_for_backward(z, a, h, *params)
+        ctx.set_materialize_grads(False)
+        return zo, ho, ro
+
+    @staticmethod
+    def backward(ctx, dzo, dho, dro):
+        step, slot = ctx.step, ctx.slot
+        if not slot.live:
+            raise RuntimeError("DssmTrainStep.next: this call's saved activations were released by an earlier backward")
+        z, a, h, *params = ctx.saved_tensors
+        R = z.shape[0]
+        dzo, dho, dro = _f32c(dzo), _f32c(dho), _f32c(dro)
+        need = ctx.needs_input_grad
+        dz, da, dh = (torch.empty_like(t) if need[1 + i] else None for i, t in enumerate((z, a, h)))
+        grads = [torch.empty_like(p) for p in params]
+        tab, n = _table(params, step._next_stats)
+        gtab, _ = _table(grads, (None, None))
+        call("tdmpc_drnn_next_bwd", step.dims, tab, n, z, a, h, R, slot.buf, slot.buf.numel(), ptr(dzo), ptr(dho),
+             ptr(dro), ptr(dz), ptr(da), ptr(dh), gtab, step._ws, step._ws.numel(),
+             torch.cuda.current_stream().cuda_stream)
+        slot.release()
+        return (None, dz, da, dh) + tuple(g if need[4 + i] else None for i, g in enumerate(grads))
+
+
+class _LossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, step, q, k, *params):
+        q, k = _f32c(q), _f32c(k)
+        R = q.shape[0]
+        slot = _Slot(step._loss_pool, "similarity_loss")
+        loss = q.new_empty(R)
+        tab, n = _table(params, step._loss_stats)
+        try:
+            call("tdmpc_drnn_simloss_fwd", step.dims, tab, n, q, k, R, loss, slot.buf, slot.buf.numel(), step._ws,
+                 step._ws.numel(), torch.cuda.current_stream().cuda_stream)
+        except Exception:
+            slot.release()
+            raise
+        ctx.step, ctx.slot = step, slot
+        ctx.save_for_backward(q, k, *params)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        step, slot = ctx.step, ctx.slot
+        if not slot.live:
+            raise RuntimeError("DssmTrainStep.similarity_loss: this call's saved activations were released by an "
+                               "earlier backward")
+        q, k, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dq = torch.empty_like(q) if need[1] else None
+        grads = [torch.empty_like(p) for p in params]
+        tab, n = _table(params, step._loss_stats)
+        gtab, _ = _table(grads, (None, None))
+        call("tdmpc_drnn_simloss_bwd", step.dims, tab, n, q, k, q.shape[0], slot.buf, slot.buf.numel(),
+             _f32c(dloss), ptr(dq), gtab, step._ws, step._ws.numel(), torch.cuda.current_stream().cuda_stream)
+        slot.release()
+        return (None, dq, None) + tuple(g if need[3 + i] else None for i, g in enumerate(grads))
+
+
+class DssmTrainStep:
+    """Differentiable `DSSM.next` (train mode) and `similarity_loss` on HIP for `model` (a `tdmpc_amd.dssm.DSSM` on the
+    GPU, fp32). max_rows: the largest batch of `next`; max_loss_rows: of `similarity_loss` (default
+    min(4096, max_rows * max_steps): the reference concatenates the per-step predictions)."""
+
+    def __init__(self, model, max_rows: int, max_steps: int | None = None, max_loss_rows: int | None = None,
+                 max_losses: int = 2):
+        cfg = model.cfg
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("DssmTrainStep: the model must be on the GPU (there is no CPU path)")
+        self.model, self.cfg = model, cfg
+        self.L, self.A, self.Hd = int(cfg.latent_dim), int(cfg.action_dim), int(cfg.hidden_dim)
+        self.max_rows = int(max_rows)
+        self.max_steps = int(max_steps if max_steps is not None else cfg.horizon + 1)
+        self.max_loss_rows = int(max_loss_rows if max_loss_rows is not None
+                                 else min(_lib.DT_MAX_ROWS, self.max_rows * self.max_steps))
+        self.dims = drnn_dims_from_cfg(cfg)
+        _lib.lib()
+        if _lib.lib().tdmpc_drnn_train_version() != _lib.DRNN_TRAIN_VERSION:
+            raise RuntimeError("libtdmpc_hip: tdmpc_drnn_train_version mismatch")
+        sn, sl = DrnnTrainSizes(), DrnnTrainSizes()
+        call("tdmpc_drnn_train_sizes_for", self.dims, self.max_rows, sn)
+        call("tdmpc_drnn_train_sizes_for", self.dims, self.max_loss_rows, sl)
+        named = dict(model.named_parameters())
+        bufs = dict(model.named_buffers())
+        self._next_params = tuple(named[k] for k in NEXT_PARAMS)
+        self._loss_params = tuple(named[k] for k in LOSS_PARAMS)
+        for p in self._next_params + self._loss_params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("DssmTrainStep: the model's parameters must be contiguous float32")
+        self._next_stats = (bufs["_dynamics.prior_mlp.1.running_mean"], bufs["_dynamics.prior_mlp.1.running_var"])
+        self._loss_stats = (bufs["_predictor.1.running_mean"], bufs["_predictor.1.running_var"])
+        self._next_pool = _Pool(self.max_steps, sn.next_saved_floats, dev, "max_steps")
+        self._loss_pool = _Pool(int(max_losses), sl.loss_saved_floats, dev, "max_losses")
+        self._ws = torch.empty(max(sn.workspace_floats, sl.workspace_floats), dtype=torch.float32, device=dev)
+
+    def _check(self, what, rows, cap, *shaped):
+        if not self.model.training:
+            raise RuntimeError(f"DssmTrainStep.{what}: the model is in eval() mode; these passes run the BatchNorms on "
+                               "batch statistics (model.train()). For inference use DrnnPlanner.next")
+        if rows > cap:
+            raise ValueError(f"DssmTrainStep.{what}: {rows} rows, sized for {cap}")
+        for name, t, width in shaped:
+            if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != width or not t.is_cuda:
+                raise ValueError(f"DssmTrainStep.{what}: {name} must be a GPU tensor of shape [{rows}, {width}], got "
+                                 f"{tuple(t.shape)} on {t.device}")
+
+    def next(self, z, a, h):
+        """`DSSM.next(z, a, h)` under `model.train()`: (z' [R, L], h' [R, Hd], r [R, 1]), differentiable in z, a, h and
+        the 20 parameter tensors of `_dynamics` and `_reward`. Moves prior_mlp's running statistics."""
+        self._check("next", z.shape[0], self.max_rows, ("z", z, self.L), ("a", a, self.A), ("h", h, self.Hd))
+        zo, ho, ro = _NextFn.apply(self, z, a, h, *self._next_params)
+        self.model._dynamics.prior_mlp[1].num_batches_tracked += 1
+        return zo, ho, ro.unsqueeze(1)
+
+    def similarity_loss(self, queries, keys):
+        """The reference's `similarity_loss(queries, keys)` -> [R]: 2 - 2 cos(_predictor(queries), keys) per row, the
+        keys detached. `queries` and `keys` may be lists of per-step [B, L] tensors (concatenated, as the reference does)."""
+        if isinstance(queries, (list, tuple)):
+            queries = torch.cat(list(queries), dim=0)
+        if isinstance(keys, (list, tuple)):
+            keys = torch.cat(list(keys), dim=0)
+        self._check("similarity_loss", queries.shape[0], self.max_loss_rows, ("queries", queries, self.L),
+                    ("keys", keys, self.L))
+        loss = _LossFn.apply(self, queries, keys.detach(), *self._loss_params)
+        self.model._predictor[1].num_batches_tracked += 1
+        return loss
