@@ -91,6 +91,53 @@ int tdmpc_drnn_simloss_bwd(const tdmpc_drnn_dims* dims, float* const* tensors, i
                            size_t saved_floats, const float* dloss, float* dqueries, float* const* grads,
                            float* workspace, size_t workspace_floats, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The DSSM update's own parts (TdICemSimDssm.update, tdmpc_icem_similarity_drnn.py:421-553).
+ * ------------------------------------------------------------------------------------------------------------- */
+
+/* Workspace floats of one tdmpc_drnn_intrinsic_fwd over `segments` segments of `seg_rows` rows. */
+int tdmpc_drnn_intrinsic_workspace_floats(const tdmpc_drnn_dims* dims, int32_t segments, int32_t seg_rows,
+                                          size_t* out);
+
+/* intrinsic_rewards' model uncertainty (:421-433) as one launch chain: `segments` independent one-step rollouts of
+ * seg_rows rows each from a zero hidden state, rows s * seg_rows + b. z [S B, L], a [S B, A], keys [S B, L] ->
+ * loss [S B] = similarity_loss(next(z, a, 0).z', keys), forward only. Both BatchNorms (prior_mlp.1, _predictor.1)
+ * normalise PER SEGMENT, and their running statistics (next_tensors[4] / [5], loss_tensors[4] / [5]) move `segments`
+ * times in segment order, so the result and the statistics are bitwise those of `segments` pairs of
+ * tdmpc_drnn_next_fwd (h = zeros) + tdmpc_drnn_simloss_fwd calls on the segments in order. The reward head is not run.
+ * Admitted: the shapes above, 1 <= segments, 2 <= seg_rows, segments * seg_rows <= TDMPC_DT_MAX_ROWS. */
+int tdmpc_drnn_intrinsic_fwd(const tdmpc_drnn_dims* dims, float* const* next_tensors, int32_t n_next,
+                             float* const* loss_tensors, int32_t n_loss, const float* z, const float* a,
+                             const float* keys, int32_t segments, int32_t seg_rows, float* loss, float* workspace,
+                             size_t workspace_floats, void* stream);
+
+/* The rest of intrinsic_rewards (:435-443) without the host: mean and population variance of loss [n] (float64, fixed
+ * order), gym's RunningMeanStd.update_from_moments(mean, var, 1) on the device state rms = double {mean, var, count}
+ * (initially 0, 1, 1e-4), then intrinsic[i] = max(loss[i] / sqrt(var') - mean' / sqrt(var'), 0) and
+ * reward_pi[i] = coef[0] * intrinsic[i] + reward[i]. coef: a device float (the explore schedule's value).
+ * One workgroup; 1 <= n <= TDMPC_DT_MAX_ROWS. */
+int tdmpc_drnn_intrinsic_finish(const float* loss, int32_t n, double* rms, const float* coef, const float* reward,
+                                float* intrinsic, float* reward_pi, void* stream);
+
+/* TdICemSimDssm.update's loss composition (:471-485, :497-499, :522-530). All [H][B] float32 but w [B]:
+ *   td[t]     TD-lambda targets, backwards from last = nq[H-1]: td[t] = rwpi[t] + discount nq[t] (1 - td_lambda) +
+ *             discount td_lambda td[t+1] (td[H] = nq[H-1])
+ *   rows [6][B]: sum_t sim, sum_t (rp - rw)^2, sum_t (q1 - td)^2 + (q2 - td)^2, min(sum_t |q1 - td| + |q2 - td|, 1e4),
+ *             model_loss = sim_coef min(sim, 1e4) + reward_coef min(rew, 1e4), td_loss = value_coef min(val, 1e4)
+ *   scal [8]: the means of sim, rew, val, model_loss + td_loss; weighted = mean(model_loss) mean(w) + mean(td_loss)
+ *             (the reference's mean over the [B, B] broadcast of model_loss [B, 1] * w [B]); mean(w); mean(model_loss);
+ *             mean(td_loss). */
+typedef struct tdmpc_drnn_loss_args {
+    const float *sim, *q1, *q2, *rp, *rw, *rwpi, *nq, *w;
+    int32_t H, B;
+    float sim_coef, reward_coef, value_coef, discount, td_lambda;
+} tdmpc_drnn_loss_args;
+int tdmpc_drnn_loss_forward(const tdmpc_drnn_loss_args* a, float* td, float* rows, float* scal, void* stream);
+/* gw [1] = dL / dweighted -> dsim, dq1, dq2, drp [H][B] (each may be null); the clamps pass gradient where the sum
+ * is <= 1e4 (torch.clamp). */
+int tdmpc_drnn_loss_backward(const tdmpc_drnn_loss_args* a, const float* td, const float* rows, const float* scal,
+                             const float* gw, float* dsim, float* dq1, float* dq2, float* drp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ The drop-in names:
     from tdmpc_amd import ReplayBuffer     # src/algorithm/helper.py:434 (device prioritized replay)
     from tdmpc_amd import TdICEM           # src/algorithm/tdmpc_icem_similarity_mlp.py:116 (iCEM planner)
     from tdmpc_amd import TdMpcDrnn        # src/algorithm/tdmpc_similarity_drnn.py:87 (GRU-dynamics DSSM planner)
-    from tdmpc_amd import TdIcemDrnn       # src/algorithm/tdmpc_icem_similarity_drnn.py:81 (iCEM on the DSSM)
+    from tdmpc_amd import TdIcemDrnn       # src/algorithm/tdmpc_icem_similarity_drnn.py:81 (iCEM on the DSSM: plan / update)
     from tdmpc_amd import EnvShardedPlanner  # vectorised envs over the GPUs of one node
 
 Imports are resolved lazily, so `import tdmpc_amd` does not load torch or the HIP library.
@@ -26,6 +26,7 @@ _EXPORTS = {
     "TdMpcDrnn": "drnn",
     "TdIcemDrnn": "drnn_icem",
     "DSSM": "dssm",
+    "DssmLearner": "drnn_learner",
     "EnvShardedPlanner": "parallel",
     "shard_bounds": "parallel",
     "make_cfg": "config",

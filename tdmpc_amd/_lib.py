@@ -36,7 +36,9 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_drnn_icem_sizes_for", "tdmpc_drnn_plan_icem", "tdmpc_drnn_colored_noise",
             # include/tdmpc_drnn_learner.h
             "tdmpc_drnn_train_version", "tdmpc_drnn_train_sizes_for", "tdmpc_drnn_next_fwd", "tdmpc_drnn_next_bwd",
-            "tdmpc_drnn_simloss_fwd", "tdmpc_drnn_simloss_bwd")
+            "tdmpc_drnn_simloss_fwd", "tdmpc_drnn_simloss_bwd", "tdmpc_drnn_intrinsic_workspace_floats",
+            "tdmpc_drnn_intrinsic_fwd", "tdmpc_drnn_intrinsic_finish", "tdmpc_drnn_loss_forward",
+            "tdmpc_drnn_loss_backward")
 DRNN_VERSION = 2
 DRNN_TRAIN_VERSION = 1
 DT_NEXT_TENSORS, DT_LOSS_TENSORS, DT_MAX_ROWS = 22, 8, 4096   # include/tdmpc_drnn_learner.h
@@ -158,6 +160,12 @@ class DrnnTrainSizes(C.Structure):   # tdmpc_drnn_train_sizes (include/tdmpc_drn
     _fields_ = [(n, C.c_size_t) for n in ("next_saved_floats", "loss_saved_floats", "workspace_floats")]
 
 
+class DrnnLossArgs(C.Structure):   # tdmpc_drnn_loss_args (include/tdmpc_drnn_learner.h)
+    _fields_ = [(n, C.c_void_p) for n in ("sim", "q1", "q2", "rp", "rw", "rwpi", "nq", "w")] + \
+               [("H", C.c_int32), ("B", C.c_int32)] + \
+               [(n, C.c_float) for n in ("sim_coef", "reward_coef", "value_coef", "discount", "td_lambda")]
+
+
 class Sizes(C.Structure):
     _fields_ = [("packed_weight_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t),
                 ("noise_floats_per_env", C.c_size_t)]
@@ -246,6 +254,11 @@ def lib():
     L.tdmpc_drnn_next_bwd.argtypes = [dd, pv, i32, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, pv, vp, sz, vp]
     L.tdmpc_drnn_simloss_fwd.argtypes = [dd, pv, i32, vp, vp, i32, vp, vp, sz, vp, sz, vp]
     L.tdmpc_drnn_simloss_bwd.argtypes = [dd, pv, i32, vp, vp, i32, vp, sz, vp, vp, pv, vp, sz, vp]
+    L.tdmpc_drnn_intrinsic_workspace_floats.argtypes = [dd, i32, i32, C.POINTER(sz)]
+    L.tdmpc_drnn_intrinsic_fwd.argtypes = [dd, pv, i32, pv, i32, vp, vp, vp, i32, i32, vp, vp, sz, vp]
+    L.tdmpc_drnn_intrinsic_finish.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.tdmpc_drnn_loss_forward.argtypes = [C.POINTER(DrnnLossArgs), vp, vp, vp, vp]
+    L.tdmpc_drnn_loss_backward.argtypes = [C.POINTER(DrnnLossArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED:
         if not hasattr(L, name) and not (name.startswith("tdmpc_debug_") and os.environ.get("TDMPC_LIB_PATH")):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")

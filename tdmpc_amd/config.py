@@ -58,6 +58,13 @@ DEFAULTS = dict(
     plan2expl=False,             # :108
     normalize=True,              # :97 (DSSM encoder: helper.dmlab_enc_norm; TOLD ignores it)
     norm_type="ln",              # :98
+    # learning of the DSSM agents (TdICemSimDssm.update, tdmpc_icem_similarity_drnn.py:445-553)
+    similarity_coef=1.0,         # :35
+    td_lambda=0.4,               # :38
+    explore_schedule="linear(0, 0.5, 25000, 5000)",   # :49 (intrinsic_reward_coef :36 substituted)
+    pi_lr=1e-3,                  # :65
+    optim_id="adamw",            # :68
+    weight_decay=0.0,            # :69
     # pixels.yaml
     frame_stack=3,               # cfgs/pixels.yaml:2
     num_channels=32,             # cfgs/pixels.yaml:3
@@ -78,10 +85,12 @@ TASK_OVERRIDES = {
     "humanoid": dict(latent_dim=100,    # cfgs/tasks/humanoid.yaml:6 (iterations:3 / num_samples:4 are
                                         # overridden by BASELINE.json's N=512, iters=6)
                      regularization_schedule="linear(0.05, 0.5, 1, 50000)",     # :9
-                     batch_size=512, lr=1e-3),                                    # :7
+                     batch_size=512, lr=1e-3,                                     # :7
+                     explore_schedule="linear(0, 0.5, 250000, 50000)"),           # :8
     "dog": dict(latent_dim=100, batch_size=2048, lr=3e-4),                        # cfgs/tasks/dog.yaml:4-6
     "cartpole": dict(regularization_schedule="linear(0.05, 0.5, 10000, 2500)",  # cfgs/tasks/cartpole.yaml:3
-                     lr=3e-4),                                                    # :4
+                     lr=3e-4, pi_lr=3e-4,                                         # :4-5
+                     explore_schedule="linear(0, 0.5, 10000, 2500)"),             # :2
 }
 
 # The BASELINE.json configs (name -> overrides). N/H/I come from BASELINE.json itself.

@@ -14,6 +14,12 @@
 //     per 128-row chunk a (mean, M2) or (sum dY, sum dY xhat) partial per column, combined in chunk order;
 //   * dt_cos_fwd / dt_cos_bwd: F.normalize on both sides and 2 - 2 cos, one wave per row;
 //   * dt_finish (column sums of partials in order), dt_unpack (a [out][in + 1] weight-gradient product -> dW, db).
+// For the DSSM update (TdICemSimDssm.update, tdmpc_icem_similarity_drnn.py:421-553):
+//   * tdmpc_drnn_intrinsic_fwd: intrinsic_rewards' H + 1 one-step rollouts from a zero hidden state and their similarity
+//     losses as one launch chain over S B rows -- dt_bn_stat / dt_bn_fwd normalise per segment of B rows and move the
+//     running statistics S times in segment order, dt_gate_fwd<true> reads no hidden state;
+//   * dt_intrinsic_finish: float64 moments of the losses, the RunningMeanStd update on the device, the rewards;
+//   * dt_loss_rows / dt_loss_means / dt_loss_bwd: the TD-lambda targets and the loss composition, forward and backward.
 // Every reduction runs in a fixed order: wave butterflies, LDS sums over waves in wave order, partials in index order.
 #include <hip/hip_runtime.h>
 
@@ -73,7 +79,9 @@ struct GateArgs {
     int rows, Hd;
 };
 
-// NormGRUCell.forward (models/rnns.py:19-29), one wave per row, four rows per workgroup.
+// NormGRUCell.forward (models/rnns.py:19-29), one wave per row, four rows per workgroup. ZH: the hidden state is zero
+// (a.gh and a.h are not read: weight_hh(0) = 0).
+template <bool ZH>
 __global__ void __launch_bounds__(256) dt_gate_fwd(const GateArgs a) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6), Hd = a.Hd;
     if (row >= a.rows) return;
@@ -85,11 +93,11 @@ __global__ void __launch_bounds__(256) dt_gate_fwd(const GateArgs a) {
         const int c = lane + 64 * i;
         ok[i] = c < Hd;
         const int cc = ok[i] ? c : 0;
-        sr[i] = a.gi[r3 + cc] + a.gh[r3 + cc];
-        su[i] = a.gi[r3 + Hd + cc] + a.gh[r3 + Hd + cc];
+        sr[i] = a.gi[r3 + cc] + (ZH ? 0.f : a.gh[r3 + cc]);
+        su[i] = a.gi[r3 + Hd + cc] + (ZH ? 0.f : a.gh[r3 + Hd + cc]);
         gin[i] = a.gi[r3 + 2 * Hd + cc];
-        ghn[i] = a.gh[r3 + 2 * Hd + cc];
-        hp[i] = a.h[r1 + cc];
+        ghn[i] = ZH ? 0.f : a.gh[r3 + 2 * Hd + cc];
+        hp[i] = ZH ? 0.f : a.h[r1 + cc];
     }
     float xr[4], xu[4], xn[4], rs[4], sn[4];
     const float rstd_r = ln_row(sr, ok, Hd, xr);
@@ -227,6 +235,9 @@ __global__ void __launch_bounds__(256) dt_finish(const FinishArgs a) {
 // ---- BatchNorm1d on batch statistics over C columns (+ ELU). Geometry of all four kernels: grid (C / 64, chunks),
 // 256 threads = 64 columns x 4 row phases; thread (tx, ty) takes rows chunk * CHUNK + ty, + 4, ... of column
 // 64 blockIdx.x + tx, and the four row phases add through LDS in phase order.
+// The two forward kernels normalise per segment of `seg` rows (rows = nseg * seg; one segment everywhere but in
+// tdmpc_drnn_intrinsic_fwd): blockIdx.y = segment * chunks(seg) + chunk, every segment's chunks start at its own row 0,
+// part and rstd are indexed per segment.
 struct BnArgs {
     const float* x;          // fwd: the Linear's output [R,C]; bwd: dL/d(ELU output) [R,C]
     const float* g; const float* b; float* rmean; float* rvar;
@@ -234,6 +245,7 @@ struct BnArgs {
     float* part;             // [chunks][2][C]
     float* dx; float* dg; float* db;        // bwd outputs: [R,C] (may be x), [C], [C]
     int rows, C;
+    int seg, nseg;           // fwd: rows per segment and segments (bn_forward fills them in: rows, 1)
 };
 
 __device__ __forceinline__ float phase_sum(float (&red)[4][64], float v, int tx, int ty) {
@@ -247,7 +259,8 @@ __device__ __forceinline__ float phase_sum(float (&red)[4][64], float v, int tx,
 __global__ void __launch_bounds__(256) dt_bn_stat(const BnArgs a) {
     __shared__ float red[4][64];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, c = blockIdx.x * 64 + tx, C = a.C;
-    const int r0 = blockIdx.y * CHUNK, r1 = min(a.rows, r0 + CHUNK);
+    const int cps = (a.seg + CHUNK - 1) / CHUNK, sg = blockIdx.y / cps, ch = blockIdx.y % cps;
+    const int r0 = sg * a.seg + ch * CHUNK, r1 = min((sg + 1) * a.seg, r0 + CHUNK);
     float s = 0.f;
     for (int r = r0 + ty; r < r1; r += 4) s += a.x[(size_t)r * C + c];
     const float mean = phase_sum(red, s, tx, ty) / (float)(r1 - r0);
@@ -278,24 +291,34 @@ __device__ __forceinline__ void bn_combine(const float* part, int rows, int C, i
     }
 }
 
-// xhat = (x - mean) / sqrt(biased var + eps), e = ELU(g xhat + b); chunk 0 also writes the columns' 1 / std and moves
-// the running statistics (momentum 0.1, the unbiased variance M2 / (R - 1), as nn.BatchNorm1d).
+// xhat = (x - mean) / sqrt(biased var + eps), e = ELU(g xhat + b); a segment's chunk 0 also writes its columns' 1 / std
+// and block row 0 moves the running statistics (momentum 0.1, the unbiased variance M2 / (R - 1), as nn.BatchNorm1d).
 __global__ void __launch_bounds__(256) dt_bn_fwd(const BnArgs a) {
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, c = blockIdx.x * 64 + tx, C = a.C;
-    const int r0 = blockIdx.y * CHUNK, r1 = min(a.rows, r0 + CHUNK);
+    const int cps = (a.seg + CHUNK - 1) / CHUNK, sg = blockIdx.y / cps, ch = blockIdx.y % cps;
+    const int r0 = sg * a.seg + ch * CHUNK, r1 = min((sg + 1) * a.seg, r0 + CHUNK);
     float mean, m2;
-    bn_combine(a.part, a.rows, C, c, mean, m2);
-    const float rstd = 1.f / sqrtf(m2 / (float)a.rows + BN_EPS);
+    bn_combine(a.part + (size_t)sg * cps * 2 * C, a.seg, C, c, mean, m2);
+    const float rstd = 1.f / sqrtf(m2 / (float)a.seg + BN_EPS);
     const float g = a.g[c], b = a.b[c];
     for (int r = r0 + ty; r < r1; r += 4) {
         const float xh = (a.x[(size_t)r * C + c] - mean) * rstd;
         a.xhat[(size_t)r * C + c] = xh;
         a.e[(size_t)r * C + c] = elu_f(xh * g + b);
     }
+    if (ch == 0 && ty == 0) a.rstd[(size_t)sg * C + c] = rstd;
     if (blockIdx.y == 0 && ty == 0) {
-        a.rstd[c] = rstd;
-        a.rmean[c] = (1.f - BN_MOM) * a.rmean[c] + BN_MOM * mean;
-        a.rvar[c] = (1.f - BN_MOM) * a.rvar[c] + BN_MOM * (m2 / (float)(a.rows - 1));
+        // the block that owns the column moves its running statistics once per segment, in segment order
+        float rm = a.rmean[c], rv = a.rvar[c];
+        for (int s = 0; s < a.nseg; ++s) {
+            if (s) bn_combine(a.part + (size_t)s * cps * 2 * C, a.seg, C, c, mean, m2);
+            // (1 - momentum) old, rounded, then one fma with the new term: spelled out so that the bits do not hang on
+            // which of the two products the compiler chooses to contract
+            rm = __fmaf_rn(BN_MOM, mean, __fmul_rn(1.f - BN_MOM, rm));
+            rv = __fmaf_rn(BN_MOM, m2 / (float)(a.seg - 1), __fmul_rn(1.f - BN_MOM, rv));
+        }
+        a.rmean[c] = rm;
+        a.rvar[c] = rv;
     }
 }
 
@@ -395,6 +418,129 @@ __global__ void __launch_bounds__(256) dt_unpack(const UnpackArgs a) {
         if (c < j.in) j.dw[(size_t)r * j.in + c] = v;
         else j.db[r] = v;
     }
+}
+
+// ---- intrinsic_rewards' normalisation (tdmpc_icem_similarity_drnn.py:435-443) in one workgroup: float64 moments of
+// n <= 4096 losses (thread-strided sums, then the 256 threads' sums in thread order), gym's update_from_moments with
+// batch_count 1 on the device state, the normalised and thresholded rewards.
+__device__ __forceinline__ double block_sum_f64(double (&red)[256], double v) {
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    double s = 0.0;
+    for (int i = 0; i < 256; ++i) s += red[i];
+    return s;
+}
+
+__global__ void __launch_bounds__(256) dt_intrinsic_finish(const float* loss, int n, double* rms, const float* coef,
+                                                           const float* reward, float* intrinsic, float* reward_pi) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += (double)loss[i];
+    const double bm = block_sum_f64(red, s) / (double)n;
+    double q = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double d = (double)loss[i] - bm;
+        q += d * d;
+    }
+    const double bv = block_sum_f64(red, q) / (double)n;
+    const double mean = rms[0], var = rms[1], count = rms[2];
+    const double delta = bm - mean, tot = count + 1.0;
+    const double mean2 = mean + delta / tot;
+    const double var2 = (var * count + bv + delta * delta * count / tot) / tot;
+    __syncthreads();   // every thread has read the old state
+    if (threadIdx.x == 0) {
+        rms[0] = mean2;
+        rms[1] = var2;
+        rms[2] = tot;
+    }
+    const double sd = sqrt(var2), thr = mean2 / sd;
+    const float k = coef[0];
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float v = (float)fmax((double)loss[i] / sd - thr, 0.0);
+        intrinsic[i] = v;
+        reward_pi[i] = k * v + reward[i];
+    }
+}
+
+// ---- TdICemSimDssm.update's loss composition (tdmpc_drnn_learner.h): one thread per batch column for the TD-lambda
+// recursion and the per-row sums, one workgroup for the means, one elementwise pass for the backward.
+constexpr float LOSS_CLAMP = 1e4f;
+
+__global__ void __launch_bounds__(256) dt_loss_rows(const tdmpc_drnn_loss_args a, float* td, float* rows) {
+    const int b = blockIdx.x * 256 + threadIdx.x, H = a.H, B = a.B;
+    if (b >= B) return;
+    float last = a.nq[(size_t)(H - 1) * B + b];
+    for (int t = H - 1; t >= 0; --t) {
+        const size_t i = (size_t)t * B + b;
+        const float in = a.rwpi[i] + a.discount * a.nq[i] * (1.f - a.td_lambda);
+        last = in + a.discount * last * a.td_lambda;
+        td[i] = last;
+    }
+    float sim = 0.f, rew = 0.f, val = 0.f, pri = 0.f;
+    for (int t = 0; t < H; ++t) {
+        const size_t i = (size_t)t * B + b;
+        const float dr = a.rp[i] - a.rw[i], d1 = a.q1[i] - td[i], d2 = a.q2[i] - td[i];
+        sim += a.sim[i];
+        rew += dr * dr;
+        val += d1 * d1 + d2 * d2;
+        pri += fabsf(d1) + fabsf(d2);
+    }
+    rows[b] = sim;
+    rows[B + b] = rew;
+    rows[2 * B + b] = val;
+    rows[3 * B + b] = fminf(pri, LOSS_CLAMP);
+    rows[4 * B + b] = a.sim_coef * fminf(sim, LOSS_CLAMP) + a.reward_coef * fminf(rew, LOSS_CLAMP);
+    rows[5 * B + b] = a.value_coef * fminf(val, LOSS_CLAMP);
+}
+
+__global__ void __launch_bounds__(512) dt_loss_means(const tdmpc_drnn_loss_args a, const float* rows, float* scal) {
+    __shared__ float red[6][8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, B = a.B;
+    float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int b = tid; b < B; b += 512) {
+        s[0] += rows[b];
+        s[1] += rows[B + b];
+        s[2] += rows[2 * B + b];
+        s[3] += rows[4 * B + b];
+        s[4] += rows[5 * B + b];
+        s[5] += a.w[b];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float v = wsum(s[k]);
+        if (lane == 0) red[k][wave] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float m[6];
+        for (int k = 0; k < 6; ++k) {
+            float v = 0.f;
+            for (int w = 0; w < 8; ++w) v += red[k][w];
+            m[k] = v / (float)B;
+        }
+        scal[0] = m[0]; scal[1] = m[1]; scal[2] = m[2];
+        scal[3] = m[3] + m[4];
+        scal[4] = m[3] * m[5] + m[4];
+        scal[5] = m[5]; scal[6] = m[3]; scal[7] = m[4];
+    }
+}
+
+__global__ void __launch_bounds__(256) dt_loss_bwd(const tdmpc_drnn_loss_args a, const float* td, const float* rows,
+                                                   const float* scal, const float* gw, float* dsim, float* dq1,
+                                                   float* dq2, float* drp) {
+    const int B = a.B;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)a.H * B) return;
+    const int b = (int)(i % B);
+    const float dmodel = gw[0] * scal[5] / (float)B, dtd = gw[0] / (float)B;
+    const float ds = rows[b] <= LOSS_CLAMP ? a.sim_coef * dmodel : 0.f;
+    const float dr = rows[B + b] <= LOSS_CLAMP ? a.reward_coef * dmodel : 0.f;
+    const float dv = rows[2 * B + b] <= LOSS_CLAMP ? a.value_coef * dtd : 0.f;
+    if (dsim) dsim[i] = ds;
+    if (drp) drp[i] = 2.f * (a.rp[i] - a.rw[i]) * dr;
+    if (dq1) dq1[i] = 2.f * (a.q1[i] - td[i]) * dv;
+    if (dq2) dq2[i] = 2.f * (a.q2[i] - td[i]) * dv;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -581,14 +727,18 @@ tdmpc_lg_job with_elu_bwd(tdmpc_lg_job j, const float* y) {
 }
 
 // One grouped launch on the exact f32 MFMA: 64 x 64 register tiles once the largest job fills the chip with them.
-int gemm(const tdmpc_lg_job* jobs, int n, void* stream) {
+// tile_rows > 0: choose the tile as for jobs of that many rows (the two tiles sum K in different orders; the segmented
+// pass keeps the bits of a one-segment call).
+int gemm(const tdmpc_lg_job* jobs, int n, void* stream, int tile_rows = 0) {
     long big = 0;
-    for (int q = 0; q < n; ++q) big = std::max(big, (long)((jobs[q].m + 63) / 64) * ((jobs[q].n + 63) / 64));
+    for (int q = 0; q < n; ++q)
+        big = std::max(big, (long)(((tile_rows ? tile_rows : jobs[q].m) + 63) / 64) * ((jobs[q].n + 63) / 64));
     return tdmpc_lg_gemm(jobs, n, (big >= 256 ? 2 : 1) | TDMPC_LG_TILE_EXACT, stream);
 }
 
 int bn_forward(BnArgs a, hipStream_t st) {
-    const dim3 g(a.C / 64, chunks(a.rows));
+    if (!a.seg) { a.seg = a.rows; a.nseg = 1; }
+    const dim3 g(a.C / 64, chunks(a.seg) * a.nseg);
     hipLaunchKernelGGL(dt_bn_stat, g, dim3(256), 0, st, a);
     if (int rc = launched("bn_stat")) return rc;
     hipLaunchKernelGGL(dt_bn_fwd, g, dim3(256), 0, st, a);
@@ -631,9 +781,133 @@ int size_err(const char* what, size_t have, size_t want) {
     return TDMPC_E_SIZE;
 }
 
+// tdmpc_drnn_intrinsic_fwd's workspace: what next_fwd and simloss_fwd save or stage, all scratch here. s.R = S * B rows.
+struct IntrWs { float *gi, *gate, *lnx, *lnr, *hn, *p1, *bnx, *bnr, *e, *part, *zo, *pred; size_t total; };
+IntrWs intr_ws(const Shape& s, int segments, int seg_rows, float* base) {
+    Bump b(base);
+    IntrWs v;
+    const size_t R = s.R;
+    v.gi = b.take(R * 3 * s.Hd);
+    v.gate = b.take(R * 3 * s.Hd);
+    v.lnx = b.take(R * 3 * s.Hd);
+    v.lnr = b.take(R * 4);
+    v.hn = b.take(R * s.Hd);
+    v.p1 = b.take(R * M);
+    v.bnx = b.take(R * M);
+    v.bnr = b.take((size_t)segments * M);
+    v.e = b.take(R * M);
+    v.part = b.take((size_t)segments * chunks(seg_rows) * 2 * M);
+    v.zo = b.take(R * s.L);
+    v.pred = b.take(R * s.L);
+    v.total = b.off;
+    return v;
+}
+
+int check_segments(const tdmpc_drnn_dims* d, int segments, int seg_rows, Shape& s) {
+    if (segments < 1 || seg_rows < 2 || (long)segments * seg_rows > TDMPC_DT_MAX_ROWS)
+        return bad("drnn_learner: %ld segments of %ld rows (at least 1 of at least 2 rows, 4096 rows in all)", segments,
+                   seg_rows);
+    return check_shape(d, segments * seg_rows, s);
+}
+
+bool loss_args_ok(const tdmpc_drnn_loss_args* a) {
+    return a && a->sim && a->q1 && a->q2 && a->rp && a->rw && a->rwpi && a->nq && a->w && a->H > 0 && a->B > 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int tdmpc_drnn_intrinsic_workspace_floats(const tdmpc_drnn_dims* dims, int32_t segments, int32_t seg_rows,
+                                          size_t* out) {
+    Shape s;
+    if (int rc = check_segments(dims, segments, seg_rows, s)) return rc;
+    if (int rc = need(out, "out")) return rc;
+    *out = intr_ws(s, segments, seg_rows, nullptr).total;
+    return 0;
+}
+
+int tdmpc_drnn_intrinsic_fwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_next, float* const* P,
+                             int32_t n_loss, const float* z, const float* a, const float* keys, int32_t segments,
+                             int32_t seg_rows, float* loss, float* workspace, size_t workspace_floats, void* stream) {
+    Shape s;
+    if (int rc = check_segments(dims, segments, seg_rows, s)) return rc;
+    if (int rc = need_table(T, n_next, TDMPC_DT_NEXT_TENSORS, "next_tensors", true)) return rc;
+    if (int rc = need_table(P, n_loss, TDMPC_DT_LOSS_TENSORS, "loss_tensors", true)) return rc;
+    const void* ptrs[] = {z, a, keys, loss, workspace};
+    const char* names[] = {"z", "a", "keys", "loss", "workspace"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const IntrWs W = intr_ws(s, segments, seg_rows, workspace);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L, A = s.A, Hd = s.Hd;
+
+    // next from h = 0: weight_hh(h) = 0, so only [z | a] weight_ih^T is a product
+    tdmpc_lg_job j = job(R, 3 * Hd, W.gi, 3 * Hd, seg(z, L, T[WIH], L + A, L, 0, 0));
+    j.seg[1] = seg(a, A, T[WIH] + L, L + A, A, 0, 0);
+    j.nseg = 2;
+    if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
+    GateArgs g;
+    memset(&g, 0, sizeof g);
+    g.gi = W.gi;
+    for (int k = 0; k < 3; ++k) { g.g[k] = T[LRG + 2 * k]; g.b[k] = T[LRB + 2 * k]; }
+    g.gate = W.gate; g.lnx = W.lnx; g.lnr = W.lnr; g.hn = W.hn; g.h_out = W.hn;
+    g.rows = R; g.Hd = Hd;
+    hipLaunchKernelGGL(dt_gate_fwd<true>, dim3((R + 3) / 4), dim3(256), 0, st, g);
+    if (int rc = launched("gate_fwd")) return rc;
+    j = linear(R, M, Hd, W.hn, T[P0W], T[P0B], W.p1);
+    if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.p1; b.g = T[P1G]; b.b = T[P1B]; b.rmean = T[P1RM]; b.rvar = T[P1RV];
+    b.xhat = W.bnx; b.rstd = W.bnr; b.e = W.e; b.part = W.part; b.rows = R; b.C = M;
+    b.seg = seg_rows; b.nseg = segments;
+    if (int rc = bn_forward(b, st)) return rc;
+    j = linear(R, L, M, W.e, T[P3W], T[P3B], W.zo);
+    if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
+
+    // similarity_loss(z', keys): the predictor's table has the same layout as prior_mlp's first eight slots
+    j = linear(R, M, L, W.zo, P[P0W], P[P0B], W.p1);
+    if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
+    b.g = P[P1G]; b.b = P[P1B]; b.rmean = P[P1RM]; b.rvar = P[P1RV];
+    if (int rc = bn_forward(b, st)) return rc;
+    j = linear(R, L, M, W.e, P[P3W], P[P3B], W.pred);
+    if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
+    hipLaunchKernelGGL(dt_cos_fwd, dim3((R + 3) / 4), dim3(256), 0, st, W.pred, keys, loss, R, L);
+    return launched("cos_fwd");
+}
+
+int tdmpc_drnn_intrinsic_finish(const float* loss, int32_t n, double* rms, const float* coef, const float* reward,
+                                float* intrinsic, float* reward_pi, void* stream) {
+    if (n < 1 || n > TDMPC_DT_MAX_ROWS) return bad("drnn_learner: intrinsic_finish over %ld values (1..4096)", n);
+    const void* ptrs[] = {loss, rms, coef, reward, intrinsic, reward_pi};
+    const char* names[] = {"loss", "rms", "coef", "reward", "intrinsic", "reward_pi"};
+    for (int i = 0; i < 6; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    hipLaunchKernelGGL(dt_intrinsic_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, loss, n, rms, coef, reward,
+                       intrinsic, reward_pi);
+    return launched("intrinsic_finish");
+}
+
+int tdmpc_drnn_loss_forward(const tdmpc_drnn_loss_args* a, float* td, float* rows, float* scal, void* stream) {
+    if (!loss_args_ok(a) || !td || !rows || !scal) return bad("drnn_learner: loss_forward: a null pointer or H, B < 1");
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(dt_loss_rows, dim3((a->B + 255) / 256), dim3(256), 0, st, *a, td, rows);
+    if (int rc = launched("loss_rows")) return rc;
+    hipLaunchKernelGGL(dt_loss_means, dim3(1), dim3(512), 0, st, *a, rows, scal);
+    return launched("loss_means");
+}
+
+int tdmpc_drnn_loss_backward(const tdmpc_drnn_loss_args* a, const float* td, const float* rows, const float* scal,
+                             const float* gw, float* dsim, float* dq1, float* dq2, float* drp, void* stream) {
+    if (!loss_args_ok(a) || !td || !rows || !scal || !gw)
+        return bad("drnn_learner: loss_backward: a null pointer or H, B < 1");
+    const long n = (long)a->H * a->B;
+    hipLaunchKernelGGL(dt_loss_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a, td, rows,
+                       scal, gw, dsim, dq1, dq2, drp);
+    return launched("loss_bwd");
+}
 
 int tdmpc_drnn_train_version(void) { return TDMPC_DRNN_TRAIN_VERSION; }
 
@@ -679,7 +953,7 @@ int tdmpc_drnn_next_fwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_
     for (int k = 0; k < 3; ++k) { g.g[k] = T[LRG + 2 * k]; g.b[k] = T[LRB + 2 * k]; }
     g.gate = S.gate; g.lnx = S.lnx; g.lnr = S.lnr; g.hn = S.hn; g.h_out = h_out;
     g.rows = R; g.Hd = Hd;
-    hipLaunchKernelGGL(dt_gate_fwd, dim3((R + 3) / 4), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(dt_gate_fwd<false>, dim3((R + 3) / 4), dim3(256), 0, st, g);
     if (int rc = launched("gate_fwd")) return rc;
 
     j[0] = linear(R, M, Hd, S.hn, T[P0W], T[P0B], W.p1);

@@ -18,6 +18,10 @@ Randomness: `rng="reference"` consumes torch's device generator and numpy's glob
 order (the coloured sequences through tdmpc_amd.colored_noise, as `TdICEM`); `rng="device"` draws the call's streams
 with one normal_, the spectrum normals with another and turns them into every coloured block of every env with one
 `tdmpc_drnn_colored_noise` launch; `plan(..., noise=IcemNoise-like)` takes explicit draws (parity tests).
+
+Learning: `update(replay_buffer, step)`, `update_pi(zs)`, `optim` / `pi_optim`, `explore_coef` and `reward_rms` as the
+reference's (:367-384, :421-553), run by `tdmpc_amd.drnn_learner.DssmLearner`, which is built on first use (an agent
+that only plans allocates none of it, and a cfg the learner refuses -- the dog task's batch of 2048 -- still plans).
 """
 from __future__ import annotations
 
@@ -102,6 +106,49 @@ class TdIcemDrnn(Agent):
         self._noise_params = {}
         self._has_prev = False
         self._has_elites = False
+        self.explore_coef = 0                                                 # :99
+        self._learner = None
+
+    # ------------------------------------------------------------------ learning (:367-384, :421-553)
+    @property
+    def learner(self):
+        if self._learner is None:
+            from .drnn_learner import DssmLearner
+            self._learner = DssmLearner(self, graph=self.graph)   # sets optim / pi_optim
+        return self._learner
+
+    @property
+    def reward_rms(self):
+        return self.learner.reward_rms
+
+    # optim / pi_optim: DssmLearner.__init__ assigns them; reading one builds the learner
+    def _optim_get(name):
+        def get(self):
+            self.learner
+            return self.__dict__["_" + name]
+        return property(get, lambda self, v: self.__dict__.__setitem__("_" + name, v))
+
+    optim, pi_optim = _optim_get("optim"), _optim_get("pi_optim")
+    del _optim_get
+
+    def update_pi(self, zs):
+        """:367-384 -> pi_loss (float; synchronises)."""
+        try:
+            return float(self.learner.update_pi(zs))
+        finally:
+            self.planner._packed_key = None   # the policy changed in place: the next plan() repacks
+
+    def update(self, replay_buffer, step, sync_metrics=True, noise=None):
+        """:445-553 -> the reference's metrics dict (floats; sync_metrics=False: 0-d device tensors, no
+        synchronisation). noise: optional 2H + 1 [B, A] TruncatedNormal draws (parity tests)."""
+        from .drnn_learner import METRICS
+        self.std = linear_schedule(self.cfg.std_schedule, step)              # :449
+        m, self.explore_coef = self.learner.update(replay_buffer, step, noise)
+        vals = m.tolist() if sync_metrics else list(m.unbind(0))
+        out = dict(zip(METRICS, vals))
+        out["current_explore_coef"] = self.explore_coef
+        out["mixture_coef"] = self.mixture_coef
+        return out
 
     # ------------------------------------------------------------------ reference state
     @property

@@ -1,0 +1,354 @@
+"""The DSSM iCEM agent's learner: `TdICemSimDssm.update / update_pi / intrinsic_rewards` on the GPU.
+
+Reference: src/algorithm/tdmpc_icem_similarity_drnn.py:367-384 (update_pi), :421-443 (intrinsic_rewards), :445-553
+(update). The math is the reference's (tests/drnn_update_ref.py restates it and is pinned bit for bit to the reference
+on the CPU; tests/test_gpu_drnn_update.py holds this module to it), including its quirks: no `rho` anywhere (the
+discount of later steps is computed and not used), the similarity term in the place of TOLD's consistency term, the
+weighting `mean(model_loss [B, 1] * weights [B]) + mean(td_loss)` whose first term is a mean over the [B, B] broadcast
+(= mean(model_loss) * mean(weights)), TD-lambda value targets from `reward + explore_coef * intrinsic`, the online
+encoder and policy with the target Q in those targets, and intrinsic rewards normalised by a running mean / std.
+
+`DssmLearner(agent, graph=True, warmup=3)` has two paths.
+
+The HIP path (the model on the GPU) orders one update for the device:
+  * the online encoder on `obs` with grad; the online and target encoders on `next_obses` once, without grad (the
+    reference encodes them twice with identical results);
+  * the intrinsic rewards -- in the reference H + 1 separate train-mode `next` + `pred_z` passes, each normalising its
+    BatchNorms over its own B rows, then a `.cpu()` round trip through a float64 RunningMeanStd -- as ONE segmented
+    launch chain and one finishing kernel on a device-resident RunningMeanStd (DssmTrainStep.intrinsic_rewards);
+  * the target-Q minimum of all H steps in one H B-row pass;
+  * the H-step rollout through `DssmTrainStep.next`, Q1 / Q2 on (z_t, a_t) for all t in one pass, `similarity_loss`
+    over the H B concatenated rows, the loss composition with its TD-lambda recursion as `_DssmFusedLoss`;
+  * backward, `clip_grad_norm_19`, the optimiser step, the priority write-back, and `update_pi` over the H + 1 latents in
+    one pass.
+Nothing synchronises with the host. After `warmup` eager updates one update per (buffer.idx, buffer._full) is captured
+into a HIP graph and replayed, as `learner.Learner` does; the explore coefficient changes every step, so it lives in a
+device scalar that is written before each replay. The encoder, Q and pi MLPs run on PyTorch-ROCm autograd here (float32
+matmul precision pinned); moving them onto tdmpc_lg_gemm / tdmpc_lg_rows_* is the follow-up.
+
+The PyTorch path is the reference's own order of operations, call by call, in plain PyTorch. It runs when the model is on
+the CPU (tests/test_drnn_update_cpu.py holds it bit for bit to the restatement) and on the GPU with
+TDMPC_DSSM_LEARNER_HIP=0 (tools/drnn_update_bench.py's comparison leg: the PyTorch-ROCm update on the same GPU, its
+RunningMeanStd on the device as well, so that it synchronises no more than the HIP path).
+
+Optimisers: the reference builds them with rlpyt's `create_optimizer(model, optim_id, lr)`, a package that is not
+available to check its defaults against. Here `cfg.optim_id` 'adam' gives `torch.optim.Adam` and 'adamw'
+`torch.optim.AdamW`, with lr = cfg.lr (model) / cfg.pi_lr (policy), weight_decay = getattr(cfg, 'weight_decay', 0.0)
+(cfgs/default.yaml: 0.0, at which AdamW and Adam take the same step) and torch's other defaults; `capturable=graph`.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from .config import linear_schedule
+from .dssm import check_dssm_cfg
+from .learner import clip_grad_norm_19
+
+METRICS = ("consistency_loss", "reward_loss", "value_loss", "pi_loss", "total_loss", "weighted_loss", "grad_norm",
+           "intrinsic_batch_reward_mean")
+
+
+def check_learner_cfg(cfg):
+    """Raise for what the DSSM learner does not cover, each setting named, before anything touches the device."""
+    check_dssm_cfg(cfg)
+    B, H = int(cfg.batch_size), int(cfg.horizon)
+    if B < 2:
+        raise ValueError(f"DssmLearner: batch_size={B} is not supported (train-mode BatchNorm needs two rows)")
+    if (H + 1) * B > _lib.DT_MAX_ROWS:
+        raise ValueError(f"DssmLearner: (horizon + 1) * batch_size = {(H + 1) * B} rows exceed {_lib.DT_MAX_ROWS} "
+                         f"(horizon={H}, batch_size={B}): the intrinsic-reward pass and its normalisation take at most "
+                         f"that many rows")
+    if str(getattr(cfg, "optim_id", "adamw")).lower() not in ("adam", "adamw"):
+        raise ValueError(f"DssmLearner: optim_id={cfg.optim_id!r} is not supported ('adam' or 'adamw')")
+
+
+def make_optimizer(params, cfg, lr, capturable=False):
+    cls = torch.optim.AdamW if str(getattr(cfg, "optim_id", "adamw")).lower() == "adamw" else torch.optim.Adam
+    return cls(params, lr=lr, weight_decay=float(getattr(cfg, "weight_decay", 0.0)), capturable=capturable)
+
+
+class RewardRms:
+    """The reference's `reward_rms` (gym's RunningMeanStd) as a view of the learner's device state [mean, var, count];
+    reading an attribute synchronises."""
+
+    def __init__(self, state):
+        self.state = state
+
+    mean = property(lambda self: float(self.state[0]))
+    var = property(lambda self: float(self.state[1]))
+    count = property(lambda self: float(self.state[2]))
+
+
+def rms_update(state, x):
+    """gym's RunningMeanStd.update_from_moments(mean(x), var(x), 1) on state = float64 [mean, var, count], in place
+    (tdmpc_icem_similarity_drnn.py:436-438). On the CPU the moments are numpy's, in x's precision, as the reference
+    takes them; on the GPU float64 device reductions (no host round trip)."""
+    if x.device.type == "cpu":
+        arr = x.detach().numpy()
+        bm = torch.tensor(float(np.mean(arr)), dtype=torch.float64)
+        bv = torch.tensor(float(np.std(arr) ** 2), dtype=torch.float64)
+    else:
+        xd = x.detach().double()
+        bm, bv = xd.mean(), xd.var(unbiased=False)
+    mean, var, count = state[0].clone(), state[1].clone(), state[2].clone()
+    delta = bm - mean
+    tot = count + 1
+    state[0] = mean + delta / tot
+    state[1] = (var * count + bv + delta * delta * count / tot) / tot
+    state[2] = tot
+
+
+def rms_normalize(state, x):
+    """:439-441 as the reference's NumPy computes it on a float32 array against the float64 state: the division in
+    float64 rounded to x's precision, the threshold subtracted in float64, max(., 0), back to x's precision."""
+    sd = torch.sqrt(state[1])
+    y = (x.double() / sd).to(x.dtype)
+    return torch.clamp_min(y.double() - state[0] / sd, 0).to(x.dtype)
+
+
+class DssmLearner:
+    """Owns the optimisers, the RunningMeanStd state and (in graph mode) the captured update graphs of one DSSM iCEM
+    agent (`agent`: cfg, model, model_target, device and, when it plans, planner)."""
+
+    def __init__(self, agent, graph: bool = True, warmup: int = 3):
+        cfg = self.cfg = agent.cfg
+        check_learner_cfg(cfg)
+        self.agent = agent
+        model = agent.model
+        p0 = next(model.parameters())
+        self.device, self.dtype = p0.device, p0.dtype
+        on_gpu = self.device.type == "cuda"
+        self.hip = on_gpu and os.environ.get("TDMPC_DSSM_LEARNER_HIP", "1") != "0"
+        self.graph = bool(graph) and on_gpu
+        self.warmup = warmup
+        self.params = list(model.parameters())
+        self.pi_params = list(model._pi.parameters())
+        self.target_params = list(agent.model_target.parameters())
+        agent.optim = make_optimizer(self.params, cfg, cfg.lr, capturable=self.graph)
+        agent.pi_optim = make_optimizer(self.pi_params, cfg, cfg.pi_lr, capturable=self.graph)
+        from .dssm_train import new_rms_state
+        self.rms = new_rms_state(self.device)
+        self.reward_rms = RewardRms(self.rms)
+        self.coef = torch.zeros(1, dtype=torch.float32 if self.hip else self.dtype, device=self.device)
+        self.train_step = None
+        if self.hip:
+            from .dssm_train import DssmTrainStep
+            B, H = int(cfg.batch_size), int(cfg.horizon)
+            self.train_step = DssmTrainStep(model, max_rows=B, max_steps=H, max_loss_rows=H * B, max_losses=1)
+        self.calls = 0
+        self._graphs = {}
+        self.last = {}   # the last eager step's intermediate results (tests): intrinsic, priorities
+
+    # ------------------------------------------------------------------ the policy update (:367-384)
+    def update_pi(self, zs, eps=None):
+        """-> pi_loss (tensor). zs: the H + 1 detached latents; eps: optional H + 1 [B, A] TruncatedNormal draws."""
+        a, cfg, m = self.agent, self.cfg, self.agent.model
+        a.pi_optim.zero_grad(set_to_none=True)
+        m.track_q_grad(False)
+        if self.hip:   # one pass over the (H + 1) B rows; no rho, as the reference's live line
+            n = len(zs)
+            Z = torch.cat(list(zs))
+            act = m.pi(Z, cfg.min_std, eps=None if eps is None else torch.cat(list(eps[:n])))
+            pi_loss = (-torch.min(*m.Q(Z, act)).view(n, -1).mean(dim=1)).sum()
+        else:
+            pi_loss = 0
+            for t, z in enumerate(zs):
+                act = m.pi(z, cfg.min_std, eps=None if eps is None else eps[t])
+                pi_loss += -torch.min(*m.Q(z, act)).mean()
+        pi_loss.backward()
+        clip_grad_norm_19(self.pi_params, cfg.grad_clip_norm)
+        a.pi_optim.step()
+        m.track_q_grad(True)
+        return pi_loss.detach()
+
+    # ------------------------------------------------------------------ one update
+    def step(self, buffer, noise=None):
+        """One `TdICemSimDssm.update` without the EMA -> metrics tensor [8] (METRICS order), no synchronisation.
+        noise: optional list of 2H + 1 [B, A] TruncatedNormal draws (H for the value targets, H + 1 for update_pi).
+        The explore coefficient is read from `self.coef` (`update` writes it)."""
+        return self._step_hip(buffer, noise) if self.hip else self._step_torch(buffer, noise)
+
+    def _finish(self, buffer, idxs, prio, zs, noise, H, means, weighted, grad_norm, intrinsic):
+        buffer.update_priorities(idxs, prio)
+        pi_loss = self.update_pi(zs, eps=None if noise is None else noise[H:])
+        self.last = dict(intrinsic=intrinsic, prio=prio)
+        return torch.stack([means[0], means[1], means[2], pi_loss.to(weighted.dtype), means[3], weighted.detach(),
+                            grad_norm, intrinsic.mean()]).detach()
+
+    def _step_hip(self, buffer, noise):
+        a, cfg, m, mt, ts = self.agent, self.cfg, self.agent.model, self.agent.model_target, self.train_step
+        H = int(cfg.horizon)
+        obs, next_obses, action, reward, idxs, weights = buffer.sample()
+        B, L = obs.shape[0], int(cfg.latent_dim)
+        a.optim.zero_grad(set_to_none=True)
+        z = m.h(obs)
+        with torch.no_grad():
+            flat = next_obses.reshape((H + 1) * B, -1)
+            nz_on, nz_tg = m.h(flat), mt.h(flat)                    # [(H + 1) B, L]: online, target
+            # :421-443: rollout t starts at z_traj[t] = (z, online next latents)[t] and is compared with target[t]
+            z_traj = torch.cat([z.detach(), nz_on[:H * B]])
+            intrinsic, reward_pi = ts.intrinsic_rewards(z_traj, action.reshape((H + 1) * B, -1), nz_tg, H + 1,
+                                                        self.rms, self.coef, reward.reshape(-1))
+            # :475-478: min target Q at the online next latents under the online policy, every step at once
+            x = nz_on[:H * B]
+            act = m.pi(x, cfg.min_std, eps=None if noise is None else torch.cat(list(noise[:H])))
+            next_q = torch.min(*mt.Q(x, act)).view(H, B)
+        hidden = m.init_hidden_state(B, z.device)
+        zt, zs, rps = z, [z], []
+        for t in range(H):
+            zt, hidden, r = ts.next(zt, action[t], hidden)
+            zs.append(zt)
+            rps.append(r)
+        x = torch.cat([torch.stack(zs[:H]), action[:H]], dim=-1).view(H * B, -1)
+        Q1, Q2 = m._Q1(x).view(H, B), m._Q2(x).view(H, B)
+        sim = ts.similarity_loss(zs[1:], nz_tg[:H * B])
+        from .dssm_train import _DssmFusedLoss
+        scal, rows, _ = _DssmFusedLoss.apply(
+            sim.view(H, B), Q1, Q2, torch.stack(rps).view(H, B), reward[:H].reshape(H, B),
+            reward_pi.view(H + 1, B)[:H], next_q, weights,
+            (float(cfg.similarity_coef), float(cfg.reward_coef), float(cfg.value_coef), float(cfg.discount),
+             float(cfg.td_lambda)))
+        weighted = scal[4]
+        weighted.register_hook(lambda grad: grad * (1 / H))
+        weighted.backward()
+        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
+        a.optim.step()
+        return self._finish(buffer, idxs, rows[3].view(B, 1), [t.detach() for t in zs], noise, H,
+                            (scal[0], scal[1], scal[2], scal[3]), weighted, grad_norm, intrinsic.view(H + 1, B, 1))
+
+    def _intrinsic_torch(self, obs, next_obses, action):
+        """:421-443 call by call (H + 1 train-mode `next` + `pred_z` passes), the RunningMeanStd by `rms_update`."""
+        m, mt, H = self.agent.model, self.agent.model_target, int(self.cfg.horizon)
+        with torch.no_grad():
+            zs_target = mt.h(next_obses)
+            z_traj = m.h(torch.cat([obs.unsqueeze(0), next_obses], dim=0))
+            out = []
+            for t in range(H + 1):
+                hidden = m.init_hidden_state(obs.shape[0], obs.device).to(obs.dtype)
+                zl, _, _ = m.next(z_traj[t], action[t], hidden)
+                pred = F.normalize(m.pred_z(zl).unsqueeze(0), dim=-1, p=2)
+                target = F.normalize(zs_target[t:t + 1], dim=-1, p=2)
+                out.append((2.0 - 2.0 * (pred * target).sum(dim=-1, keepdim=True))[0])
+            raw = torch.stack(out)                                   # [H + 1, B, 1]
+            rms_update(self.rms, raw)
+            return rms_normalize(self.rms, raw)
+
+    def _step_torch(self, buffer, noise):
+        a, cfg, m, mt = self.agent, self.cfg, self.agent.model, self.agent.model_target
+        H = int(cfg.horizon)
+        obs, next_obses, action, reward, idxs, weights = buffer.sample()
+        B = obs.shape[0]
+        a.optim.zero_grad(set_to_none=True)
+        z = m.h(obs)
+        next_zs = mt.h(next_obses)
+        online_next_zs = m.h(next_obses)
+        zs = [z.detach()]
+        intrinsic = self._intrinsic_torch(obs, next_obses, action)
+        reward_pi = self.coef * intrinsic + reward
+        rewards = reward_pi[:H]
+        discounts = torch.ones_like(rewards) * cfg.discount
+        next_q = []
+        for t in range(H):
+            with torch.no_grad():
+                nz = online_next_zs[t]
+                next_q.append(torch.min(*mt.Q(nz, m.pi(nz, cfg.min_std, eps=None if noise is None else noise[t]))))
+        next_q = torch.stack(next_q, dim=0)
+        last = next_q[-1]
+        inputs = rewards + discounts * next_q * (1 - cfg.td_lambda)
+        outputs = []
+        for index in reversed(range(H)):
+            last = inputs[index] + discounts[index] * last * cfg.td_lambda
+            outputs.append(last)
+        td = torch.stack(list(reversed(outputs)), dim=0)
+        reward_loss, value_loss, priority_loss = 0, 0, 0
+        hidden = m.init_hidden_state(B, z.device).to(z.dtype)
+        queries, keys = [], []
+        for t in range(H):
+            Q1, Q2 = m.Q(z, action[t])
+            z, hidden, reward_pred = m.next(z, action[t], hidden)
+            reward_loss += F.mse_loss(reward_pred, reward[t], reduction="none")
+            value_loss += F.mse_loss(Q1, td[t], reduction="none") + F.mse_loss(Q2, td[t], reduction="none")
+            priority_loss += F.l1_loss(Q1, td[t], reduction="none") + F.l1_loss(Q2, td[t], reduction="none")
+            queries.append(z)
+            keys.append(next_zs[t].detach())
+            zs.append(z.detach())
+        q = F.normalize(m.pred_z(torch.cat(queries, dim=0)), dim=-1, p=2)
+        k = F.normalize(torch.cat(keys, dim=0), dim=-1, p=2)
+        similarity_loss = 0 + (2.0 - 2.0 * (q * k).sum(dim=-1)).reshape(H, B, -1).sum(dim=0)
+        model_loss = cfg.similarity_coef * similarity_loss.clamp(max=1e4) + cfg.reward_coef * reward_loss.clamp(max=1e4)
+        td_loss = cfg.value_coef * value_loss.clamp(max=1e4)
+        total_loss = model_loss + td_loss
+        weighted = (model_loss * weights).mean() + td_loss.mean()   # the reference's [B, B] broadcast, literally
+        weighted.register_hook(lambda grad: grad * (1 / H))
+        weighted.backward()
+        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
+        a.optim.step()
+        return self._finish(buffer, idxs, priority_loss.clamp(max=1e4).detach(), zs, noise, H,
+                            (similarity_loss.mean(), reward_loss.mean(), value_loss.mean(), total_loss.mean()),
+                            weighted, grad_norm, intrinsic)
+
+    @torch.no_grad()
+    def ema(self):
+        """helper.py:48-52: target <- lerp(target, model, tau)."""
+        torch._foreach_lerp_(self.target_params, self.params, self.cfg.tau)
+
+    # ------------------------------------------------------------------ graph driver (learner.Learner's)
+    def _capturable(self, buffer):
+        return self.graph and getattr(buffer, "graph_safe", False)
+
+    def update(self, buffer, step, noise=None):
+        """`TdICemSimDssm.update` semantics -> (metrics tensor [8] on the device, explore_coef); no synchronisation."""
+        coef = linear_schedule(self.cfg.explore_schedule, step)
+        self.coef.fill_(coef)
+        if self.device.type != "cuda":
+            return self._update(buffer, step, noise), coef
+        prec = torch.get_float32_matmul_precision()
+        tf32 = torch.backends.cuda.matmul.allow_tf32
+        torch.set_float32_matmul_precision("highest")
+        torch.backends.cuda.matmul.allow_tf32 = False
+        try:
+            return self._update(buffer, step, noise), coef
+        finally:
+            torch.set_float32_matmul_precision(prec)
+            torch.backends.cuda.matmul.allow_tf32 = tf32
+
+    def _update(self, buffer, step, noise=None):
+        model = self.agent.model
+        model.train()
+        if noise is not None or not self._capturable(buffer) or self.calls < self.warmup:
+            if self._capturable(buffer) and self.calls == self.warmup - 1:
+                # the last warm-up runs on a side stream, as graph capture requires of lazily created state
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    m = self.step(buffer, noise)
+                torch.cuda.current_stream().wait_stream(s)
+            else:
+                m = self.step(buffer, noise)
+        else:
+            key = (buffer.idx, buffer._full)
+            g = self._graphs.get(key)
+            if g is None:
+                if len(self._graphs) >= 2:   # the buffer grew: drop the stale captures
+                    self._graphs.clear()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    out = self.step(buffer)
+                g = self._graphs[key] = (graph, out)
+                # capture recorded the kernels without running them: run this call's update
+            g[0].replay()
+            m = g[1]
+        self.calls += 1
+        if step % self.cfg.update_freq == 0:
+            self.ema()
+        model.eval()
+        planner = getattr(self.agent, "planner", None)
+        if planner is not None:
+            # parameters changed in place (a graph replay does not bump tensor versions): repack for planning
+            planner._packed_key = None
+        return m

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .told import _enc, _mlp, _orthogonal_init, _q
+from .told import _enc, _mlp, _orthogonal_init, _q, truncated_normal_sample
 
 
 def check_dssm_cfg(cfg):
@@ -116,6 +116,28 @@ class DSSM(nn.Module):
     def Q(self, z, a):
         x = torch.cat([z, a], dim=-1)
         return self._Q1(x), self._Q2(x)
+
+    # What the learner (tdmpc_amd/drnn_learner.py) differentiates besides `next` (tdmpc_icem_similarity_drnn.py:36-78)
+    def track_q_grad(self, enable=True):
+        for m in (self._Q1, self._Q2):
+            for p in m.parameters():
+                p.requires_grad_(enable)
+
+    def track_model_grad(self, enable=True):
+        for m in (self._Q1, self._Q2, self._reward, self._dynamics):
+            for p in m.parameters():
+                p.requires_grad_(enable)
+
+    def pi(self, z, std=0, eps=None):
+        """tanh(pi(z)), plus a TruncatedNormal(mu, std).sample(clip=0.3) when std > 0 (`eps`: the N(0, 1) draw to use
+        instead of drawing one -- parity tests)."""
+        mu = torch.tanh(self._pi(z))
+        if std > 0:
+            return truncated_normal_sample(mu, torch.ones_like(mu) * std, clip=0.3, noise=eps)
+        return mu
+
+    def pred_z(self, z):
+        return self._predictor(z)
 
 
 def float_tensors(sd: dict) -> list:

@@ -14,8 +14,14 @@ BatchNorms' running statistics in place as `nn.BatchNorm1d` does, and run every 
 `next` call (one whose backward has not run yet) holds one saved-activation buffer of the pool; the pool has
 `max_steps` of them (default `cfg.horizon + 1`) and `max_losses` for the loss (default 2).
 
-There is no eager fall-back: a missing library or an unsupported shape raises. This is not the `update` engine: no
-optimiser, no replay, no TD targets.
+Two more pieces serve the DSSM update (tdmpc_amd/drnn_learner.py), both forward-only or elementwise:
+`step.intrinsic_rewards(...)` runs `intrinsic_rewards`' H + 1 independent one-step rollouts and their similarity losses
+as ONE launch chain whose BatchNorms normalise per segment of B rows (tdmpc_drnn_intrinsic_fwd), then normalises the
+result against a device-resident float64 RunningMeanStd (tdmpc_drnn_intrinsic_finish) without a host round trip;
+`_DssmFusedLoss` is the update's loss composition with its TD-lambda targets and its backward.
+
+There is no eager fall-back: a missing library or an unsupported shape raises. The update itself (optimisers, replay,
+the encoder / Q / pi passes) is `tdmpc_amd.drnn_learner.DssmLearner`.
 """
 from __future__ import annotations
 
@@ -24,7 +30,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import DrnnTrainSizes, call, drnn_dims_from_cfg, ptr
+from ._lib import DrnnLossArgs, DrnnTrainSizes, call, drnn_dims_from_cfg, ptr
 
 NEXT_PARAMS = tuple(f"_dynamics.prior_mlp.{k}" for k in ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight",
                                                          "3.bias")) + \
@@ -150,6 +156,64 @@ class _LossFn(torch.autograd.Function):
         return (None, dq, None) + tuple(g if need[3 + i] else None for i, g in enumerate(grads))
 
 
+class _DssmFusedLoss(torch.autograd.Function):
+    """TdICemSimDssm.update's loss composition (tdmpc_icem_similarity_drnn.py:471-485, :497-499, :522-530) and its
+    backward as HIP kernels (tdmpc_drnn_loss_forward / _backward): forward(sim, q1, q2, rp, rw, rwpi, nq [H, B], w [B],
+    coefs = (similarity_coef, reward_coef, value_coef, discount, td_lambda)) -> (scal [8], rows [6, B], td [H, B]);
+    scal = (mean similarity, mean reward, mean value, mean total, weighted, mean w, mean model_loss, mean td_loss),
+    rows = (similarity, reward, value, clamped priority, model_loss, td_loss) per batch row, td = the TD-lambda targets.
+    Only scal[4] (the weighted loss) carries a gradient, to sim, q1, q2 and rp."""
+
+    @staticmethod
+    def forward(ctx, sim, q1, q2, rp, rw, rwpi, nq, w, coefs):
+        H, B = sim.shape
+        ins = [_f32c(t) for t in (sim, q1, q2, rp, rw, rwpi, nq, w)]
+        for t in ins[:7]:
+            if tuple(t.shape) != (H, B):
+                raise ValueError(f"_DssmFusedLoss: every operand but w must be [{H}, {B}], got {tuple(t.shape)}")
+        if tuple(ins[7].shape) != (B,):
+            raise ValueError(f"_DssmFusedLoss: w must be [{B}], got {tuple(ins[7].shape)}")
+        args = DrnnLossArgs(*[t.data_ptr() for t in ins], H, B, *[float(c) for c in coefs])
+        td, rows, scal = sim.new_empty(H, B), sim.new_empty(6, B), sim.new_empty(8)
+        call("tdmpc_drnn_loss_forward", args, td, rows, scal, torch.cuda.current_stream().cuda_stream)
+        ctx.save_for_backward(*ins, td, rows, scal)
+        ctx.coefs = coefs
+        ctx.mark_non_differentiable(rows, td)
+        return scal, rows, td
+
+    @staticmethod
+    def backward(ctx, g_scal, g_rows, g_td):
+        *ins, td, rows, scal = ctx.saved_tensors
+        H, B = ins[0].shape
+        args = DrnnLossArgs(*[t.data_ptr() for t in ins], H, B, *[float(c) for c in ctx.coefs])
+        g = g_scal.contiguous()
+        need = ctx.needs_input_grad
+        dsim, dq1, dq2, drp = (torch.empty_like(ins[0]) if need[i] else None for i in range(4))
+        call("tdmpc_drnn_loss_backward", args, td, rows, scal, g.data_ptr() + 16, ptr(dsim), ptr(dq1), ptr(dq2),
+             ptr(drp), torch.cuda.current_stream().cuda_stream)
+        return dsim, dq1, dq2, drp, None, None, None, None, None
+
+
+def new_rms_state(device):
+    """gym's RunningMeanStd() as a float64 [mean, var, count] tensor (tdmpc_drnn_intrinsic_finish's device state)."""
+    return torch.tensor([0.0, 1.0, 1e-4], dtype=torch.float64, device=device)
+
+
+@torch.no_grad()
+def intrinsic_finish(loss, rms, coef, reward):
+    """tdmpc_drnn_intrinsic_finish: the RunningMeanStd update of `rms` from the losses' mean and population variance,
+    then (intrinsic, reward_pi) -- see DssmTrainStep.intrinsic_rewards."""
+    if rms.dtype != torch.float64 or rms.numel() != 3 or not rms.is_cuda or not rms.is_contiguous():
+        raise ValueError("intrinsic_finish: rms must be new_rms_state()'s float64 [3] device tensor")
+    loss, reward = _f32c(loss).view(-1), _f32c(reward).view(-1)
+    if reward.numel() != loss.numel() or coef.dtype != torch.float32 or not coef.is_cuda:
+        raise ValueError("intrinsic_finish: reward must match the losses and coef be a float32 device scalar")
+    intrinsic, reward_pi = torch.empty_like(loss), torch.empty_like(loss)
+    call("tdmpc_drnn_intrinsic_finish", loss, loss.numel(), rms, coef, reward, intrinsic, reward_pi,
+         torch.cuda.current_stream().cuda_stream)
+    return intrinsic, reward_pi
+
+
 class DssmTrainStep:
     """Differentiable `DSSM.next` (train mode) and `similarity_loss` on HIP for `model` (a `tdmpc_amd.dssm.DSSM` on the
     GPU, fp32). max_rows: the largest batch of `next`; max_loss_rows: of `similarity_loss` (default
@@ -186,6 +250,7 @@ class DssmTrainStep:
         self._next_pool = _Pool(self.max_steps, sn.next_saved_floats, dev, "max_steps")
         self._loss_pool = _Pool(int(max_losses), sl.loss_saved_floats, dev, "max_losses")
         self._ws = torch.empty(max(sn.workspace_floats, sl.workspace_floats), dtype=torch.float32, device=dev)
+        self._iws = {}   # (segments, rows per segment) -> the workspace of intrinsic_loss
 
     def _check(self, what, rows, cap, *shaped):
         if not self.model.training:
@@ -218,3 +283,37 @@ class DssmTrainStep:
         loss = _LossFn.apply(self, queries, keys.detach(), *self._loss_params)
         self.model._predictor[1].num_batches_tracked += 1
         return loss
+
+    @torch.no_grad()
+    def intrinsic_loss(self, z, a, keys, segments):
+        """`segments` independent `next(z, a, 0)` + `similarity_loss(z', keys)` passes over the row blocks
+        [s B, (s + 1) B) of z [S B, L], a [S B, A], keys [S B, L] as one launch chain -> loss [S B]. Forward only. Each
+        segment normalises both BatchNorms over its own B rows and moves their running statistics once, in segment
+        order: bitwise what S pairs of `next` / `similarity_loss` calls on the segments give."""
+        R = z.shape[0]
+        S = int(segments)
+        if S < 1 or R % S:
+            raise ValueError(f"DssmTrainStep.intrinsic_loss: {R} rows do not split into {S} segments")
+        self._check("intrinsic_loss", R, _lib.DT_MAX_ROWS, ("z", z, self.L), ("a", a, self.A), ("keys", keys, self.L))
+        z, a, keys = _f32c(z), _f32c(a), _f32c(keys)
+        ws = self._iws.get((S, R // S))
+        if ws is None:
+            n = C.c_size_t()
+            call("tdmpc_drnn_intrinsic_workspace_floats", self.dims, S, R // S, C.byref(n))
+            ws = self._iws[(S, R // S)] = torch.empty(n.value, dtype=torch.float32, device=z.device)
+        loss = z.new_empty(R)
+        ntab, nn_ = _table(self._next_params, self._next_stats)
+        ltab, nl = _table(self._loss_params, self._loss_stats)
+        call("tdmpc_drnn_intrinsic_fwd", self.dims, ntab, nn_, ltab, nl, z, a, keys, S, R // S, loss, ws, ws.numel(),
+             torch.cuda.current_stream().cuda_stream)
+        self.model._dynamics.prior_mlp[1].num_batches_tracked += S
+        self.model._predictor[1].num_batches_tracked += S
+        return loss
+
+    @torch.no_grad()
+    def intrinsic_rewards(self, z, a, keys, segments, rms, coef, reward):
+        """The reference's `intrinsic_rewards` on the device: `intrinsic_loss`, then the RunningMeanStd update of `rms`
+        (`new_rms_state`) from the losses' mean and population variance and intrinsic = max(loss / sqrt(var) -
+        mean / sqrt(var), 0) -> (intrinsic [S B], reward_pi [S B] = coef * intrinsic + reward). coef: a one-element
+        float32 device tensor (the explore schedule's value of this step); reward [S B]."""
+        return intrinsic_finish(self.intrinsic_loss(z, a, keys, segments), rms, coef, reward)
