@@ -138,6 +138,51 @@ int tdmpc_drnn_loss_forward(const tdmpc_drnn_loss_args* a, float* td, float* row
 int tdmpc_drnn_loss_backward(const tdmpc_drnn_loss_args* a, const float* td, const float* rows, const float* scal,
                              const float* gw, float* dsim, float* dq1, float* dq2, float* drp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * TdMpcSimDssm.update's own parts (tdmpc_similarity_drnn.py:373-496).
+ * ------------------------------------------------------------------------------------------------------------- */
+
+/* Workspace floats of one tdmpc_drnn_intrinsic_chain_fwd over `segments` segments of `seg_rows` rows. */
+int tdmpc_drnn_intrinsic_chain_workspace_floats(const tdmpc_drnn_dims* dims, int32_t segments, int32_t seg_rows,
+                                                size_t* out);
+
+/* TdMpcSimDssm.intrinsic_rewards' model uncertainty (:373-391, similarity_horizon 1): ONE hidden state runs through the
+ * S = `segments` closed-loop steps, h_0 = 0, h_{s+1} = cell([z_s | a_s], h_s) over rows s * seg_rows + b of
+ * z [S B, L], a [S B, A]. prior_mlp runs on every h_{s+1} (each segment normalises its BatchNorm over its own B rows
+ * and moves next_tensors[4] / [5] once, in segment order: S times). Segments s >= warm go on through _predictor and
+ * loss[s B + b] = 2 - 2 cos(pred, keys[s B + b]) (loss_tensors[4] / [5] move S - warm times); loss is zero in the
+ * first `warm` segments. h_out [B, Hd] = h_S. Forward only; the reward head is not run.
+ *   mode 0  the recurrence as a launch chain (per step h weight_hh^T and the gate kernel): loss, h_out and the running
+ *           statistics are bitwise those of S tdmpc_drnn_next_fwd calls with the hidden state handed on (the first from
+ *           zeros) and tdmpc_drnn_simloss_fwd on z' of the segments >= warm, in order;
+ *   mode 1  the recurrence in one launch (a workgroup owns 16 batch rows through all S steps); the same math with the
+ *           hidden product summed in another order.
+ * The workspace begins with hn [S B, Hd], every segment's new hidden state. Admitted: the shapes of
+ * tdmpc_drnn_intrinsic_fwd, 0 <= warm < segments. */
+int tdmpc_drnn_intrinsic_chain_fwd(const tdmpc_drnn_dims* dims, float* const* next_tensors, int32_t n_next,
+                                   float* const* loss_tensors, int32_t n_loss, const float* z, const float* a,
+                                   const float* keys, int32_t segments, int32_t seg_rows, int32_t warm, int32_t mode,
+                                   float* loss, float* h_out, float* workspace, size_t workspace_floats, void* stream);
+
+/* TdMpcSimDssm.update's loss composition (:423, :447-471) over H steps of which the last N = H - W are shoot steps
+ * (1 <= W <= H - 1). sim [H][B]; q1, q2, rp, rw, rwpi, nq [N][B] (shoot step t = W + i at row i); w [B].
+ *   td [N][B]:   td = rwpi + discount nq (one step; rho ** shoot_count is 1 in the reference)
+ *   rows [5][B]: sum_{t<H} sim, sum_i (rp - rw)^2, sum_i (q1 - td)^2 + (q2 - td)^2, min(sum_i |q1 - td| + |q2 - td|,
+ *                1e4), total = sim_coef min(sim, 1e4) + reward_coef min(rew, 1e4) + value_coef min(val, 1e4)
+ *   scal [6]:    the means of sim, rew, val, total; weighted = mean(total) mean(w) (the reference's mean over the
+ *                [B, B] broadcast of total [B, 1] * w [B]); mean(w). */
+typedef struct tdmpc_drnn_sim_loss_args {
+    const float *sim, *q1, *q2, *rp, *rw, *rwpi, *nq, *w;
+    int32_t H, W, B;
+    float sim_coef, reward_coef, value_coef, discount;
+} tdmpc_drnn_sim_loss_args;
+int tdmpc_drnn_sim_loss_forward(const tdmpc_drnn_sim_loss_args* a, float* td, float* rows, float* scal, void* stream);
+/* gw [1] = dL / dweighted -> dsim [H][B], dq1, dq2, drp [N][B] (each may be null) in one elementwise pass; the clamps
+ * pass gradient where the sum is <= 1e4. */
+int tdmpc_drnn_sim_loss_backward(const tdmpc_drnn_sim_loss_args* a, const float* td, const float* rows,
+                                 const float* scal, const float* gw, float* dsim, float* dq1, float* dq2, float* drp,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,7 +38,8 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_drnn_train_version", "tdmpc_drnn_train_sizes_for", "tdmpc_drnn_next_fwd", "tdmpc_drnn_next_bwd",
             "tdmpc_drnn_simloss_fwd", "tdmpc_drnn_simloss_bwd", "tdmpc_drnn_intrinsic_workspace_floats",
             "tdmpc_drnn_intrinsic_fwd", "tdmpc_drnn_intrinsic_finish", "tdmpc_drnn_loss_forward",
-            "tdmpc_drnn_loss_backward")
+            "tdmpc_drnn_loss_backward", "tdmpc_drnn_intrinsic_chain_workspace_floats",
+            "tdmpc_drnn_intrinsic_chain_fwd", "tdmpc_drnn_sim_loss_forward", "tdmpc_drnn_sim_loss_backward")
 DRNN_VERSION = 2
 DRNN_TRAIN_VERSION = 1
 DT_NEXT_TENSORS, DT_LOSS_TENSORS, DT_MAX_ROWS = 22, 8, 4096   # include/tdmpc_drnn_learner.h
@@ -166,6 +167,12 @@ class DrnnLossArgs(C.Structure):   # tdmpc_drnn_loss_args (include/tdmpc_drnn_le
                [(n, C.c_float) for n in ("sim_coef", "reward_coef", "value_coef", "discount", "td_lambda")]
 
 
+class DrnnSimLossArgs(C.Structure):   # tdmpc_drnn_sim_loss_args (include/tdmpc_drnn_learner.h)
+    _fields_ = [(n, C.c_void_p) for n in ("sim", "q1", "q2", "rp", "rw", "rwpi", "nq", "w")] + \
+               [("H", C.c_int32), ("W", C.c_int32), ("B", C.c_int32)] + \
+               [(n, C.c_float) for n in ("sim_coef", "reward_coef", "value_coef", "discount")]
+
+
 class Sizes(C.Structure):
     _fields_ = [("packed_weight_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t),
                 ("noise_floats_per_env", C.c_size_t)]
@@ -259,6 +266,10 @@ def lib():
     L.tdmpc_drnn_intrinsic_finish.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.tdmpc_drnn_loss_forward.argtypes = [C.POINTER(DrnnLossArgs), vp, vp, vp, vp]
     L.tdmpc_drnn_loss_backward.argtypes = [C.POINTER(DrnnLossArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tdmpc_drnn_intrinsic_chain_workspace_floats.argtypes = [dd, i32, i32, C.POINTER(sz)]
+    L.tdmpc_drnn_intrinsic_chain_fwd.argtypes = [dd, pv, i32, pv, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    L.tdmpc_drnn_sim_loss_forward.argtypes = [C.POINTER(DrnnSimLossArgs), vp, vp, vp, vp]
+    L.tdmpc_drnn_sim_loss_backward.argtypes = [C.POINTER(DrnnSimLossArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED:
         if not hasattr(L, name) and not (name.startswith("tdmpc_debug_") and os.environ.get("TDMPC_LIB_PATH")):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")

@@ -20,6 +20,13 @@
 //     running statistics S times in segment order, dt_gate_fwd<true> reads no hidden state;
 //   * dt_intrinsic_finish: float64 moments of the losses, the RunningMeanStd update on the device, the rewards;
 //   * dt_loss_rows / dt_loss_means / dt_loss_bwd: the TD-lambda targets and the loss composition, forward and backward.
+// For TdMpcSimDssm.update (tdmpc_similarity_drnn.py:373-496):
+//   * tdmpc_drnn_intrinsic_chain_fwd: intrinsic_rewards with ONE hidden state carried through the S = H + 1 closed-loop
+//     steps. weight_ih's product does not depend on the hidden state and runs once over all S B rows; the recurrence is
+//     either a launch chain (per step h weight_hh^T + dt_gate_fwd) or dt_gru_chain, one launch in which a workgroup owns
+//     16 batch rows for all steps (the cell has only row LayerNorms, so rows are independent through time);
+//   * dt_sloss_rows / dt_sloss_means / dt_sloss_bwd: the one-step TD targets and the loss composition over the shoot
+//     steps W..H-1 (the similarity term over all H), forward and backward.
 // Every reduction runs in a fixed order: wave butterflies, LDS sums over waves in wave order, partials in index order.
 #include <hip/hip_runtime.h>
 
@@ -543,6 +550,179 @@ __global__ void __launch_bounds__(256) dt_loss_bwd(const tdmpc_drnn_loss_args a,
     if (dq2) dq2[i] = 2.f * (a.q2[i] - td[i]) * dv;
 }
 
+// ---- The GRU recurrence of tdmpc_drnn_intrinsic_chain_fwd (mode 1) in one launch. A workgroup owns CROWS batch rows
+// and walks the S segments itself: the h tile [CROWS][Hd] and the step's weight_hh(h) [CROWS][3Hd] live in LDS,
+// weight_hh [3Hd][Hd] streams from L2 every step, the product runs on the exact f32 MFMA (v_mfma_f32_16x16x4_f32; lane
+// (r = lane % 16, q = lane / 16) loads k0 + 4q .. k0 + 4q + 3 of row r of h and of output column r of the tile as one
+// float4 each, so the MFMA's four k slots of a step are k0 + i, k0 + 4 + i, k0 + 8 + i, k0 + 12 + i: a permutation of
+// the sum), wave w of the 16 takes the 16-column tiles w, w + 16, ...; then wave w runs dt_gate_fwd's epilogue on row w
+// and writes h' to hn[s] and back into the tile. Rows past B compute on zeros and write nothing.
+constexpr int CROWS = 16;
+constexpr int CWAVES = 16;   // one wave per row in the epilogue, 3 Hd / 16 column tiles over 16 waves in the product
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+
+struct ChainArgs {
+    const float* gi;         // [S B, 3Hd]: [z | a] weight_ih^T
+    const float* whh;        // [3Hd, Hd]
+    const float* g[3]; const float* b[3];
+    float* hn;               // [S B, Hd]: every segment's h'
+    int S, B, Hd;
+};
+
+__global__ void __launch_bounds__(64 * CWAVES) dt_gru_chain(const ChainArgs a) {
+    extern __shared__ float lds[];
+    const int Hd = a.Hd, B = a.B, hs = Hd + 4, ps = 3 * Hd + 4;   // row strides: 16-B aligned, off the bank grid
+    float* ht = lds;                   // [CROWS][hs]
+    float* pre = lds + CROWS * hs;     // [CROWS][ps]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int row0 = blockIdx.x * CROWS;
+    for (int e = threadIdx.x; e < CROWS * hs; e += 64 * CWAVES) ht[e] = 0.f;
+    bool ok[4];
+    float g[3][4], bb[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        ok[i] = c < Hd;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            g[k][i] = a.g[k][ok[i] ? c : 0];
+            bb[k][i] = a.b[k][ok[i] ? c : 0];
+        }
+    }
+    __syncthreads();
+    for (int s = 0; s < a.S; ++s) {
+        if (s) {
+            for (int t = wave; t < 3 * Hd / 16; t += CWAVES) {
+                const float* wrow = a.whh + (size_t)(t * 16 + r) * Hd + 4 * q;
+                const float* hrow = ht + r * hs + 4 * q;
+                floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+                for (int k0 = 0; k0 < Hd; k0 += 32) {   // (Hd is a multiple of 32: two groups of 16 k in flight)
+                    const float4 w0 = *reinterpret_cast<const float4*>(wrow + k0);
+                    const float4 w1 = *reinterpret_cast<const float4*>(wrow + k0 + 16);
+                    const float4 h0 = *reinterpret_cast<const float4*>(hrow + k0);
+                    const float4 h1 = *reinterpret_cast<const float4*>(hrow + k0 + 16);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h0.x, w0.x, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h0.y, w0.y, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h0.z, w0.z, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h0.w, w0.w, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h1.x, w1.x, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h1.y, w1.y, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h1.z, w1.z, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(h1.w, w1.w, acc, 0, 0, 0);
+                }
+                // D: lane (r, q) holds rows 4q .. 4q + 3 of column r
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pre[(4 * q + i) * ps + t * 16 + r] = acc[i];
+            }
+            __syncthreads();
+        }
+        for (int lr = wave; lr < CROWS; lr += CWAVES) {
+            const int b = row0 + lr;
+            if (b >= B) break;   // (wave-uniform)
+            const size_t r3 = ((size_t)s * B + b) * 3 * Hd, r1 = ((size_t)s * B + b) * Hd;
+            const float* pr = pre + lr * ps;
+            float sr[4], su[4], ghn[4], gin[4], hp[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int cc = ok[i] ? lane + 64 * i : 0;
+                sr[i] = a.gi[r3 + cc] + (s ? pr[cc] : 0.f);
+                su[i] = a.gi[r3 + Hd + cc] + (s ? pr[Hd + cc] : 0.f);
+                gin[i] = a.gi[r3 + 2 * Hd + cc];
+                ghn[i] = s ? pr[2 * Hd + cc] : 0.f;
+                hp[i] = ht[lr * hs + cc];
+            }
+            float xr[4], xu[4], xn[4], sn[4];
+            ln_row(sr, ok, Hd, xr);
+            ln_row(su, ok, Hd, xu);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sn[i] = gin[i] + sigmoid_f(xr[i] * g[0][i] + bb[0][i]) * ghn[i];
+            ln_row(sn, ok, Hd, xn);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = lane + 64 * i;
+                if (!ok[i]) continue;
+                const float u = sigmoid_f(xu[i] * g[1][i] + bb[1][i]);
+                const float n = tanhf(xn[i] * g[2][i] + bb[2][i]);
+                const float hn = u * n + (1.f - u) * hp[i];
+                a.hn[r1 + c] = hn;
+                ht[lr * hs + c] = hn;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- TdMpcSimDssm.update's loss composition (tdmpc_drnn_learner.h): as dt_loss_* with one-step TD targets, the
+// reward / value / priority sums over the N = H - W shoot steps and every term under the priority weights.
+__global__ void __launch_bounds__(256) dt_sloss_rows(const tdmpc_drnn_sim_loss_args a, float* td, float* rows) {
+    const int b = blockIdx.x * 256 + threadIdx.x, H = a.H, N = a.H - a.W, B = a.B;
+    if (b >= B) return;
+    float sim = 0.f, rew = 0.f, val = 0.f, pri = 0.f;
+    for (int t = 0; t < H; ++t) sim += a.sim[(size_t)t * B + b];
+    for (int t = 0; t < N; ++t) {
+        const size_t i = (size_t)t * B + b;
+        const float tg = a.rwpi[i] + a.discount * a.nq[i];
+        const float dr = a.rp[i] - a.rw[i], d1 = a.q1[i] - tg, d2 = a.q2[i] - tg;
+        td[i] = tg;
+        rew += dr * dr;
+        val += d1 * d1 + d2 * d2;
+        pri += fabsf(d1) + fabsf(d2);
+    }
+    rows[b] = sim;
+    rows[B + b] = rew;
+    rows[2 * B + b] = val;
+    rows[3 * B + b] = fminf(pri, LOSS_CLAMP);
+    rows[4 * B + b] = a.sim_coef * fminf(sim, LOSS_CLAMP) + a.reward_coef * fminf(rew, LOSS_CLAMP) +
+                      a.value_coef * fminf(val, LOSS_CLAMP);
+}
+
+__global__ void __launch_bounds__(512) dt_sloss_means(const tdmpc_drnn_sim_loss_args a, const float* rows, float* scal) {
+    __shared__ float red[5][8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, B = a.B;
+    float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int b = tid; b < B; b += 512) {
+        s[0] += rows[b];
+        s[1] += rows[B + b];
+        s[2] += rows[2 * B + b];
+        s[3] += rows[4 * B + b];
+        s[4] += a.w[b];
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const float v = wsum(s[k]);
+        if (lane == 0) red[k][wave] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float m[5];
+        for (int k = 0; k < 5; ++k) {
+            float v = 0.f;
+            for (int w = 0; w < 8; ++w) v += red[k][w];
+            m[k] = v / (float)B;
+        }
+        scal[0] = m[0]; scal[1] = m[1]; scal[2] = m[2]; scal[3] = m[3];
+        scal[4] = m[3] * m[4];
+        scal[5] = m[4];
+    }
+}
+
+__global__ void __launch_bounds__(256) dt_sloss_bwd(const tdmpc_drnn_sim_loss_args a, const float* td, const float* rows,
+                                                    const float* scal, const float* gw, float* dsim, float* dq1,
+                                                    float* dq2, float* drp) {
+    const int B = a.B;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)a.H * B) return;
+    const int b = (int)(i % B);
+    const float dtot = gw[0] * scal[5] / (float)B;
+    if (dsim) dsim[i] = rows[b] <= LOSS_CLAMP ? a.sim_coef * dtot : 0.f;
+    if (i >= (long)(a.H - a.W) * B) return;
+    const float dr = rows[B + b] <= LOSS_CLAMP ? a.reward_coef * dtot : 0.f;
+    const float dv = rows[2 * B + b] <= LOSS_CLAMP ? a.value_coef * dtot : 0.f;
+    if (drp) drp[i] = 2.f * (a.rp[i] - a.rw[i]) * dr;
+    if (dq1) dq1[i] = 2.f * (a.q1[i] - td[i]) * dv;
+    if (dq2) dq2[i] = 2.f * (a.q2[i] - td[i]) * dv;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
@@ -729,10 +909,13 @@ tdmpc_lg_job with_elu_bwd(tdmpc_lg_job j, const float* y) {
 // One grouped launch on the exact f32 MFMA: 64 x 64 register tiles once the largest job fills the chip with them.
 // tile_rows > 0: choose the tile as for jobs of that many rows (the two tiles sum K in different orders; the segmented
 // pass keeps the bits of a one-segment call).
-int gemm(const tdmpc_lg_job* jobs, int n, void* stream, int tile_rows = 0) {
+// tile_cols > 0 likewise: as if the widest job of the launch had that many columns (a product that shares its launch
+// with a wider one in tdmpc_drnn_next_fwd).
+int gemm(const tdmpc_lg_job* jobs, int n, void* stream, int tile_rows = 0, int tile_cols = 0) {
     long big = 0;
     for (int q = 0; q < n; ++q)
-        big = std::max(big, (long)(((tile_rows ? tile_rows : jobs[q].m) + 63) / 64) * ((jobs[q].n + 63) / 64));
+        big = std::max(big, (long)(((tile_rows ? tile_rows : jobs[q].m) + 63) / 64) *
+                                (((tile_cols ? tile_cols : jobs[q].n) + 63) / 64));
     return tdmpc_lg_gemm(jobs, n, (big >= 256 ? 2 : 1) | TDMPC_LG_TILE_EXACT, stream);
 }
 
@@ -812,6 +995,42 @@ int check_segments(const tdmpc_drnn_dims* d, int segments, int seg_rows, Shape& 
 
 bool loss_args_ok(const tdmpc_drnn_loss_args* a) {
     return a && a->sim && a->q1 && a->q2 && a->rp && a->rw && a->rwpi && a->nq && a->w && a->H > 0 && a->B > 0;
+}
+
+// tdmpc_drnn_intrinsic_chain_fwd's workspace. hn comes first (tdmpc_drnn_learner.h promises it). gh / gate / lnx / lnr
+// hold one step of seg_rows rows (the launch chain's dt_gate_fwd writes them; nothing reads them back).
+struct ChainWs { float *hn, *gi, *gh, *gate, *lnx, *lnr, *p1, *bnx, *bnr, *e, *part, *zo, *pred; size_t total; };
+ChainWs chain_ws(const Shape& s, int segments, int seg_rows, float* base) {
+    Bump b(base);
+    ChainWs v;
+    const size_t R = s.R, B = seg_rows;
+    v.hn = b.take(R * s.Hd);
+    v.gi = b.take(R * 3 * s.Hd);
+    v.gh = b.take(B * 3 * s.Hd);
+    v.gate = b.take(B * 3 * s.Hd);
+    v.lnx = b.take(B * 3 * s.Hd);
+    v.lnr = b.take(B * 4);
+    v.p1 = b.take(R * M);
+    v.bnx = b.take(R * M);
+    v.bnr = b.take((size_t)segments * M);
+    v.e = b.take(R * M);
+    v.part = b.take((size_t)segments * chunks(seg_rows) * 2 * M);
+    v.zo = b.take(R * s.L);
+    v.pred = b.take(R * s.L);
+    v.total = b.off;
+    return v;
+}
+
+int check_chain(const tdmpc_drnn_dims* d, int segments, int seg_rows, int warm, Shape& s) {
+    if (int rc = check_segments(d, segments, seg_rows, s)) return rc;
+    if (warm < 0 || warm >= segments)
+        return bad("drnn_learner: warm %ld is not in [0, segments = %ld)", warm, segments);
+    return 0;
+}
+
+bool sim_loss_args_ok(const tdmpc_drnn_sim_loss_args* a) {
+    return a && a->sim && a->q1 && a->q2 && a->rp && a->rw && a->rwpi && a->nq && a->w && a->B > 0 && a->W >= 1 &&
+           a->W < a->H;
 }
 
 }  // namespace
@@ -907,6 +1126,128 @@ int tdmpc_drnn_loss_backward(const tdmpc_drnn_loss_args* a, const float* td, con
     hipLaunchKernelGGL(dt_loss_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a, td, rows,
                        scal, gw, dsim, dq1, dq2, drp);
     return launched("loss_bwd");
+}
+
+int tdmpc_drnn_intrinsic_chain_workspace_floats(const tdmpc_drnn_dims* dims, int32_t segments, int32_t seg_rows,
+                                                size_t* out) {
+    Shape s;
+    if (int rc = check_segments(dims, segments, seg_rows, s)) return rc;
+    if (int rc = need(out, "out")) return rc;
+    *out = chain_ws(s, segments, seg_rows, nullptr).total;
+    return 0;
+}
+
+int tdmpc_drnn_intrinsic_chain_fwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_next, float* const* P,
+                                   int32_t n_loss, const float* z, const float* a, const float* keys, int32_t segments,
+                                   int32_t seg_rows, int32_t warm, int32_t mode, float* loss, float* h_out,
+                                   float* workspace, size_t workspace_floats, void* stream) {
+    Shape s;
+    if (int rc = check_chain(dims, segments, seg_rows, warm, s)) return rc;
+    if (mode != 0 && mode != 1) return bad("drnn_learner: intrinsic_chain_fwd mode %ld (0: launch chain, 1: one launch)", mode);
+    if (int rc = need_table(T, n_next, TDMPC_DT_NEXT_TENSORS, "next_tensors", true)) return rc;
+    if (int rc = need_table(P, n_loss, TDMPC_DT_LOSS_TENSORS, "loss_tensors", true)) return rc;
+    const void* ptrs[] = {z, a, keys, loss, h_out, workspace};
+    const char* names[] = {"z", "a", "keys", "loss", "h_out", "workspace"};
+    for (int i = 0; i < 6; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const ChainWs W = chain_ws(s, segments, seg_rows, workspace);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L, A = s.A, Hd = s.Hd, S = segments, B = seg_rows;
+
+    // 1: [z | a] weight_ih^T of all S B rows (the inputs do not depend on the hidden state)
+    tdmpc_lg_job j = job(R, 3 * Hd, W.gi, 3 * Hd, seg(z, L, T[WIH], L + A, L, 0, 0));
+    j.seg[1] = seg(a, A, T[WIH] + L, L + A, A, 0, 0);
+    j.nseg = 2;
+    if (int rc = gemm(&j, 1, stream, B)) return rc;
+
+    // 2: the recurrence, h_0 = 0
+    if (mode == 1) {
+        ChainArgs c;
+        memset(&c, 0, sizeof c);
+        c.gi = W.gi; c.whh = T[WHH]; c.hn = W.hn; c.S = S; c.B = B; c.Hd = Hd;
+        for (int k = 0; k < 3; ++k) { c.g[k] = T[LRG + 2 * k]; c.b[k] = T[LRB + 2 * k]; }
+        const size_t lds = (size_t)CROWS * (Hd + 4 + 3 * Hd + 4) * sizeof(float);   // 64.5 KB at Hd = 256
+        static bool attr = false;
+        if (!attr) {
+            if (hipFuncSetAttribute((const void*)dt_gru_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+                hipSuccess)
+                return launched("gru_chain (LDS attribute)");
+            attr = true;
+        }
+        hipLaunchKernelGGL(dt_gru_chain, dim3((B + CROWS - 1) / CROWS), dim3(64 * CWAVES), lds, st, c);
+        if (int rc = launched("gru_chain")) return rc;
+    } else {
+        GateArgs g;
+        memset(&g, 0, sizeof g);
+        for (int k = 0; k < 3; ++k) { g.g[k] = T[LRG + 2 * k]; g.b[k] = T[LRB + 2 * k]; }
+        g.gate = W.gate; g.lnx = W.lnx; g.lnr = W.lnr; g.rows = B; g.Hd = Hd;
+        for (int t = 0; t < S; ++t) {
+            float* hn = W.hn + (size_t)t * B * Hd;
+            g.gi = W.gi + (size_t)t * B * 3 * Hd;
+            g.hn = hn; g.h_out = hn;
+            if (t == 0) {
+                hipLaunchKernelGGL(dt_gate_fwd<true>, dim3((B + 3) / 4), dim3(256), 0, st, g);
+            } else {
+                g.h = hn - (size_t)B * Hd;
+                g.gh = W.gh;
+                j = linear(B, 3 * Hd, Hd, g.h, T[WHH], nullptr, W.gh);
+                if (int rc = gemm(&j, 1, stream)) return rc;
+                hipLaunchKernelGGL(dt_gate_fwd<false>, dim3((B + 3) / 4), dim3(256), 0, st, g);
+            }
+            if (int rc = launched("gate_fwd")) return rc;
+        }
+    }
+    if (hipMemcpyAsync(h_out, W.hn + (size_t)(S - 1) * B * Hd, (size_t)B * Hd * sizeof(float), hipMemcpyDeviceToDevice,
+                       st) != hipSuccess)
+        return launched("memcpy");
+
+    // 3: prior_mlp over every segment (the warm-up steps move its BatchNorm's running statistics too)
+    j = linear(R, M, Hd, W.hn, T[P0W], T[P0B], W.p1);
+    if (int rc = gemm(&j, 1, stream, B)) return rc;
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.p1; b.g = T[P1G]; b.b = T[P1B]; b.rmean = T[P1RM]; b.rvar = T[P1RV];
+    b.xhat = W.bnx; b.rstd = W.bnr; b.e = W.e; b.part = W.part; b.rows = R; b.C = M;
+    b.seg = B; b.nseg = S;
+    if (int rc = bn_forward(b, st)) return rc;
+
+    // 4: prior_mlp.3, _predictor and the cosine loss over segments warm .. S - 1
+    const int R2 = (S - warm) * B;
+    const size_t o = (size_t)warm * B;
+    if (warm && hipMemsetAsync(loss, 0, o * sizeof(float), st) != hipSuccess) return launched("memset");
+    j = linear(R2, L, M, W.e + o * M, T[P3W], T[P3B], W.zo);
+    if (int rc = gemm(&j, 1, stream, B, M)) return rc;   // (next_fwd launches it beside _reward.2, M columns)
+    j = linear(R2, M, L, W.zo, P[P0W], P[P0B], W.p1);
+    if (int rc = gemm(&j, 1, stream, B)) return rc;
+    b.g = P[P1G]; b.b = P[P1B]; b.rmean = P[P1RM]; b.rvar = P[P1RV];
+    b.rows = R2; b.nseg = S - warm;
+    if (int rc = bn_forward(b, st)) return rc;
+    j = linear(R2, L, M, W.e, P[P3W], P[P3B], W.pred);
+    if (int rc = gemm(&j, 1, stream, B)) return rc;
+    hipLaunchKernelGGL(dt_cos_fwd, dim3((R2 + 3) / 4), dim3(256), 0, st, W.pred, keys + o * L, loss + o, R2, L);
+    return launched("cos_fwd");
+}
+
+int tdmpc_drnn_sim_loss_forward(const tdmpc_drnn_sim_loss_args* a, float* td, float* rows, float* scal, void* stream) {
+    if (!sim_loss_args_ok(a) || !td || !rows || !scal)
+        return bad("drnn_learner: sim_loss_forward: a null pointer, B < 1 or W outside [1, H - 1]");
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(dt_sloss_rows, dim3((a->B + 255) / 256), dim3(256), 0, st, *a, td, rows);
+    if (int rc = launched("sloss_rows")) return rc;
+    hipLaunchKernelGGL(dt_sloss_means, dim3(1), dim3(512), 0, st, *a, rows, scal);
+    return launched("sloss_means");
+}
+
+int tdmpc_drnn_sim_loss_backward(const tdmpc_drnn_sim_loss_args* a, const float* td, const float* rows,
+                                 const float* scal, const float* gw, float* dsim, float* dq1, float* dq2, float* drp,
+                                 void* stream) {
+    if (!sim_loss_args_ok(a) || !td || !rows || !scal || !gw)
+        return bad("drnn_learner: sim_loss_backward: a null pointer, B < 1 or W outside [1, H - 1]");
+    const long n = (long)a->H * a->B;
+    hipLaunchKernelGGL(dt_sloss_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a, td, rows,
+                       scal, gw, dsim, dq1, dq2, drp);
+    return launched("sloss_bwd");
 }
 
 int tdmpc_drnn_train_version(void) { return TDMPC_DRNN_TRAIN_VERSION; }

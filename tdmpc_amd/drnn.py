@@ -6,7 +6,12 @@ namespace), attributes (`cfg`, `device`, `std`, `mixture_coef`, `model`, `model_
 and `state_dict / save / load`. Planning runs in the HIP library (include/tdmpc_drnn.h): the rollout step is
 drnn_step_kernel (a fused layer-normed GRU cell + prior MLP + reward MLP), everything else -- the encoder, the
 terminal pi / Q chain kernels, the CEM kernel, the noise layout and the reference-order draws -- is the TDMPC
-planner's. The learner (`update`, the similarity loss) and plan2explore are not part of this class.
+planner's. plan2explore is not part of this class.
+
+Learning: `update(replay_buffer, step)`, `update_pi(zs)`, `optim` / `pi_optim` and `reward_rms` as the reference's
+(:269-286, :373-496), run by `tdmpc_amd.drnn_learner.DssmSimLearner` through `DssmLearning`, the block of lazily built
+learner state that this agent and `TdIcemDrnn` share: an agent that only plans allocates none of it, and a cfg the
+learner refuses (cfgs/default.yaml's `warmup_len: 0`, the dog task's batch of 2048) still plans.
 
 `plan_batch(obs[B], hidden[B], ...)` plans B environments in one call, each with its own memory, `_prev_mean` and
 plan horizon; the envs of one call must agree on the horizon (the kernels take one).
@@ -101,8 +106,53 @@ class DrnnPlanner(HipPlanner):
         return out
 
 
-class TdMpcDrnn(Agent):
-    """Drop-in for the reference `TdMpcSimDssm` planning interface (tdmpc_similarity_drnn.py:87-267)."""
+class DssmLearning:
+    """The learning half of a DSSM agent: `learner` (the class named by LEARNER in tdmpc_amd.drnn_learner) is built on
+    first use and sets `optim` / `pi_optim`; reading either, or `reward_rms`, builds it."""
+
+    LEARNER = "DssmLearner"
+    _learner = None
+
+    @property
+    def learner(self):
+        if self._learner is None:
+            from . import drnn_learner
+            self._learner = getattr(drnn_learner, self.LEARNER)(self, graph=self.graph)   # sets optim / pi_optim
+        return self._learner
+
+    @property
+    def reward_rms(self):
+        return self.learner.reward_rms
+
+    def _optim_get(name):
+        def get(self):
+            self.learner
+            return self.__dict__["_" + name]
+        return property(get, lambda self, v: self.__dict__.__setitem__("_" + name, v))
+
+    optim, pi_optim = _optim_get("optim"), _optim_get("pi_optim")
+    del _optim_get
+
+    def update_pi(self, zs):
+        """The reference's `update_pi` -> pi_loss (float; synchronises)."""
+        try:
+            return float(self.learner.update_pi(zs))
+        finally:
+            self.planner._packed_key = None   # the policy changed in place: the next plan() repacks
+
+    def _learn(self, replay_buffer, step, sync_metrics, noise):
+        """One update -> ({metric: value}, explore_coef): floats, or with sync_metrics=False 0-d device tensors and no
+        synchronisation. Sets `std` from std_schedule as the reference's update does."""
+        from .drnn_learner import METRICS
+        self.std = linear_schedule(self.cfg.std_schedule, step)
+        m, coef = self.learner.update(replay_buffer, step, noise)
+        return dict(zip(METRICS, m.tolist() if sync_metrics else list(m.unbind(0)))), coef
+
+
+class TdMpcDrnn(DssmLearning, Agent):
+    """Drop-in for the reference `TdMpcSimDssm` (tdmpc_similarity_drnn.py:87-496): plan, update, update_pi."""
+
+    LEARNER = "DssmSimLearner"
 
     MAX_GRAPHS = 8   # captured plans kept per agent (one per (horizon, iterations, batch, num_pi, eval_mode))
     METRICS0 = {"intrinsic_reward_mean": 0.0, "external_reward_mean": 0.0, "current_std": 0.0}
@@ -117,6 +167,14 @@ class TdMpcDrnn(Agent):
         self._plan_H = np.ones(max_batch, dtype=np.int64)                            # :108, one per env
         self._has_prev = np.zeros(max_batch, dtype=bool)
         self._prev_H = np.zeros(max_batch, dtype=np.int64)
+
+    # ------------------------------------------------------------------ learning (:269-286, :373-496)
+    def update(self, replay_buffer, step, sync_metrics=True, noise=None):
+        """:404-496 -> the reference's metrics dict and `intrinsic_batch_reward_mean` (floats; sync_metrics=False: 0-d
+        device tensors, no synchronisation). noise: optional explicit draws (DssmSimLearner; parity tests)."""
+        out, _ = self._learn(replay_buffer, step, sync_metrics, noise)
+        out["mixture_coef"] = self.mixture_coef
+        return out
 
     # ------------------------------------------------------------------ reference API
     @property

@@ -20,8 +20,9 @@ with one normal_, the spectrum normals with another and turns them into every co
 `tdmpc_drnn_colored_noise` launch; `plan(..., noise=IcemNoise-like)` takes explicit draws (parity tests).
 
 Learning: `update(replay_buffer, step)`, `update_pi(zs)`, `optim` / `pi_optim`, `explore_coef` and `reward_rms` as the
-reference's (:367-384, :421-553), run by `tdmpc_amd.drnn_learner.DssmLearner`, which is built on first use (an agent
-that only plans allocates none of it, and a cfg the learner refuses -- the dog task's batch of 2048 -- still plans).
+reference's (:367-384, :421-553), run by `tdmpc_amd.drnn_learner.DssmLearner` through `tdmpc_amd.drnn.DssmLearning`,
+which builds it on first use (an agent that only plans allocates none of it, and a cfg the learner refuses -- the dog
+task's batch of 2048 -- still plans).
 """
 from __future__ import annotations
 
@@ -31,7 +32,7 @@ import torch
 from . import _lib
 from .colored_noise import irfft_matrices, powerlaw_psd_gaussian, spectrum_rows
 from .config import linear_schedule
-from .drnn import DrnnPlanner
+from .drnn import DrnnPlanner, DssmLearning
 from .dssm import DSSM, check_dssm_cfg
 from .icem import (IcemBuffers, icem_counts, icem_draw_reference, icem_layout, icem_load, icem_params,
                    icem_trace_values)
@@ -80,7 +81,7 @@ class IcemDrnnPlanner(IcemBuffers, DrnnPlanner):
     entry, sizes_abi = "tdmpc_drnn_plan_icem", "tdmpc_drnn_icem_sizes_for"
 
 
-class TdIcemDrnn(Agent):
+class TdIcemDrnn(DssmLearning, Agent):
     """Drop-in for the reference `TdICemSimDssm` planning interface (tdmpc_icem_similarity_drnn.py:81-272)."""
 
     MAX_GRAPHS = 8   # captured plans kept per agent
@@ -110,42 +111,10 @@ class TdIcemDrnn(Agent):
         self._learner = None
 
     # ------------------------------------------------------------------ learning (:367-384, :421-553)
-    @property
-    def learner(self):
-        if self._learner is None:
-            from .drnn_learner import DssmLearner
-            self._learner = DssmLearner(self, graph=self.graph)   # sets optim / pi_optim
-        return self._learner
-
-    @property
-    def reward_rms(self):
-        return self.learner.reward_rms
-
-    # optim / pi_optim: DssmLearner.__init__ assigns them; reading one builds the learner
-    def _optim_get(name):
-        def get(self):
-            self.learner
-            return self.__dict__["_" + name]
-        return property(get, lambda self, v: self.__dict__.__setitem__("_" + name, v))
-
-    optim, pi_optim = _optim_get("optim"), _optim_get("pi_optim")
-    del _optim_get
-
-    def update_pi(self, zs):
-        """:367-384 -> pi_loss (float; synchronises)."""
-        try:
-            return float(self.learner.update_pi(zs))
-        finally:
-            self.planner._packed_key = None   # the policy changed in place: the next plan() repacks
-
     def update(self, replay_buffer, step, sync_metrics=True, noise=None):
         """:445-553 -> the reference's metrics dict (floats; sync_metrics=False: 0-d device tensors, no
         synchronisation). noise: optional 2H + 1 [B, A] TruncatedNormal draws (parity tests)."""
-        from .drnn_learner import METRICS
-        self.std = linear_schedule(self.cfg.std_schedule, step)              # :449
-        m, self.explore_coef = self.learner.update(replay_buffer, step, noise)
-        vals = m.tolist() if sync_metrics else list(m.unbind(0))
-        out = dict(zip(METRICS, vals))
+        out, self.explore_coef = self._learn(replay_buffer, step, sync_metrics, noise)   # (:449: std)
         out["current_explore_coef"] = self.explore_coef
         out["mixture_coef"] = self.mixture_coef
         return out

@@ -1,4 +1,5 @@
-"""The DSSM iCEM agent's learner: `TdICemSimDssm.update / update_pi / intrinsic_rewards` on the GPU.
+"""The DSSM agents' learners. `DssmLearner`, the iCEM agent's: `TdICemSimDssm.update / update_pi / intrinsic_rewards`
+on the GPU.
 
 Reference: src/algorithm/tdmpc_icem_similarity_drnn.py:367-384 (update_pi), :421-443 (intrinsic_rewards), :445-553
 (update). The math is the reference's (tests/drnn_update_ref.py restates it and is pinned bit for bit to the reference
@@ -30,6 +31,17 @@ The PyTorch path is the reference's own order of operations, call by call, in pl
 the CPU (tests/test_drnn_update_cpu.py holds it bit for bit to the restatement) and on the GPU with
 TDMPC_DSSM_LEARNER_HIP=0 (tools/drnn_update_bench.py's comparison leg: the PyTorch-ROCm update on the same GPU, its
 RunningMeanStd on the device as well, so that it synchronises no more than the HIP path).
+
+`DssmSimLearner(DssmLearner)` is the MPC agent's (`TdMpcSimDssm.update / intrinsic_rewards`,
+src/algorithm/tdmpc_similarity_drnn.py:373-496; tests/drnn_sim_update_ref.py restates it). It shares the
+optimisers, `update_pi`, the EMA, the graph driver and the RunningMeanStd state, and differs in three parts: the
+intrinsic rewards carry ONE hidden state through the H + 1 closed-loop steps, of which the first `warmup_len` only
+advance it (DssmTrainStep.intrinsic_chain_rewards); the update is `warmup_len` closed-loop `next` calls from the online
+encodings (gradient into the encoder) followed by `horizon - warmup_len` open-loop steps, every predicted latent
+augmented with Gaussian noise of scale 0.1; one-step TD targets, reward / value / priority sums over the open-loop
+steps only, the similarity sum over all H, and every term under the priority weights (`_DssmSimFusedLoss`). The
+reference admits 1 <= warmup_len <= horizon - 1 (it raises on an empty `torch.cat` at either end) and this class
+refuses the rest, and similarity_horizon != 1, by name.
 
 Optimisers: the reference builds them with rlpyt's `create_optimizer(model, optim_id, lr)`, a package that is not
 available to check its defaults against. Here `cfg.optim_id` 'adam' gives `torch.optim.Adam` and 'adamw'
@@ -115,9 +127,12 @@ class DssmLearner:
     """Owns the optimisers, the RunningMeanStd state and (in graph mode) the captured update graphs of one DSSM iCEM
     agent (`agent`: cfg, model, model_target, device and, when it plans, planner)."""
 
+    MAX_LOSSES = 1   # live similarity_loss calls of one update
+    check_cfg = staticmethod(check_learner_cfg)
+
     def __init__(self, agent, graph: bool = True, warmup: int = 3):
         cfg = self.cfg = agent.cfg
-        check_learner_cfg(cfg)
+        self.check_cfg(cfg)
         self.agent = agent
         model = agent.model
         p0 = next(model.parameters())
@@ -139,7 +154,7 @@ class DssmLearner:
         if self.hip:
             from .dssm_train import DssmTrainStep
             B, H = int(cfg.batch_size), int(cfg.horizon)
-            self.train_step = DssmTrainStep(model, max_rows=B, max_steps=H, max_loss_rows=H * B, max_losses=1)
+            self.train_step = DssmTrainStep(model, max_rows=B, max_steps=H, max_loss_rows=H * B, max_losses=self.MAX_LOSSES)
         self.calls = 0
         self._graphs = {}
         self.last = {}   # the last eager step's intermediate results (tests): intrinsic, priorities
@@ -352,3 +367,165 @@ class DssmLearner:
             # parameters changed in place (a graph replay does not bump tensor versions): repack for planning
             planner._packed_key = None
         return m
+
+
+def check_sim_learner_cfg(cfg):
+    """`check_learner_cfg` and what `TdMpcSimDssm.update` itself admits, each setting named."""
+    check_learner_cfg(cfg)
+    H, W = int(cfg.horizon), int(getattr(cfg, "warmup_len", 0))
+    if not 1 <= W <= H - 1:
+        raise ValueError(f"DssmSimLearner: warmup_len={W} is not in [1, horizon - 1 = {H - 1}]: the reference's update "
+                         f"concatenates an empty list of latents at warmup_len = 0 and at warmup_len = horizon")
+    sh = int(getattr(cfg, "similarity_horizon", 1))
+    if sh != 1:
+        raise NotImplementedError(f"DssmSimLearner: similarity_horizon={sh} is not supported (1 only: longer rollouts "
+                                  f"hand their last hidden state to the next start)")
+
+
+class DssmSimLearner(DssmLearner):
+    """The learner of `TdMpcDrnn` (`TdMpcSimDssm.update`, tdmpc_similarity_drnn.py:373-496). `step(buffer, noise)`:
+    noise = (2 (H - W) + 1 [B, A] TruncatedNormal draws -- H - W for the TD targets, H - W + 1 for update_pi --, H
+    [B, L] augmentation noises, added as they are: the reference's Normal(0, 0.1) samples), or None to draw on the
+    device."""
+
+    MAX_LOSSES = 2
+    check_cfg = staticmethod(check_sim_learner_cfg)
+    AUG_SCALE = 0.1   # helper.RandomAdditiveGaussianNoiseAug(cfg, scale=0.1), :103
+
+    def _draws(self, noise, B):
+        H, L = int(self.cfg.horizon), int(self.cfg.latent_dim)
+        if noise is not None:
+            return noise[0], list(noise[1])
+        return None, list((torch.randn(H, B, L, dtype=self.dtype, device=self.device) * self.AUG_SCALE).unbind(0))
+
+    def _step_hip(self, buffer, noise):
+        a, cfg, m, mt, ts = self.agent, self.cfg, self.agent.model, self.agent.model_target, self.train_step
+        H, W = int(cfg.horizon), int(cfg.warmup_len)
+        N = H - W
+        obs, next_obses, action, reward, idxs, weights = buffer.sample()
+        B = obs.shape[0]
+        eps, aug = self._draws(noise, B)
+        a.optim.zero_grad(set_to_none=True)
+        # the latents the gradient reaches: obs and next_obses[:W] (zs_traj[0 .. W]); the later online encodings feed
+        # only no_grad consumers
+        zg = m.h(torch.cat([obs.unsqueeze(0), next_obses[:W]]).reshape((W + 1) * B, -1)).view(W + 1, B, -1)
+        with torch.no_grad():
+            flat = next_obses.reshape((H + 1) * B, -1)
+            nz_on, nz_tg = m.h(flat), mt.h(flat)                    # [(H + 1) B, L]: online, target
+        # :428-434: the closed-loop warm-up and its similarity loss
+        hidden = m.init_hidden_state(B, obs.device)
+        queries = []
+        for i in range(W):
+            zp, hidden, _ = ts.next(zg[i], action[i], hidden)
+            queries.append(zp + aug[i])
+        sim_w = ts.similarity_loss(queries, nz_tg[:W * B])
+        with torch.no_grad():
+            # :373-402, one hidden state through the H + 1 steps
+            z_traj = torch.cat([zg[0].detach(), nz_on[:H * B]])
+            intrinsic, reward_pi = ts.intrinsic_chain_rewards(z_traj, action.reshape((H + 1) * B, -1), nz_tg, H + 1, W,
+                                                              self.rms, self.coef, reward.reshape(-1))
+            # :339-344: min target Q at the online next latents under the online policy, the shoot steps at once
+            x = nz_on[W * B:H * B]
+            act = m.pi(x, cfg.min_std, eps=None if eps is None else torch.cat(list(eps[:N])))
+            next_q = torch.min(*mt.Q(x, act)).view(N, B)
+        # :443-455: the open-loop shoot
+        zt, zin, zout, rps = zg[W], [], [], []
+        for t in range(W, H):
+            zin.append(zt)
+            zt, hidden, r = ts.next(zt, action[t], hidden)
+            zt = zt + aug[t]
+            zout.append(zt)
+            rps.append(r)
+        x = torch.cat([torch.stack(zin), action[W:H]], dim=-1).view(N * B, -1)
+        Q1, Q2 = m._Q1(x).view(N, B), m._Q2(x).view(N, B)
+        sim_s = ts.similarity_loss(zout, nz_tg[W * B:H * B])
+        from .dssm_train import _DssmSimFusedLoss
+        scal, rows, _ = _DssmSimFusedLoss.apply(
+            torch.cat([sim_w, sim_s]).view(H, B), Q1, Q2, torch.stack(rps).view(N, B), reward[W:H].reshape(N, B),
+            reward_pi.view(H + 1, B)[W:H], next_q, weights,
+            (float(cfg.similarity_coef), float(cfg.reward_coef), float(cfg.value_coef), float(cfg.discount)))
+        weighted = scal[4]
+        weighted.register_hook(lambda grad: grad * (1 / H))
+        weighted.backward()
+        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
+        a.optim.step()
+        return self._finish(buffer, idxs, rows[3].view(B, 1), [zg[W].detach()] + [t.detach() for t in zout], eps, N,
+                            (scal[0], scal[1], scal[2], scal[3]), weighted, grad_norm, intrinsic.view(H + 1, B, 1))
+
+    def _intrinsic_torch(self, obs, next_obses, action):
+        """:373-402 call by call at similarity_horizon 1, the RunningMeanStd by `rms_update`."""
+        m, mt, cfg = self.agent.model, self.agent.model_target, self.cfg
+        H, W = int(cfg.horizon), int(cfg.warmup_len)
+        with torch.no_grad():
+            zs_target = mt.h(next_obses)
+            zs_traj = m.h(torch.cat([obs.unsqueeze(0), next_obses], dim=0))
+            hidden = m.init_hidden_state(obs.shape[0], obs.device).to(obs.dtype)
+            out = []
+            for i in range(W):
+                _, hidden, _ = m.next(zs_traj[i], action[i], hidden)
+                out.append(torch.zeros(obs.shape[0], 1, dtype=obs.dtype, device=obs.device))
+            for t in range(W, H + 1):
+                zl, hidden, _ = m.next(zs_traj[t], action[t], hidden)
+                pred = F.normalize(m.pred_z(zl).unsqueeze(0), dim=-1, p=2)
+                target = F.normalize(zs_target[t:t + 1], dim=-1, p=2)
+                out.append((2.0 - 2.0 * (pred * target).sum(dim=-1, keepdim=True))[0])
+            raw = torch.stack(out)                                   # [H + 1, B, 1], zeros in the warm-up rows
+            rms_update(self.rms, raw)
+            return rms_normalize(self.rms, raw)
+
+    def _similarity_torch(self, queries, keys, n):
+        m = self.agent.model
+        q = F.normalize(m.pred_z(torch.cat(queries, dim=0)), dim=-1, p=2)
+        k = F.normalize(torch.cat(keys, dim=0), dim=-1, p=2)
+        return (2.0 - 2.0 * (q * k).sum(dim=-1)).reshape(n, self.cfg.batch_size, -1).sum(dim=0)
+
+    def _step_torch(self, buffer, noise):
+        a, cfg, m, mt = self.agent, self.cfg, self.agent.model, self.agent.model_target
+        H, W = int(cfg.horizon), int(cfg.warmup_len)
+        N = H - W
+        obs, next_obses, action, reward, idxs, weights = buffer.sample()
+        B = obs.shape[0]
+        eps, aug = self._draws(noise, B)
+        a.optim.zero_grad(set_to_none=True)
+        z = m.h(obs)
+        online_next_zs = m.h(next_obses)
+        target_next_zs = mt.h(next_obses)
+        zs_traj = torch.cat([z.unsqueeze(0), online_next_zs], dim=0)
+        similarity_loss, reward_loss, value_loss, priority_loss = 0, 0, 0, 0
+        hidden = m.init_hidden_state(B, z.device).to(z.dtype)
+        queries, keys = [], []
+        for i in range(W):
+            z_pred, hidden, _ = m.next(zs_traj[i], action[i], hidden)
+            queries.append(z_pred + aug[i])
+            keys.append(target_next_zs[i].detach())
+        similarity_loss += self._similarity_torch(queries, keys, W)
+        intrinsic = self._intrinsic_torch(obs, next_obses, action)
+        reward_pi = self.coef * intrinsic + reward
+        queries, keys = [], []
+        z_shoot = zs_traj[W]
+        zs = [z_shoot.detach()]
+        for t in range(W, H):
+            Q1, Q2 = m.Q(z_shoot, action[t])
+            z_shoot, hidden, reward_pred = m.next(z_shoot, action[t], hidden)
+            z_shoot = z_shoot + aug[t]
+            queries.append(z_shoot)
+            keys.append(target_next_zs[t].detach())
+            zs.append(z_shoot.detach())
+            with torch.no_grad():
+                nz = online_next_zs[t]
+                e = None if eps is None else eps[t - W]
+                td = reward_pi[t] + cfg.discount * torch.min(*mt.Q(nz, m.pi(nz, cfg.min_std, eps=e)))
+            reward_loss += F.mse_loss(reward_pred, reward[t], reduction="none")
+            value_loss += F.mse_loss(Q1, td, reduction="none") + F.mse_loss(Q2, td, reduction="none")
+            priority_loss += F.l1_loss(Q1, td, reduction="none") + F.l1_loss(Q2, td, reduction="none")
+        similarity_loss += self._similarity_torch(queries, keys, N)
+        total_loss = cfg.similarity_coef * similarity_loss.clamp(max=1e4) + \
+            cfg.reward_coef * reward_loss.clamp(max=1e4) + cfg.value_coef * value_loss.clamp(max=1e4)
+        weighted = (total_loss * weights).mean()                    # the reference's [B, B] broadcast, literally
+        weighted.register_hook(lambda grad: grad * (1 / H))
+        weighted.backward()
+        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
+        a.optim.step()
+        return self._finish(buffer, idxs, priority_loss.clamp(max=1e4).detach(), zs, eps, N,
+                            (similarity_loss.mean(), reward_loss.mean(), value_loss.mean(), total_loss.mean()),
+                            weighted, grad_norm, intrinsic)

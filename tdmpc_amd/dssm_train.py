@@ -20,17 +20,25 @@ as ONE launch chain whose BatchNorms normalise per segment of B rows (tdmpc_drnn
 result against a device-resident float64 RunningMeanStd (tdmpc_drnn_intrinsic_finish) without a host round trip;
 `_DssmFusedLoss` is the update's loss composition with its TD-lambda targets and its backward.
 
+For the MPC agent's update (`TdMpcSimDssm.update`, tdmpc_amd/drnn_learner.py::DssmSimLearner; DESIGN.md §7 f9):
+`step.intrinsic_chain_rewards(...)` is the intrinsic-reward pass with ONE hidden state carried through the H + 1
+closed-loop steps (tdmpc_drnn_intrinsic_chain_fwd; `chain_mode` 0 runs the recurrence as a launch chain, 1 in one
+launch; the default is TDMPC_DSSM_CHAIN_MODE or CHAIN_MODE below), and `_DssmSimFusedLoss` that update's loss composition.
+
 There is no eager fall-back: a missing library or an unsupported shape raises. The update itself (optimisers, replay,
 the encoder / Q / pi passes) is `tdmpc_amd.drnn_learner.DssmLearner`.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
 from . import _lib
-from ._lib import DrnnLossArgs, DrnnTrainSizes, call, drnn_dims_from_cfg, ptr
+from ._lib import DrnnLossArgs, DrnnSimLossArgs, DrnnTrainSizes, call, drnn_dims_from_cfg, ptr
+
+CHAIN_MODE = 1   # the recurrence of intrinsic_chain_loss: the faster form at the bench shape (DESIGN.md §7 f9)
 
 NEXT_PARAMS = tuple(f"_dynamics.prior_mlp.{k}" for k in ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight",
                                                          "3.bias")) + \
@@ -194,6 +202,50 @@ class _DssmFusedLoss(torch.autograd.Function):
         return dsim, dq1, dq2, drp, None, None, None, None, None
 
 
+class _DssmSimFusedLoss(torch.autograd.Function):
+    """TdMpcSimDssm.update's loss composition (tdmpc_similarity_drnn.py:447-471) and its backward as HIP kernels
+    (tdmpc_drnn_sim_loss_forward / _backward): forward(sim [H, B], q1, q2, rp, rw, rwpi, nq [H - W, B] (the shoot steps),
+    w [B], coefs = (similarity_coef, reward_coef, value_coef, discount)) -> (scal [6], rows [5, B], td [H - W, B]);
+    scal = (mean similarity, mean reward, mean value, mean total, weighted = mean(total) mean(w), mean w), rows =
+    (similarity, reward, value, clamped priority, total) per batch row, td = the one-step TD targets. Only scal[4]
+    carries a gradient, to sim, q1, q2 and rp."""
+
+    @staticmethod
+    def _args(ins, H, N, B, coefs):
+        return DrnnSimLossArgs(*[t.data_ptr() for t in ins], H, H - N, B, *[float(c) for c in coefs])
+
+    @staticmethod
+    def forward(ctx, sim, q1, q2, rp, rw, rwpi, nq, w, coefs):
+        H, B = sim.shape
+        N = q1.shape[0]
+        ins = [_f32c(t) for t in (sim, q1, q2, rp, rw, rwpi, nq, w)]
+        if not 1 <= N < H:
+            raise ValueError(f"_DssmSimFusedLoss: {N} shoot steps of {H} (1 <= horizon - warmup_len <= horizon - 1)")
+        for t in ins[1:7]:
+            if tuple(t.shape) != (N, B):
+                raise ValueError(f"_DssmSimFusedLoss: q1 .. nq must be [{N}, {B}], got {tuple(t.shape)}")
+        if tuple(ins[7].shape) != (B,):
+            raise ValueError(f"_DssmSimFusedLoss: w must be [{B}], got {tuple(ins[7].shape)}")
+        td, rows, scal = sim.new_empty(N, B), sim.new_empty(5, B), sim.new_empty(6)
+        call("tdmpc_drnn_sim_loss_forward", _DssmSimFusedLoss._args(ins, H, N, B, coefs), td, rows, scal,
+             torch.cuda.current_stream().cuda_stream)
+        ctx.save_for_backward(*ins, td, rows, scal)
+        ctx.coefs = coefs
+        ctx.mark_non_differentiable(rows, td)
+        return scal, rows, td
+
+    @staticmethod
+    def backward(ctx, g_scal, g_rows, g_td):
+        *ins, td, rows, scal = ctx.saved_tensors
+        (H, B), N = ins[0].shape, ins[1].shape[0]
+        g = g_scal.contiguous()
+        need = ctx.needs_input_grad
+        dsim, dq1, dq2, drp = (torch.empty_like(ins[i]) if need[i] else None for i in range(4))
+        call("tdmpc_drnn_sim_loss_backward", _DssmSimFusedLoss._args(ins, H, N, B, ctx.coefs), td, rows, scal,
+             g.data_ptr() + 16, ptr(dsim), ptr(dq1), ptr(dq2), ptr(drp), torch.cuda.current_stream().cuda_stream)
+        return dsim, dq1, dq2, drp, None, None, None, None, None
+
+
 def new_rms_state(device):
     """gym's RunningMeanStd() as a float64 [mean, var, count] tensor (tdmpc_drnn_intrinsic_finish's device state)."""
     return torch.tensor([0.0, 1.0, 1e-4], dtype=torch.float64, device=device)
@@ -251,6 +303,8 @@ class DssmTrainStep:
         self._loss_pool = _Pool(int(max_losses), sl.loss_saved_floats, dev, "max_losses")
         self._ws = torch.empty(max(sn.workspace_floats, sl.workspace_floats), dtype=torch.float32, device=dev)
         self._iws = {}   # (segments, rows per segment) -> the workspace of intrinsic_loss
+        self._cws = {}   # likewise of intrinsic_chain_loss
+        self.chain_mode = int(os.environ.get("TDMPC_DSSM_CHAIN_MODE", CHAIN_MODE))
 
     def _check(self, what, rows, cap, *shaped):
         if not self.model.training:
@@ -317,3 +371,43 @@ class DssmTrainStep:
         mean / sqrt(var), 0) -> (intrinsic [S B], reward_pi [S B] = coef * intrinsic + reward). coef: a one-element
         float32 device tensor (the explore schedule's value of this step); reward [S B]."""
         return intrinsic_finish(self.intrinsic_loss(z, a, keys, segments), rms, coef, reward)
+
+    @torch.no_grad()
+    def intrinsic_chain_loss(self, z, a, keys, segments, warm, mode=None, hidden=False):
+        """`TdMpcSimDssm.intrinsic_rewards`' model uncertainty (similarity_horizon 1) -> loss [S B]: one hidden state
+        runs from zeros through the S closed-loop steps `next(z[s], a[s], h)`; the first `warm` steps only advance it
+        (loss 0 there, but prior_mlp's BatchNorm statistics move), the others compare `pred_z(z')` with keys[s]. mode: 0
+        the recurrence as a launch chain (bitwise S `next` calls + `similarity_loss` on the later segments), 1 in one
+        launch; default `self.chain_mode`. hidden=True: -> (loss, h_out [B, Hd], every segment's hidden state
+        [S, B, Hd], a view of the workspace that the next call overwrites)."""
+        R = z.shape[0]
+        S, W = int(segments), int(warm)
+        if S < 1 or R % S:
+            raise ValueError(f"DssmTrainStep.intrinsic_chain_loss: {R} rows do not split into {S} segments")
+        if not 0 <= W < S:
+            raise ValueError(f"DssmTrainStep.intrinsic_chain_loss: warm={W} is not in [0, {S})")
+        self._check("intrinsic_chain_loss", R, _lib.DT_MAX_ROWS, ("z", z, self.L), ("a", a, self.A),
+                    ("keys", keys, self.L))
+        z, a, keys = _f32c(z), _f32c(a), _f32c(keys)
+        B = R // S
+        ws = self._cws.get((S, B))
+        if ws is None:
+            n = C.c_size_t()
+            call("tdmpc_drnn_intrinsic_chain_workspace_floats", self.dims, S, B, C.byref(n))
+            ws = self._cws[(S, B)] = torch.empty(n.value, dtype=torch.float32, device=z.device)
+        loss, h_out = z.new_empty(R), z.new_empty(B, self.Hd)
+        ntab, nn_ = _table(self._next_params, self._next_stats)
+        ltab, nl = _table(self._loss_params, self._loss_stats)
+        call("tdmpc_drnn_intrinsic_chain_fwd", self.dims, ntab, nn_, ltab, nl, z, a, keys, S, B, W,
+             self.chain_mode if mode is None else int(mode), loss, h_out, ws, ws.numel(),
+             torch.cuda.current_stream().cuda_stream)
+        self.model._dynamics.prior_mlp[1].num_batches_tracked += S
+        self.model._predictor[1].num_batches_tracked += S - W
+        return (loss, h_out, ws[:R * self.Hd].view(S, B, self.Hd)) if hidden else loss
+
+    @torch.no_grad()
+    def intrinsic_chain_rewards(self, z, a, keys, segments, warm, rms, coef, reward):
+        """`TdMpcSimDssm.intrinsic_rewards` on the device: `intrinsic_chain_loss`, then `intrinsic_finish` over all
+        S B values (the zero rows of the warm-up segments enter the moments, as in the reference) ->
+        (intrinsic [S B], reward_pi [S B])."""
+        return intrinsic_finish(self.intrinsic_chain_loss(z, a, keys, segments, warm), rms, coef, reward)
