@@ -6,6 +6,7 @@ The drop-in names:
     from tdmpc_amd import TOLD             # src/algorithm/tdmpc.py:9 (same module tree and state_dict keys)
     from tdmpc_amd import ReplayBuffer     # src/algorithm/helper.py:434 (device prioritized replay)
     from tdmpc_amd import TdICEM           # src/algorithm/tdmpc_icem_similarity_mlp.py:116 (iCEM planner)
+    from tdmpc_amd import TdIcemMlp        # src/algorithm/tdmpc_icem_similarity_mlp.py:77 (the same agent with its update)
     from tdmpc_amd import TdMpcDrnn        # src/algorithm/tdmpc_similarity_drnn.py:87 (GRU-dynamics DSSM planner)
     from tdmpc_amd import TdIcemDrnn       # src/algorithm/tdmpc_icem_similarity_drnn.py:81 (iCEM on the DSSM: plan / update)
     from tdmpc_amd import EnvShardedPlanner  # vectorised envs over the GPUs of one node
@@ -23,6 +24,9 @@ _EXPORTS = {
     "TOLD": "told",
     "ReplayBuffer": "replay",
     "TdICEM": "icem",
+    "TdIcemMlp": "icem_mlp",
+    "IcemMlpModel": "icem_mlp",
+    "IcemMlpLearner": "icem_learner",
     "TdMpcDrnn": "drnn",
     "TdIcemDrnn": "drnn_icem",
     "DSSM": "dssm",

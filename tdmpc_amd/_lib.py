@@ -39,9 +39,15 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_drnn_simloss_fwd", "tdmpc_drnn_simloss_bwd", "tdmpc_drnn_intrinsic_workspace_floats",
             "tdmpc_drnn_intrinsic_fwd", "tdmpc_drnn_intrinsic_finish", "tdmpc_drnn_loss_forward",
             "tdmpc_drnn_loss_backward", "tdmpc_drnn_intrinsic_chain_workspace_floats",
-            "tdmpc_drnn_intrinsic_chain_fwd", "tdmpc_drnn_sim_loss_forward", "tdmpc_drnn_sim_loss_backward")
+            "tdmpc_drnn_intrinsic_chain_fwd", "tdmpc_drnn_sim_loss_forward", "tdmpc_drnn_sim_loss_backward",
+            # include/tdmpc_icem_learner.h
+            "tdmpc_icem_learner_version", "tdmpc_icem_intrinsic_workspace_floats", "tdmpc_icem_intrinsic_fwd",
+            "tdmpc_icem_simloss_sizes_for", "tdmpc_icem_simloss_fwd", "tdmpc_icem_simloss_bwd",
+            "tdmpc_icem_loss_forward", "tdmpc_icem_loss_backward")
 DRNN_VERSION = 2
 DRNN_TRAIN_VERSION = 1
+ICEM_LEARNER_VERSION = 1
+ICEM_DYN_TENSORS = 6   # include/tdmpc_icem_learner.h
 DT_NEXT_TENSORS, DT_LOSS_TENSORS, DT_MAX_ROWS = 22, 8, 4096   # include/tdmpc_drnn_learner.h
 NOISE_MAX_JOBS, NOISE_MAX_SPECTRA = 17, 4
 
@@ -173,6 +179,16 @@ class DrnnSimLossArgs(C.Structure):   # tdmpc_drnn_sim_loss_args (include/tdmpc_
                [(n, C.c_float) for n in ("sim_coef", "reward_coef", "value_coef", "discount")]
 
 
+class IcemSimlossSizes(C.Structure):   # tdmpc_icem_simloss_sizes (include/tdmpc_icem_learner.h)
+    _fields_ = [(n, C.c_size_t) for n in ("loss_saved_floats", "workspace_floats")]
+
+
+class IcemLossArgs(C.Structure):   # tdmpc_icem_loss_args (include/tdmpc_icem_learner.h)
+    _fields_ = [(n, C.c_void_p) for n in ("sim", "q1", "q2", "rp", "rw", "rwpi", "nq", "w")] + \
+               [("H", C.c_int32), ("B", C.c_int32)] + \
+               [(n, C.c_float) for n in ("sim_coef", "reward_coef", "value_coef", "discount")] + [("rho", C.c_double)]
+
+
 class Sizes(C.Structure):
     _fields_ = [("packed_weight_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t),
                 ("noise_floats_per_env", C.c_size_t)]
@@ -270,6 +286,14 @@ def lib():
     L.tdmpc_drnn_intrinsic_chain_fwd.argtypes = [dd, pv, i32, pv, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
     L.tdmpc_drnn_sim_loss_forward.argtypes = [C.POINTER(DrnnSimLossArgs), vp, vp, vp, vp]
     L.tdmpc_drnn_sim_loss_backward.argtypes = [C.POINTER(DrnnSimLossArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    pd = C.POINTER(Dims)
+    L.tdmpc_icem_intrinsic_workspace_floats.argtypes = [pd, i32, i32, C.POINTER(sz)]
+    L.tdmpc_icem_intrinsic_fwd.argtypes = [pd, pv, i32, pv, i32, vp, vp, vp, i32, i32, vp, vp, sz, vp]
+    L.tdmpc_icem_simloss_sizes_for.argtypes = [pd, i32, C.POINTER(IcemSimlossSizes)]
+    L.tdmpc_icem_simloss_fwd.argtypes = [pd, pv, i32, vp, vp, i32, vp, vp, sz, vp, sz, vp]
+    L.tdmpc_icem_simloss_bwd.argtypes = [pd, pv, i32, vp, vp, i32, vp, sz, vp, vp, pv, vp, sz, vp]
+    L.tdmpc_icem_loss_forward.argtypes = [C.POINTER(IcemLossArgs), vp, vp, vp, vp]
+    L.tdmpc_icem_loss_backward.argtypes = [C.POINTER(IcemLossArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED:
         if not hasattr(L, name) and not (name.startswith("tdmpc_debug_") and os.environ.get("TDMPC_LIB_PATH")):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")

@@ -27,6 +27,7 @@
 //     16 batch rows for all steps (the cell has only row LayerNorms, so rows are independent through time);
 //   * dt_sloss_rows / dt_sloss_means / dt_sloss_bwd: the one-step TD targets and the loss composition over the shoot
 //     steps W..H-1 (the similarity term over all H), forward and backward.
+// The MLP iCEM agent's update (TdICemSimMlp.update) is icem_learner.inc, included at the end.
 // Every reduction runs in a fixed order: wave butterflies, LDS sums over waves in wave order, partials in index order.
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,7 @@
 #include <algorithm>
 
 #include "../../include/tdmpc_drnn_learner.h"
+#include "../../include/tdmpc_icem_learner.h"
 #include "../../include/tdmpc_learner.h"
 
 namespace tdmpc_internal {
@@ -1033,6 +1035,74 @@ bool sim_loss_args_ok(const tdmpc_drnn_sim_loss_args* a) {
            a->W < a->H;
 }
 
+// similarity_loss forward and backward over a checked shape (tdmpc_drnn_simloss_* and, behind the planner's tdmpc_dims,
+// tdmpc_icem_simloss_*: the hidden width plays no part in them).
+int simloss_fwd(const Shape& s, float* const* T, int32_t n_tensors, const float* queries, const float* keys,
+                float* loss, float* saved, size_t saved_floats, float* workspace, size_t workspace_floats,
+                void* stream) {
+    if (int rc = need_table(T, n_tensors, TDMPC_DT_LOSS_TENSORS, "tensors", true)) return rc;
+    const void* ptrs[] = {queries, keys, loss, saved, workspace};
+    const char* names[] = {"queries", "keys", "loss", "saved", "workspace"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const LossSaved S = loss_saved(s, saved);
+    const LossFwdWs W = loss_fwd_ws(s, workspace);
+    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L;
+
+    tdmpc_lg_job j = linear(R, M, L, queries, T[P0W], T[P0B], W.p1);
+    if (int rc = gemm(&j, 1, stream)) return rc;
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.p1; b.g = T[P1G]; b.b = T[P1B]; b.rmean = T[P1RM]; b.rvar = T[P1RV];
+    b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part; b.rows = R; b.C = M;
+    if (int rc = bn_forward(b, st)) return rc;
+    j = linear(R, L, M, S.e, T[P3W], T[P3B], S.pred);
+    if (int rc = gemm(&j, 1, stream)) return rc;
+    hipLaunchKernelGGL(dt_cos_fwd, dim3((R + 3) / 4), dim3(256), 0, st, S.pred, keys, loss, R, L);
+    return launched("cos_fwd");
+}
+
+int simloss_bwd(const Shape& s, float* const* T, int32_t n_tensors, const float* queries, const float* keys,
+                const float* saved, size_t saved_floats, const float* dloss, float* dqueries, float* const* G,
+                float* workspace, size_t workspace_floats, void* stream) {
+    if (int rc = need_table(T, n_tensors, TDMPC_DT_LOSS_TENSORS, "tensors", true)) return rc;
+    if (int rc = need_table(G, n_tensors, TDMPC_DT_LOSS_TENSORS, "grads", false)) return rc;
+    const void* ptrs[] = {queries, keys, saved, dloss, workspace};
+    const char* names[] = {"queries", "keys", "saved", "dloss", "workspace"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = need(ptrs[i], names[i])) return rc;
+    const LossSaved S = loss_saved(s, const_cast<float*>(saved));
+    const LossBwdWs W = loss_bwd_ws(s, workspace);
+    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
+    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
+    const hipStream_t st = (hipStream_t)stream;
+    const int R = s.R, L = s.L;
+
+    hipLaunchKernelGGL(dt_cos_bwd, dim3((R + 3) / 4), dim3(256), 0, st, S.pred, keys, dloss, W.dpred, R, L);
+    if (int rc = launched("cos_bwd")) return rc;
+    tdmpc_lg_job j[3];
+    j[0] = dinput(R, M, L, W.dpred, T[P3W], M, W.de);
+    if (int rc = gemm(j, 1, stream)) return rc;
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = W.de; b.g = T[P1G]; b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part;
+    b.dx = W.de; b.dg = G[P1G]; b.db = G[P1B]; b.rows = R; b.C = M;
+    if (int rc = bn_backward(b, st)) return rc;
+    int n = 0;
+    if (dqueries) j[n++] = dinput(R, L, M, W.de, T[P0W], L, dqueries);
+    j[n++] = dweight(R, L, M, W.dpred, S.e, W.w3, M + 1, true);
+    j[n++] = dweight(R, M, L, W.de, queries, W.w0, L + 1, true);
+    if (int rc = gemm(j, n, stream)) return rc;
+    UnpackArgs u;
+    memset(&u, 0, sizeof u);
+    u.job[0] = UnpackJob{W.w3, G[P3W], G[P3B], L, M};
+    u.job[1] = UnpackJob{W.w0, G[P0W], G[P0B], M, L};
+    return unpack(u, 2, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1419,29 +1489,7 @@ int tdmpc_drnn_simloss_fwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t
                            float* workspace, size_t workspace_floats, void* stream) {
     Shape s;
     if (int rc = check_shape(dims, rows, s)) return rc;
-    if (int rc = need_table(T, n_tensors, TDMPC_DT_LOSS_TENSORS, "tensors", true)) return rc;
-    const void* ptrs[] = {queries, keys, loss, saved, workspace};
-    const char* names[] = {"queries", "keys", "loss", "saved", "workspace"};
-    for (int i = 0; i < 5; ++i)
-        if (int rc = need(ptrs[i], names[i])) return rc;
-    const LossSaved S = loss_saved(s, saved);
-    const LossFwdWs W = loss_fwd_ws(s, workspace);
-    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
-    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
-    const hipStream_t st = (hipStream_t)stream;
-    const int R = s.R, L = s.L;
-
-    tdmpc_lg_job j = linear(R, M, L, queries, T[P0W], T[P0B], W.p1);
-    if (int rc = gemm(&j, 1, stream)) return rc;
-    BnArgs b;
-    memset(&b, 0, sizeof b);
-    b.x = W.p1; b.g = T[P1G]; b.b = T[P1B]; b.rmean = T[P1RM]; b.rvar = T[P1RV];
-    b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part; b.rows = R; b.C = M;
-    if (int rc = bn_forward(b, st)) return rc;
-    j = linear(R, L, M, S.e, T[P3W], T[P3B], S.pred);
-    if (int rc = gemm(&j, 1, stream)) return rc;
-    hipLaunchKernelGGL(dt_cos_fwd, dim3((R + 3) / 4), dim3(256), 0, st, S.pred, keys, loss, R, L);
-    return launched("cos_fwd");
+    return simloss_fwd(s, T, n_tensors, queries, keys, loss, saved, saved_floats, workspace, workspace_floats, stream);
 }
 
 int tdmpc_drnn_simloss_bwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_tensors, const float* queries,
@@ -1450,39 +1498,10 @@ int tdmpc_drnn_simloss_bwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t
                            size_t workspace_floats, void* stream) {
     Shape s;
     if (int rc = check_shape(dims, rows, s)) return rc;
-    if (int rc = need_table(T, n_tensors, TDMPC_DT_LOSS_TENSORS, "tensors", true)) return rc;
-    if (int rc = need_table(G, n_tensors, TDMPC_DT_LOSS_TENSORS, "grads", false)) return rc;
-    const void* ptrs[] = {queries, keys, saved, dloss, workspace};
-    const char* names[] = {"queries", "keys", "saved", "dloss", "workspace"};
-    for (int i = 0; i < 5; ++i)
-        if (int rc = need(ptrs[i], names[i])) return rc;
-    const LossSaved S = loss_saved(s, const_cast<float*>(saved));
-    const LossBwdWs W = loss_bwd_ws(s, workspace);
-    if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
-    if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
-    const hipStream_t st = (hipStream_t)stream;
-    const int R = s.R, L = s.L;
-
-    hipLaunchKernelGGL(dt_cos_bwd, dim3((R + 3) / 4), dim3(256), 0, st, S.pred, keys, dloss, W.dpred, R, L);
-    if (int rc = launched("cos_bwd")) return rc;
-    tdmpc_lg_job j[3];
-    j[0] = dinput(R, M, L, W.dpred, T[P3W], M, W.de);
-    if (int rc = gemm(j, 1, stream)) return rc;
-    BnArgs b;
-    memset(&b, 0, sizeof b);
-    b.x = W.de; b.g = T[P1G]; b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part;
-    b.dx = W.de; b.dg = G[P1G]; b.db = G[P1B]; b.rows = R; b.C = M;
-    if (int rc = bn_backward(b, st)) return rc;
-    int n = 0;
-    if (dqueries) j[n++] = dinput(R, L, M, W.de, T[P0W], L, dqueries);
-    j[n++] = dweight(R, L, M, W.dpred, S.e, W.w3, M + 1, true);
-    j[n++] = dweight(R, M, L, W.de, queries, W.w0, L + 1, true);
-    if (int rc = gemm(j, n, stream)) return rc;
-    UnpackArgs u;
-    memset(&u, 0, sizeof u);
-    u.job[0] = UnpackJob{W.w3, G[P3W], G[P3B], L, M};
-    u.job[1] = UnpackJob{W.w0, G[P0W], G[P0B], M, L};
-    return unpack(u, 2, st);
+    return simloss_bwd(s, T, n_tensors, queries, keys, saved, saved_floats, dloss, dqueries, G, workspace,
+                       workspace_floats, stream);
 }
 
 }  // extern "C"
+
+#include "icem_learner.inc"

@@ -18,6 +18,7 @@ plan horizon; the envs of one call must agree on the horizon (the kernels take o
 """
 from __future__ import annotations
 
+import importlib
 from collections import deque
 
 import numpy as np
@@ -107,17 +108,18 @@ class DrnnPlanner(HipPlanner):
 
 
 class DssmLearning:
-    """The learning half of a DSSM agent: `learner` (the class named by LEARNER in tdmpc_amd.drnn_learner) is built on
-    first use and sets `optim` / `pi_optim`; reading either, or `reward_rms`, builds it."""
+    """The learning half of an agent with a similarity head: `learner` (the class named by LEARNER in the module
+    tdmpc_amd.<LEARNER_MODULE>) is built on first use and sets `optim` / `pi_optim`; reading either, or `reward_rms`,
+    builds it."""
 
-    LEARNER = "DssmLearner"
+    LEARNER, LEARNER_MODULE = "DssmLearner", "drnn_learner"
     _learner = None
 
     @property
     def learner(self):
         if self._learner is None:
-            from . import drnn_learner
-            self._learner = getattr(drnn_learner, self.LEARNER)(self, graph=self.graph)   # sets optim / pi_optim
+            module = importlib.import_module("." + self.LEARNER_MODULE, __package__)
+            self._learner = getattr(module, self.LEARNER)(self, graph=self.graph)   # sets optim / pi_optim
         return self._learner
 
     @property

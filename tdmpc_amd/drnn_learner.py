@@ -128,6 +128,7 @@ class DssmLearner:
     agent (`agent`: cfg, model, model_target, device and, when it plans, planner)."""
 
     MAX_LOSSES = 1   # live similarity_loss calls of one update
+    HIP_ENV = "TDMPC_DSSM_LEARNER_HIP"   # "0": the PyTorch path on the GPU
     check_cfg = staticmethod(check_learner_cfg)
 
     def __init__(self, agent, graph: bool = True, warmup: int = 3):
@@ -138,7 +139,7 @@ class DssmLearner:
         p0 = next(model.parameters())
         self.device, self.dtype = p0.device, p0.dtype
         on_gpu = self.device.type == "cuda"
-        self.hip = on_gpu and os.environ.get("TDMPC_DSSM_LEARNER_HIP", "1") != "0"
+        self.hip = on_gpu and os.environ.get(self.HIP_ENV, "1") != "0"
         self.graph = bool(graph) and on_gpu
         self.warmup = warmup
         self.params = list(model.parameters())
@@ -152,12 +153,14 @@ class DssmLearner:
         self.coef = torch.zeros(1, dtype=torch.float32 if self.hip else self.dtype, device=self.device)
         self.train_step = None
         if self.hip:
-            from .dssm_train import DssmTrainStep
-            B, H = int(cfg.batch_size), int(cfg.horizon)
-            self.train_step = DssmTrainStep(model, max_rows=B, max_steps=H, max_loss_rows=H * B, max_losses=self.MAX_LOSSES)
+            self.train_step = self._make_train_step(model, int(cfg.batch_size), int(cfg.horizon))
         self.calls = 0
         self._graphs = {}
         self.last = {}   # the last eager step's intermediate results (tests): intrinsic, priorities
+
+    def _make_train_step(self, model, B, H):
+        from .dssm_train import DssmTrainStep
+        return DssmTrainStep(model, max_rows=B, max_steps=H, max_loss_rows=H * B, max_losses=self.MAX_LOSSES)
 
     # ------------------------------------------------------------------ the policy update (:367-384)
     def update_pi(self, zs, eps=None):

@@ -137,7 +137,7 @@ class _LossFn(torch.autograd.Function):
         loss = q.new_empty(R)
         tab, n = _table(params, step._loss_stats)
         try:
-            call("tdmpc_drnn_simloss_fwd", step.dims, tab, n, q, k, R, loss, slot.buf, slot.buf.numel(), step._ws,
+            call(step.LOSS_ABI + "fwd", step.dims, tab, n, q, k, R, loss, slot.buf, slot.buf.numel(), step._ws,
                  step._ws.numel(), torch.cuda.current_stream().cuda_stream)
         except Exception:
             slot.release()
@@ -158,7 +158,7 @@ class _LossFn(torch.autograd.Function):
         grads = [torch.empty_like(p) for p in params]
         tab, n = _table(params, step._loss_stats)
         gtab, _ = _table(grads, (None, None))
-        call("tdmpc_drnn_simloss_bwd", step.dims, tab, n, q, k, q.shape[0], slot.buf, slot.buf.numel(),
+        call(step.LOSS_ABI + "bwd", step.dims, tab, n, q, k, q.shape[0], slot.buf, slot.buf.numel(),
              _f32c(dloss), ptr(dq), gtab, step._ws, step._ws.numel(), torch.cuda.current_stream().cuda_stream)
         slot.release()
         return (None, dq, None) + tuple(g if need[3 + i] else None for i, g in enumerate(grads))
@@ -270,6 +270,8 @@ class DssmTrainStep:
     """Differentiable `DSSM.next` (train mode) and `similarity_loss` on HIP for `model` (a `tdmpc_amd.dssm.DSSM` on the
     GPU, fp32). max_rows: the largest batch of `next`; max_loss_rows: of `similarity_loss` (default
     min(4096, max_rows * max_steps): the reference concatenates the per-step predictions)."""
+
+    LOSS_ABI = "tdmpc_drnn_simloss_"   # _LossFn's entry points (tdmpc_amd.icem_learner.IcemTrainStep: the tdmpc_dims ones)
 
     def __init__(self, model, max_rows: int, max_steps: int | None = None, max_loss_rows: int | None = None,
                  max_losses: int = 2):
