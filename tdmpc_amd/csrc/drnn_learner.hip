@@ -19,14 +19,17 @@
 //     losses as one launch chain over S B rows -- dt_bn_stat / dt_bn_fwd normalise per segment of B rows and move the
 //     running statistics S times in segment order, dt_gate_fwd<true> reads no hidden state;
 //   * dt_intrinsic_finish: float64 moments of the losses, the RunningMeanStd update on the device, the rewards;
-//   * dt_loss_rows / dt_loss_means / dt_loss_bwd: the TD-lambda targets and the loss composition, forward and backward.
+//   * dt_loss_rows / dt_loss_means / dt_loss_bwd: the TD-lambda targets and the loss composition, forward and backward
+//     (loss_means: the batch means of every loss composition here).
 // For TdMpcSimDssm.update (tdmpc_similarity_drnn.py:373-496):
 //   * tdmpc_drnn_intrinsic_chain_fwd: intrinsic_rewards with ONE hidden state carried through the S = H + 1 closed-loop
 //     steps. weight_ih's product does not depend on the hidden state and runs once over all S B rows; the recurrence is
 //     either a launch chain (per step h weight_hh^T + dt_gate_fwd) or dt_gru_chain, one launch in which a workgroup owns
 //     16 batch rows for all steps (the cell has only row LayerNorms, so rows are independent through time);
-//   * dt_sloss_rows / dt_sloss_means / dt_sloss_bwd: the one-step TD targets and the loss composition over the shoot
-//     steps W..H-1 (the similarity term over all H), forward and backward.
+//   * sl_loss_rows / sl_loss_means / sl_loss_bwd: the one-step TD targets and the loss composition over the shoot
+//     steps W..H-1 (the similarity term over all H), forward and backward; instantiated a second time, with rho ** t and
+//     the 1 / horizon hook, for the MLP iCEM agent's update.
+// predictor_fwd is `_predictor` and the cosine loss behind every similarity loss and intrinsic-reward pass.
 // The MLP iCEM agent's update (TdICemSimMlp.update) is icem_learner.inc, included at the end.
 // Every reduction runs in a fixed order: wave butterflies, LDS sums over waves in wave order, partials in index order.
 #include <hip/hip_runtime.h>
@@ -503,31 +506,39 @@ __global__ void __launch_bounds__(256) dt_loss_rows(const tdmpc_drnn_loss_args a
     rows[5 * B + b] = a.value_coef * fminf(val, LOSS_CLAMP);
 }
 
-__global__ void __launch_bounds__(512) dt_loss_means(const tdmpc_drnn_loss_args a, const float* rows, float* scal) {
-    __shared__ float red[6][8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, B = a.B;
-    float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+// The means over the batch of K - 1 rows of `rows` [*, B] (row numbers `at`) and, last, of w [B], by one workgroup of 512
+// threads: thread-strided sums, wsum, the eight wave sums added in wave order by thread 0, which alone gets m.
+template <int K>
+__device__ __forceinline__ void loss_means(const float* rows, const int (&at)[K - 1], const float* w, int B,
+                                           float (&m)[K]) {
+    __shared__ float red[K][8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float s[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = 0.f;
     for (int b = tid; b < B; b += 512) {
-        s[0] += rows[b];
-        s[1] += rows[B + b];
-        s[2] += rows[2 * B + b];
-        s[3] += rows[4 * B + b];
-        s[4] += rows[5 * B + b];
-        s[5] += a.w[b];
+#pragma unroll
+        for (int k = 0; k < K - 1; ++k) s[k] += rows[(size_t)at[k] * B + b];
+        s[K - 1] += w[b];
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
+    for (int k = 0; k < K; ++k) {
         const float v = wsum(s[k]);
         if (lane == 0) red[k][wave] = v;
     }
     __syncthreads();
-    if (tid == 0) {
-        float m[6];
-        for (int k = 0; k < 6; ++k) {
-            float v = 0.f;
-            for (int w = 0; w < 8; ++w) v += red[k][w];
-            m[k] = v / (float)B;
-        }
+    if (tid != 0) return;
+    for (int k = 0; k < K; ++k) {
+        float v = 0.f;
+        for (int wv = 0; wv < 8; ++wv) v += red[k][wv];
+        m[k] = v / (float)B;
+    }
+}
+
+__global__ void __launch_bounds__(512) dt_loss_means(const tdmpc_drnn_loss_args a, const float* rows, float* scal) {
+    float m[6];
+    loss_means<6>(rows, {0, 1, 2, 4, 5}, a.w, a.B, m);
+    if (threadIdx.x == 0) {
         scal[0] = m[0]; scal[1] = m[1]; scal[2] = m[2];
         scal[3] = m[3] + m[4];
         scal[4] = m[3] * m[5] + m[4];
@@ -654,10 +665,23 @@ __global__ void __launch_bounds__(64 * CWAVES) dt_gru_chain(const ChainArgs a) {
     }
 }
 
-// ---- TdMpcSimDssm.update's loss composition (tdmpc_drnn_learner.h): as dt_loss_* with one-step TD targets, the
-// reward / value / priority sums over the N = H - W shoot steps and every term under the priority weights.
-__global__ void __launch_bounds__(256) dt_sloss_rows(const tdmpc_drnn_sim_loss_args a, float* td, float* rows) {
-    const int b = blockIdx.x * 256 + threadIdx.x, H = a.H, N = a.H - a.W, B = a.B;
+// ---- The loss composition with one-step TD targets, every term under the priority weights: TdMpcSimDssm.update's
+// (tdmpc_drnn_sim_loss_*: the reward / value / priority sums over the N = H - W shoot steps) and TdICemSimMlp.update's
+// (tdmpc_icem_loss_*: N = H, those sums weighted by rho ** t, and the 1 / horizon gradient hook in the backward). RHO and
+// HOOK choose the expressions at compile time: each caller keeps its own contraction into FMAs.
+struct StepLossArgs {
+    const float *sim, *q1, *q2, *rp, *rw, *rwpi, *nq, *w;
+    int H, N, B;
+    float sim_coef, reward_coef, value_coef, discount;
+    double rho;
+};
+
+// (float)(rho ** t): the power in double, rounded once (a float32 tensor times a Python float).
+__device__ __forceinline__ float rho_pow(double rho, int t) { return t == 0 ? 1.f : (float)pow(rho, (double)t); }
+
+template <bool RHO>
+__global__ void __launch_bounds__(256) sl_loss_rows(const StepLossArgs a, float* td, float* rows) {
+    const int b = blockIdx.x * 256 + threadIdx.x, H = a.H, N = a.N, B = a.B;
     if (b >= B) return;
     float sim = 0.f, rew = 0.f, val = 0.f, pri = 0.f;
     for (int t = 0; t < H; ++t) sim += a.sim[(size_t)t * B + b];
@@ -666,9 +690,16 @@ __global__ void __launch_bounds__(256) dt_sloss_rows(const tdmpc_drnn_sim_loss_a
         const float tg = a.rwpi[i] + a.discount * a.nq[i];
         const float dr = a.rp[i] - a.rw[i], d1 = a.q1[i] - tg, d2 = a.q2[i] - tg;
         td[i] = tg;
-        rew += dr * dr;
-        val += d1 * d1 + d2 * d2;
-        pri += fabsf(d1) + fabsf(d2);
+        if (RHO) {
+            const float r = rho_pow(a.rho, t);
+            rew += (dr * dr) * r;
+            val += (d1 * d1 + d2 * d2) * r;
+            pri += (fabsf(d1) + fabsf(d2)) * r;
+        } else {
+            rew += dr * dr;
+            val += d1 * d1 + d2 * d2;
+            pri += fabsf(d1) + fabsf(d2);
+        }
     }
     rows[b] = sim;
     rows[B + b] = rew;
@@ -678,48 +709,37 @@ __global__ void __launch_bounds__(256) dt_sloss_rows(const tdmpc_drnn_sim_loss_a
                       a.value_coef * fminf(val, LOSS_CLAMP);
 }
 
-__global__ void __launch_bounds__(512) dt_sloss_means(const tdmpc_drnn_sim_loss_args a, const float* rows, float* scal) {
-    __shared__ float red[5][8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, B = a.B;
-    float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int b = tid; b < B; b += 512) {
-        s[0] += rows[b];
-        s[1] += rows[B + b];
-        s[2] += rows[2 * B + b];
-        s[3] += rows[4 * B + b];
-        s[4] += a.w[b];
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const float v = wsum(s[k]);
-        if (lane == 0) red[k][wave] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float m[5];
-        for (int k = 0; k < 5; ++k) {
-            float v = 0.f;
-            for (int w = 0; w < 8; ++w) v += red[k][w];
-            m[k] = v / (float)B;
-        }
+__global__ void __launch_bounds__(512) sl_loss_means(const float* rows, const float* w, int B, float* scal) {
+    float m[5];
+    loss_means<5>(rows, {0, 1, 2, 4}, w, B, m);
+    if (threadIdx.x == 0) {
         scal[0] = m[0]; scal[1] = m[1]; scal[2] = m[2]; scal[3] = m[3];
         scal[4] = m[3] * m[4];
         scal[5] = m[4];
     }
 }
 
-__global__ void __launch_bounds__(256) dt_sloss_bwd(const tdmpc_drnn_sim_loss_args a, const float* td, const float* rows,
-                                                    const float* scal, const float* gw, float* dsim, float* dq1,
-                                                    float* dq2, float* drp) {
+template <bool RHO, bool HOOK>
+__global__ void __launch_bounds__(256) sl_loss_bwd(const StepLossArgs a, const float* td, const float* rows,
+                                                   const float* scal, const float* gw, float* dsim, float* dq1,
+                                                   float* dq2, float* drp) {
     const int B = a.B;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)a.H * B) return;
-    const int b = (int)(i % B);
-    const float dtot = gw[0] * scal[5] / (float)B;
+    const int b = (int)(i % B), t = (int)(i / B);
+    // d weighted / d total_b = mean(w) / B, after the hook's 1 / horizon
+    const float dtot = HOOK ? gw[0] * (1.f / (float)a.H) * scal[5] / (float)B : gw[0] * scal[5] / (float)B;
     if (dsim) dsim[i] = rows[b] <= LOSS_CLAMP ? a.sim_coef * dtot : 0.f;
-    if (i >= (long)(a.H - a.W) * B) return;
-    const float dr = rows[B + b] <= LOSS_CLAMP ? a.reward_coef * dtot : 0.f;
-    const float dv = rows[2 * B + b] <= LOSS_CLAMP ? a.value_coef * dtot : 0.f;
+    if (i >= (long)a.N * B) return;
+    float dr, dv;
+    if (RHO) {
+        const float r = rho_pow(a.rho, t);
+        dr = rows[B + b] <= LOSS_CLAMP ? a.reward_coef * dtot * r : 0.f;
+        dv = rows[2 * B + b] <= LOSS_CLAMP ? a.value_coef * dtot * r : 0.f;
+    } else {
+        dr = rows[B + b] <= LOSS_CLAMP ? a.reward_coef * dtot : 0.f;
+        dv = rows[2 * B + b] <= LOSS_CLAMP ? a.value_coef * dtot : 0.f;
+    }
     if (drp) drp[i] = 2.f * (a.rp[i] - a.rw[i]) * dr;
     if (dq1) dq1[i] = 2.f * (a.q1[i] - td[i]) * dv;
     if (dq2) dq2[i] = 2.f * (a.q2[i] - td[i]) * dv;
@@ -1035,6 +1055,51 @@ bool sim_loss_args_ok(const tdmpc_drnn_sim_loss_args* a) {
            a->W < a->H;
 }
 
+StepLossArgs sim_step_args(const tdmpc_drnn_sim_loss_args* a) {
+    return StepLossArgs{a->sim, a->q1, a->q2, a->rp, a->rw, a->rwpi, a->nq, a->w, a->H, a->H - a->W, a->B,
+                        a->sim_coef, a->reward_coef, a->value_coef, a->discount, 1.0};
+}
+
+// The one-step loss family's launches over checked args (tdmpc_drnn_sim_loss_* and tdmpc_icem_loss_*).
+template <bool RHO>
+int step_loss_forward(const StepLossArgs& a, float* td, float* rows, float* scal, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sl_loss_rows<RHO>, dim3((a.B + 255) / 256), dim3(256), 0, st, a, td, rows);
+    if (int rc = launched("step loss_rows")) return rc;
+    hipLaunchKernelGGL(sl_loss_means, dim3(1), dim3(512), 0, st, rows, a.w, a.B, scal);
+    return launched("step loss_means");
+}
+
+template <bool RHO, bool HOOK>
+int step_loss_backward(const StepLossArgs& a, const float* td, const float* rows, const float* scal, const float* gw,
+                       float* dsim, float* dq1, float* dq2, float* drp, void* stream) {
+    const long n = (long)a.H * a.B;
+    hipLaunchKernelGGL((sl_loss_bwd<RHO, HOOK>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a,
+                       td, rows, scal, gw, dsim, dq1, dq2, drp);
+    return launched("step loss_bwd");
+}
+
+// `_predictor` on x [R, L] and the cosine loss against keys -> loss [R]: Linear, BatchNorm on batch statistics (over
+// `nseg` segments of `seg` rows each, or over all R rows when seg is 0) + ELU, Linear, dt_cos_fwd. P: the loss table
+// (its first eight slots; the running statistics move). tile_rows: gemm's row-block argument of the caller.
+struct PredictorBufs { float *p1, *bnx, *bnr, *e, *part, *pred; };   // [R, M], [R, M], [nseg, M], [R, M], partials, [R, L]
+int predictor_fwd(float* const* P, const float* x, const float* keys, float* loss, int R, int L, int seg, int nseg,
+                  int tile_rows, const PredictorBufs& w, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    tdmpc_lg_job j = linear(R, M, L, x, P[P0W], P[P0B], w.p1);
+    if (int rc = gemm(&j, 1, stream, tile_rows)) return rc;
+    BnArgs b;
+    memset(&b, 0, sizeof b);
+    b.x = w.p1; b.g = P[P1G]; b.b = P[P1B]; b.rmean = P[P1RM]; b.rvar = P[P1RV];
+    b.xhat = w.bnx; b.rstd = w.bnr; b.e = w.e; b.part = w.part; b.rows = R; b.C = M;
+    b.seg = seg; b.nseg = nseg;
+    if (int rc = bn_forward(b, st)) return rc;
+    j = linear(R, L, M, w.e, P[P3W], P[P3B], w.pred);
+    if (int rc = gemm(&j, 1, stream, tile_rows)) return rc;
+    hipLaunchKernelGGL(dt_cos_fwd, dim3((R + 3) / 4), dim3(256), 0, st, w.pred, keys, loss, R, L);
+    return launched("cos_fwd");
+}
+
 // similarity_loss forward and backward over a checked shape (tdmpc_drnn_simloss_* and, behind the planner's tdmpc_dims,
 // tdmpc_icem_simloss_*: the hidden width plays no part in them).
 int simloss_fwd(const Shape& s, float* const* T, int32_t n_tensors, const float* queries, const float* keys,
@@ -1049,20 +1114,8 @@ int simloss_fwd(const Shape& s, float* const* T, int32_t n_tensors, const float*
     const LossFwdWs W = loss_fwd_ws(s, workspace);
     if (saved_floats < S.total) return size_err("saved", saved_floats, S.total);
     if (workspace_floats < W.total) return size_err("workspace", workspace_floats, W.total);
-    const hipStream_t st = (hipStream_t)stream;
-    const int R = s.R, L = s.L;
-
-    tdmpc_lg_job j = linear(R, M, L, queries, T[P0W], T[P0B], W.p1);
-    if (int rc = gemm(&j, 1, stream)) return rc;
-    BnArgs b;
-    memset(&b, 0, sizeof b);
-    b.x = W.p1; b.g = T[P1G]; b.b = T[P1B]; b.rmean = T[P1RM]; b.rvar = T[P1RV];
-    b.xhat = S.bnx; b.rstd = S.bnr; b.e = S.e; b.part = W.part; b.rows = R; b.C = M;
-    if (int rc = bn_forward(b, st)) return rc;
-    j = linear(R, L, M, S.e, T[P3W], T[P3B], S.pred);
-    if (int rc = gemm(&j, 1, stream)) return rc;
-    hipLaunchKernelGGL(dt_cos_fwd, dim3((R + 3) / 4), dim3(256), 0, st, S.pred, keys, loss, R, L);
-    return launched("cos_fwd");
+    return predictor_fwd(T, queries, keys, loss, s.R, s.L, 0, 0, 0, PredictorBufs{W.p1, S.bnx, S.bnr, S.e, W.part, S.pred},
+                         stream);
 }
 
 int simloss_bwd(const Shape& s, float* const* T, int32_t n_tensors, const float* queries, const float* keys,
@@ -1157,14 +1210,8 @@ int tdmpc_drnn_intrinsic_fwd(const tdmpc_drnn_dims* dims, float* const* T, int32
     if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
 
     // similarity_loss(z', keys): the predictor's table has the same layout as prior_mlp's first eight slots
-    j = linear(R, M, L, W.zo, P[P0W], P[P0B], W.p1);
-    if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
-    b.g = P[P1G]; b.b = P[P1B]; b.rmean = P[P1RM]; b.rvar = P[P1RV];
-    if (int rc = bn_forward(b, st)) return rc;
-    j = linear(R, L, M, W.e, P[P3W], P[P3B], W.pred);
-    if (int rc = gemm(&j, 1, stream, seg_rows)) return rc;
-    hipLaunchKernelGGL(dt_cos_fwd, dim3((R + 3) / 4), dim3(256), 0, st, W.pred, keys, loss, R, L);
-    return launched("cos_fwd");
+    return predictor_fwd(P, W.zo, keys, loss, R, L, seg_rows, segments, seg_rows,
+                         PredictorBufs{W.p1, W.bnx, W.bnr, W.e, W.part, W.pred}, stream);
 }
 
 int tdmpc_drnn_intrinsic_finish(const float* loss, int32_t n, double* rms, const float* coef, const float* reward,
@@ -1288,25 +1335,14 @@ int tdmpc_drnn_intrinsic_chain_fwd(const tdmpc_drnn_dims* dims, float* const* T,
     if (warm && hipMemsetAsync(loss, 0, o * sizeof(float), st) != hipSuccess) return launched("memset");
     j = linear(R2, L, M, W.e + o * M, T[P3W], T[P3B], W.zo);
     if (int rc = gemm(&j, 1, stream, B, M)) return rc;   // (next_fwd launches it beside _reward.2, M columns)
-    j = linear(R2, M, L, W.zo, P[P0W], P[P0B], W.p1);
-    if (int rc = gemm(&j, 1, stream, B)) return rc;
-    b.g = P[P1G]; b.b = P[P1B]; b.rmean = P[P1RM]; b.rvar = P[P1RV];
-    b.rows = R2; b.nseg = S - warm;
-    if (int rc = bn_forward(b, st)) return rc;
-    j = linear(R2, L, M, W.e, P[P3W], P[P3B], W.pred);
-    if (int rc = gemm(&j, 1, stream, B)) return rc;
-    hipLaunchKernelGGL(dt_cos_fwd, dim3((R2 + 3) / 4), dim3(256), 0, st, W.pred, keys + o * L, loss + o, R2, L);
-    return launched("cos_fwd");
+    return predictor_fwd(P, W.zo, keys + o * L, loss + o, R2, L, B, S - warm, B,
+                         PredictorBufs{W.p1, W.bnx, W.bnr, W.e, W.part, W.pred}, stream);
 }
 
 int tdmpc_drnn_sim_loss_forward(const tdmpc_drnn_sim_loss_args* a, float* td, float* rows, float* scal, void* stream) {
     if (!sim_loss_args_ok(a) || !td || !rows || !scal)
         return bad("drnn_learner: sim_loss_forward: a null pointer, B < 1 or W outside [1, H - 1]");
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(dt_sloss_rows, dim3((a->B + 255) / 256), dim3(256), 0, st, *a, td, rows);
-    if (int rc = launched("sloss_rows")) return rc;
-    hipLaunchKernelGGL(dt_sloss_means, dim3(1), dim3(512), 0, st, *a, rows, scal);
-    return launched("sloss_means");
+    return step_loss_forward<false>(sim_step_args(a), td, rows, scal, stream);
 }
 
 int tdmpc_drnn_sim_loss_backward(const tdmpc_drnn_sim_loss_args* a, const float* td, const float* rows,
@@ -1314,10 +1350,7 @@ int tdmpc_drnn_sim_loss_backward(const tdmpc_drnn_sim_loss_args* a, const float*
                                  void* stream) {
     if (!sim_loss_args_ok(a) || !td || !rows || !scal || !gw)
         return bad("drnn_learner: sim_loss_backward: a null pointer, B < 1 or W outside [1, H - 1]");
-    const long n = (long)a->H * a->B;
-    hipLaunchKernelGGL(dt_sloss_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a, td, rows,
-                       scal, gw, dsim, dq1, dq2, drp);
-    return launched("sloss_bwd");
+    return step_loss_backward<false, false>(sim_step_args(a), td, rows, scal, gw, dsim, dq1, dq2, drp, stream);
 }
 
 int tdmpc_drnn_train_version(void) { return TDMPC_DRNN_TRAIN_VERSION; }

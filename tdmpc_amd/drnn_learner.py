@@ -23,9 +23,9 @@ The HIP path (the model on the GPU) orders one update for the device:
   * backward, `clip_grad_norm_19`, the optimiser step, the priority write-back, and `update_pi` over the H + 1 latents in
     one pass.
 Nothing synchronises with the host. After `warmup` eager updates one update per (buffer.idx, buffer._full) is captured
-into a HIP graph and replayed, as `learner.Learner` does; the explore coefficient changes every step, so it lives in a
-device scalar that is written before each replay. The encoder, Q and pi MLPs run on PyTorch-ROCm autograd here (float32
-matmul precision pinned); moving them onto tdmpc_lg_gemm / tdmpc_lg_rows_* is the follow-up.
+into a HIP graph and replayed by `learner.GraphLearner`, the driver shared with the TOLD learner; the explore coefficient
+changes every step, so it lives in a device scalar that `update` writes before each replay. The encoder, Q and pi MLPs
+run on PyTorch-ROCm autograd here (float32 matmul precision pinned); moving them onto tdmpc_lg_gemm / tdmpc_lg_rows_* is the follow-up.
 
 The PyTorch path is the reference's own order of operations, call by call, in plain PyTorch. It runs when the model is on
 the CPU (tests/test_drnn_update_cpu.py holds it bit for bit to the restatement) and on the GPU with
@@ -59,24 +59,30 @@ import torch.nn.functional as F
 from . import _lib
 from .config import linear_schedule
 from .dssm import check_dssm_cfg
-from .learner import clip_grad_norm_19
+from .dssm_train import DssmTrainStep, _DssmFusedLoss, _DssmSimFusedLoss, new_rms_state
+from .learner import GraphLearner, clip_grad_norm_19
 
 METRICS = ("consistency_loss", "reward_loss", "value_loss", "pi_loss", "total_loss", "weighted_loss", "grad_norm",
            "intrinsic_batch_reward_mean")
 
 
-def check_learner_cfg(cfg):
-    """Raise for what the DSSM learner does not cover, each setting named, before anything touches the device."""
-    check_dssm_cfg(cfg)
+def check_update_cfg(cfg, who):
+    """Raise for what no similarity learner covers (`who`: the class the message names)."""
     B, H = int(cfg.batch_size), int(cfg.horizon)
     if B < 2:
-        raise ValueError(f"DssmLearner: batch_size={B} is not supported (train-mode BatchNorm needs two rows)")
+        raise ValueError(f"{who}: batch_size={B} is not supported (train-mode BatchNorm needs two rows)")
     if (H + 1) * B > _lib.DT_MAX_ROWS:
-        raise ValueError(f"DssmLearner: (horizon + 1) * batch_size = {(H + 1) * B} rows exceed {_lib.DT_MAX_ROWS} "
+        raise ValueError(f"{who}: (horizon + 1) * batch_size = {(H + 1) * B} rows exceed {_lib.DT_MAX_ROWS} "
                          f"(horizon={H}, batch_size={B}): the intrinsic-reward pass and its normalisation take at most "
                          f"that many rows")
     if str(getattr(cfg, "optim_id", "adamw")).lower() not in ("adam", "adamw"):
-        raise ValueError(f"DssmLearner: optim_id={cfg.optim_id!r} is not supported ('adam' or 'adamw')")
+        raise ValueError(f"{who}: optim_id={cfg.optim_id!r} is not supported ('adam' or 'adamw')")
+
+
+def check_learner_cfg(cfg):
+    """Raise for what the DSSM learner does not cover, each setting named, before anything touches the device."""
+    check_dssm_cfg(cfg)
+    check_update_cfg(cfg, "DssmLearner")
 
 
 def make_optimizer(params, cfg, lr, capturable=False):
@@ -123,7 +129,13 @@ def rms_normalize(state, x):
     return torch.clamp_min(y.double() - state[0] / sd, 0).to(x.dtype)
 
 
-class DssmLearner:
+def cosine_loss(model, z_pred, target):
+    """The reference's similarity term per row: 2 - 2 <normalize(pred_z(z_pred)), normalize(target)> -> [..., 1]."""
+    pred = F.normalize(model.pred_z(z_pred), dim=-1, p=2)
+    return 2.0 - 2.0 * (pred * F.normalize(target, dim=-1, p=2)).sum(dim=-1, keepdim=True)
+
+
+class DssmLearner(GraphLearner):
     """Owns the optimisers, the RunningMeanStd state and (in graph mode) the captured update graphs of one DSSM iCEM
     agent (`agent`: cfg, model, model_target, device and, when it plans, planner)."""
 
@@ -132,34 +144,25 @@ class DssmLearner:
     check_cfg = staticmethod(check_learner_cfg)
 
     def __init__(self, agent, graph: bool = True, warmup: int = 3):
-        cfg = self.cfg = agent.cfg
+        cfg = agent.cfg
         self.check_cfg(cfg)
-        self.agent = agent
         model = agent.model
         p0 = next(model.parameters())
         self.device, self.dtype = p0.device, p0.dtype
         on_gpu = self.device.type == "cuda"
         self.hip = on_gpu and os.environ.get(self.HIP_ENV, "1") != "0"
-        self.graph = bool(graph) and on_gpu
-        self.warmup = warmup
-        self.params = list(model.parameters())
-        self.pi_params = list(model._pi.parameters())
-        self.target_params = list(agent.model_target.parameters())
+        super().__init__(agent, bool(graph) and on_gpu, warmup)
         agent.optim = make_optimizer(self.params, cfg, cfg.lr, capturable=self.graph)
         agent.pi_optim = make_optimizer(self.pi_params, cfg, cfg.pi_lr, capturable=self.graph)
-        from .dssm_train import new_rms_state
         self.rms = new_rms_state(self.device)
         self.reward_rms = RewardRms(self.rms)
         self.coef = torch.zeros(1, dtype=torch.float32 if self.hip else self.dtype, device=self.device)
         self.train_step = None
         if self.hip:
             self.train_step = self._make_train_step(model, int(cfg.batch_size), int(cfg.horizon))
-        self.calls = 0
-        self._graphs = {}
         self.last = {}   # the last eager step's intermediate results (tests): intrinsic, priorities
 
     def _make_train_step(self, model, B, H):
-        from .dssm_train import DssmTrainStep
         return DssmTrainStep(model, max_rows=B, max_steps=H, max_loss_rows=H * B, max_losses=self.MAX_LOSSES)
 
     # ------------------------------------------------------------------ the policy update (:367-384)
@@ -225,7 +228,6 @@ class DssmLearner:
         x = torch.cat([torch.stack(zs[:H]), action[:H]], dim=-1).view(H * B, -1)
         Q1, Q2 = m._Q1(x).view(H, B), m._Q2(x).view(H, B)
         sim = ts.similarity_loss(zs[1:], nz_tg[:H * B])
-        from .dssm_train import _DssmFusedLoss
         scal, rows, _ = _DssmFusedLoss.apply(
             sim.view(H, B), Q1, Q2, torch.stack(rps).view(H, B), reward[:H].reshape(H, B),
             reward_pi.view(H + 1, B)[:H], next_q, weights,
@@ -239,22 +241,25 @@ class DssmLearner:
         return self._finish(buffer, idxs, rows[3].view(B, 1), [t.detach() for t in zs], noise, H,
                             (scal[0], scal[1], scal[2], scal[3]), weighted, grad_norm, intrinsic.view(H + 1, B, 1))
 
+    def _rollout_one(self, z, a):
+        """One `next` from a fresh hidden state -> the predicted latent."""
+        m = self.agent.model
+        return m.next(z, a, m.init_hidden_state(z.shape[0], z.device).to(z.dtype))[0]
+
     def _intrinsic_torch(self, obs, next_obses, action):
         """:421-443 call by call (H + 1 train-mode `next` + `pred_z` passes), the RunningMeanStd by `rms_update`."""
         m, mt, H = self.agent.model, self.agent.model_target, int(self.cfg.horizon)
         with torch.no_grad():
             zs_target = mt.h(next_obses)
             z_traj = m.h(torch.cat([obs.unsqueeze(0), next_obses], dim=0))
-            out = []
-            for t in range(H + 1):
-                hidden = m.init_hidden_state(obs.shape[0], obs.device).to(obs.dtype)
-                zl, _, _ = m.next(z_traj[t], action[t], hidden)
-                pred = F.normalize(m.pred_z(zl).unsqueeze(0), dim=-1, p=2)
-                target = F.normalize(zs_target[t:t + 1], dim=-1, p=2)
-                out.append((2.0 - 2.0 * (pred * target).sum(dim=-1, keepdim=True))[0])
-            raw = torch.stack(out)                                   # [H + 1, B, 1]
+            raw = torch.stack([cosine_loss(m, self._rollout_one(z_traj[t], action[t]), zs_target[t])
+                               for t in range(H + 1)])              # [H + 1, B, 1]
             rms_update(self.rms, raw)
             return rms_normalize(self.rms, raw)
+
+    def _similarity_torch(self, queries, keys, n):
+        loss = cosine_loss(self.agent.model, torch.cat(queries, dim=0), torch.cat(keys, dim=0))
+        return loss.reshape(n, self.cfg.batch_size, -1).sum(dim=0)
 
     def _step_torch(self, buffer, noise):
         a, cfg, m, mt = self.agent, self.cfg, self.agent.model, self.agent.model_target
@@ -295,9 +300,7 @@ class DssmLearner:
             queries.append(z)
             keys.append(next_zs[t].detach())
             zs.append(z.detach())
-        q = F.normalize(m.pred_z(torch.cat(queries, dim=0)), dim=-1, p=2)
-        k = F.normalize(torch.cat(keys, dim=0), dim=-1, p=2)
-        similarity_loss = 0 + (2.0 - 2.0 * (q * k).sum(dim=-1)).reshape(H, B, -1).sum(dim=0)
+        similarity_loss = 0 + self._similarity_torch(queries, keys, H)
         model_loss = cfg.similarity_coef * similarity_loss.clamp(max=1e4) + cfg.reward_coef * reward_loss.clamp(max=1e4)
         td_loss = cfg.value_coef * value_loss.clamp(max=1e4)
         total_loss = model_loss + td_loss
@@ -310,66 +313,13 @@ class DssmLearner:
                             (similarity_loss.mean(), reward_loss.mean(), value_loss.mean(), total_loss.mean()),
                             weighted, grad_norm, intrinsic)
 
-    @torch.no_grad()
-    def ema(self):
-        """helper.py:48-52: target <- lerp(target, model, tau)."""
-        torch._foreach_lerp_(self.target_params, self.params, self.cfg.tau)
-
-    # ------------------------------------------------------------------ graph driver (learner.Learner's)
-    def _capturable(self, buffer):
-        return self.graph and getattr(buffer, "graph_safe", False)
-
     def update(self, buffer, step, noise=None):
         """`TdICemSimDssm.update` semantics -> (metrics tensor [8] on the device, explore_coef); no synchronisation."""
         coef = linear_schedule(self.cfg.explore_schedule, step)
         self.coef.fill_(coef)
-        if self.device.type != "cuda":
-            return self._update(buffer, step, noise), coef
-        prec = torch.get_float32_matmul_precision()
-        tf32 = torch.backends.cuda.matmul.allow_tf32
-        torch.set_float32_matmul_precision("highest")
-        torch.backends.cuda.matmul.allow_tf32 = False
-        try:
-            return self._update(buffer, step, noise), coef
-        finally:
-            torch.set_float32_matmul_precision(prec)
-            torch.backends.cuda.matmul.allow_tf32 = tf32
-
-    def _update(self, buffer, step, noise=None):
-        model = self.agent.model
-        model.train()
-        if noise is not None or not self._capturable(buffer) or self.calls < self.warmup:
-            if self._capturable(buffer) and self.calls == self.warmup - 1:
-                # the last warm-up runs on a side stream, as graph capture requires of lazily created state
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    m = self.step(buffer, noise)
-                torch.cuda.current_stream().wait_stream(s)
-            else:
-                m = self.step(buffer, noise)
-        else:
-            key = (buffer.idx, buffer._full)
-            g = self._graphs.get(key)
-            if g is None:
-                if len(self._graphs) >= 2:   # the buffer grew: drop the stale captures
-                    self._graphs.clear()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    out = self.step(buffer)
-                g = self._graphs[key] = (graph, out)
-                # capture recorded the kernels without running them: run this call's update
-            g[0].replay()
-            m = g[1]
-        self.calls += 1
-        if step % self.cfg.update_freq == 0:
-            self.ema()
-        model.eval()
-        planner = getattr(self.agent, "planner", None)
-        if planner is not None:
-            # parameters changed in place (a graph replay does not bump tensor versions): repack for planning
-            planner._packed_key = None
-        return m
+        # (on the CPU nothing follows the matmul precision the driver pins)
+        run = super().update if self.device.type == "cuda" else self._update
+        return run(buffer, step, noise), coef
 
 
 def check_sim_learner_cfg(cfg):
@@ -442,7 +392,6 @@ class DssmSimLearner(DssmLearner):
         x = torch.cat([torch.stack(zin), action[W:H]], dim=-1).view(N * B, -1)
         Q1, Q2 = m._Q1(x).view(N, B), m._Q2(x).view(N, B)
         sim_s = ts.similarity_loss(zout, nz_tg[W * B:H * B])
-        from .dssm_train import _DssmSimFusedLoss
         scal, rows, _ = _DssmSimFusedLoss.apply(
             torch.cat([sim_w, sim_s]).view(H, B), Q1, Q2, torch.stack(rps).view(N, B), reward[W:H].reshape(N, B),
             reward_pi.view(H + 1, B)[W:H], next_q, weights,
@@ -469,18 +418,10 @@ class DssmSimLearner(DssmLearner):
                 out.append(torch.zeros(obs.shape[0], 1, dtype=obs.dtype, device=obs.device))
             for t in range(W, H + 1):
                 zl, hidden, _ = m.next(zs_traj[t], action[t], hidden)
-                pred = F.normalize(m.pred_z(zl).unsqueeze(0), dim=-1, p=2)
-                target = F.normalize(zs_target[t:t + 1], dim=-1, p=2)
-                out.append((2.0 - 2.0 * (pred * target).sum(dim=-1, keepdim=True))[0])
+                out.append(cosine_loss(m, zl, zs_target[t]))
             raw = torch.stack(out)                                   # [H + 1, B, 1], zeros in the warm-up rows
             rms_update(self.rms, raw)
             return rms_normalize(self.rms, raw)
-
-    def _similarity_torch(self, queries, keys, n):
-        m = self.agent.model
-        q = F.normalize(m.pred_z(torch.cat(queries, dim=0)), dim=-1, p=2)
-        k = F.normalize(torch.cat(keys, dim=0), dim=-1, p=2)
-        return (2.0 - 2.0 * (q * k).sum(dim=-1)).reshape(n, self.cfg.batch_size, -1).sum(dim=0)
 
     def _step_torch(self, buffer, noise):
         a, cfg, m, mt = self.agent, self.cfg, self.agent.model, self.agent.model_target

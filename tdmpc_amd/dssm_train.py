@@ -25,6 +25,10 @@ For the MPC agent's update (`TdMpcSimDssm.update`, tdmpc_amd/drnn_learner.py::Ds
 closed-loop steps (tdmpc_drnn_intrinsic_chain_fwd; `chain_mode` 0 runs the recurrence as a launch chain, 1 in one
 launch; the default is TDMPC_DSSM_CHAIN_MODE or CHAIN_MODE below), and `_DssmSimFusedLoss` that update's loss composition.
 
+`LossStep` is what `DssmTrainStep` shares with the MLP iCEM agent's `icem_learner.IcemTrainStep` (`similarity_loss`, the
+operand checks, the segmented passes' workspaces), and `_StepFusedLoss` the one body of the three updates' fused loss
+Functions (`_DssmFusedLoss`, `_DssmSimFusedLoss`, `icem_learner._IcemFusedLoss`).
+
 There is no eager fall-back: a missing library or an unsupported shape raises. The update itself (optimisers, replay,
 the encoder / Q / pi passes) is `tdmpc_amd.drnn_learner.DssmLearner`.
 """
@@ -164,86 +168,70 @@ class _LossFn(torch.autograd.Function):
         return (None, dq, None) + tuple(g if need[3 + i] else None for i, g in enumerate(grads))
 
 
-class _DssmFusedLoss(torch.autograd.Function):
-    """TdICemSimDssm.update's loss composition (tdmpc_icem_similarity_drnn.py:471-485, :497-499, :522-530) and its
-    backward as HIP kernels (tdmpc_drnn_loss_forward / _backward): forward(sim, q1, q2, rp, rw, rwpi, nq [H, B], w [B],
-    coefs = (similarity_coef, reward_coef, value_coef, discount, td_lambda)) -> (scal [8], rows [6, B], td [H, B]);
-    scal = (mean similarity, mean reward, mean value, mean total, weighted, mean w, mean model_loss, mean td_loss),
-    rows = (similarity, reward, value, clamped priority, model_loss, td_loss) per batch row, td = the TD-lambda targets.
-    Only scal[4] (the weighted loss) carries a gradient, to sim, q1, q2 and rp."""
+class _StepFusedLoss(torch.autograd.Function):
+    """One update's loss composition and its backward as HIP kernels (`ABI`loss_forward / _backward), written once for
+    the three variants below: forward(sim [H, B], q1, q2, rp, rw, rwpi, nq [N, B], w [B], coefs) -> (scal [SCAL],
+    rows [ROWS, B], td [N, B]); N = H unless the variant is SHOOT. Only scal[4] (the weighted loss) carries a gradient,
+    to sim, q1, q2 and rp. A variant names its entry points, its ctypes struct and `_args`, how H / N / B go into it."""
 
-    @staticmethod
-    def forward(ctx, sim, q1, q2, rp, rw, rwpi, nq, w, coefs):
+    ABI = ARGS = ROWS = SCAL = None
+    SHOOT = False   # q1 .. nq cover the N = H - W shoot steps only
+
+    @classmethod
+    def _args(cls, ins, H, N, B, coefs):
+        return cls.ARGS(*[t.data_ptr() for t in ins], H, B, *[float(c) for c in coefs])
+
+    @classmethod
+    def forward(cls, ctx, sim, q1, q2, rp, rw, rwpi, nq, w, coefs):
         H, B = sim.shape
+        N = q1.shape[0] if cls.SHOOT else H
         ins = [_f32c(t) for t in (sim, q1, q2, rp, rw, rwpi, nq, w)]
-        for t in ins[:7]:
-            if tuple(t.shape) != (H, B):
-                raise ValueError(f"_DssmFusedLoss: every operand but w must be [{H}, {B}], got {tuple(t.shape)}")
-        if tuple(ins[7].shape) != (B,):
-            raise ValueError(f"_DssmFusedLoss: w must be [{B}], got {tuple(ins[7].shape)}")
-        args = DrnnLossArgs(*[t.data_ptr() for t in ins], H, B, *[float(c) for c in coefs])
-        td, rows, scal = sim.new_empty(H, B), sim.new_empty(6, B), sim.new_empty(8)
-        call("tdmpc_drnn_loss_forward", args, td, rows, scal, torch.cuda.current_stream().cuda_stream)
-        ctx.save_for_backward(*ins, td, rows, scal)
-        ctx.coefs = coefs
-        ctx.mark_non_differentiable(rows, td)
-        return scal, rows, td
-
-    @staticmethod
-    def backward(ctx, g_scal, g_rows, g_td):
-        *ins, td, rows, scal = ctx.saved_tensors
-        H, B = ins[0].shape
-        args = DrnnLossArgs(*[t.data_ptr() for t in ins], H, B, *[float(c) for c in ctx.coefs])
-        g = g_scal.contiguous()
-        need = ctx.needs_input_grad
-        dsim, dq1, dq2, drp = (torch.empty_like(ins[0]) if need[i] else None for i in range(4))
-        call("tdmpc_drnn_loss_backward", args, td, rows, scal, g.data_ptr() + 16, ptr(dsim), ptr(dq1), ptr(dq2),
-             ptr(drp), torch.cuda.current_stream().cuda_stream)
-        return dsim, dq1, dq2, drp, None, None, None, None, None
-
-
-class _DssmSimFusedLoss(torch.autograd.Function):
-    """TdMpcSimDssm.update's loss composition (tdmpc_similarity_drnn.py:447-471) and its backward as HIP kernels
-    (tdmpc_drnn_sim_loss_forward / _backward): forward(sim [H, B], q1, q2, rp, rw, rwpi, nq [H - W, B] (the shoot steps),
-    w [B], coefs = (similarity_coef, reward_coef, value_coef, discount)) -> (scal [6], rows [5, B], td [H - W, B]);
-    scal = (mean similarity, mean reward, mean value, mean total, weighted = mean(total) mean(w), mean w), rows =
-    (similarity, reward, value, clamped priority, total) per batch row, td = the one-step TD targets. Only scal[4]
-    carries a gradient, to sim, q1, q2 and rp."""
-
-    @staticmethod
-    def _args(ins, H, N, B, coefs):
-        return DrnnSimLossArgs(*[t.data_ptr() for t in ins], H, H - N, B, *[float(c) for c in coefs])
-
-    @staticmethod
-    def forward(ctx, sim, q1, q2, rp, rw, rwpi, nq, w, coefs):
-        H, B = sim.shape
-        N = q1.shape[0]
-        ins = [_f32c(t) for t in (sim, q1, q2, rp, rw, rwpi, nq, w)]
-        if not 1 <= N < H:
-            raise ValueError(f"_DssmSimFusedLoss: {N} shoot steps of {H} (1 <= horizon - warmup_len <= horizon - 1)")
+        if cls.SHOOT and not 1 <= N < H:
+            raise ValueError(f"{cls.__name__}: {N} shoot steps of {H} (1 <= horizon - warmup_len <= horizon - 1)")
         for t in ins[1:7]:
             if tuple(t.shape) != (N, B):
-                raise ValueError(f"_DssmSimFusedLoss: q1 .. nq must be [{N}, {B}], got {tuple(t.shape)}")
+                raise ValueError(f"{cls.__name__}: {'q1 .. nq' if cls.SHOOT else 'every operand but w'} must be "
+                                 f"[{N}, {B}], got {tuple(t.shape)}")
         if tuple(ins[7].shape) != (B,):
-            raise ValueError(f"_DssmSimFusedLoss: w must be [{B}], got {tuple(ins[7].shape)}")
-        td, rows, scal = sim.new_empty(N, B), sim.new_empty(5, B), sim.new_empty(6)
-        call("tdmpc_drnn_sim_loss_forward", _DssmSimFusedLoss._args(ins, H, N, B, coefs), td, rows, scal,
+            raise ValueError(f"{cls.__name__}: w must be [{B}], got {tuple(ins[7].shape)}")
+        td, rows, scal = sim.new_empty(N, B), sim.new_empty(cls.ROWS, B), sim.new_empty(cls.SCAL)
+        call(cls.ABI + "loss_forward", cls._args(ins, H, N, B, coefs), td, rows, scal,
              torch.cuda.current_stream().cuda_stream)
         ctx.save_for_backward(*ins, td, rows, scal)
         ctx.coefs = coefs
         ctx.mark_non_differentiable(rows, td)
         return scal, rows, td
 
-    @staticmethod
-    def backward(ctx, g_scal, g_rows, g_td):
+    @classmethod
+    def backward(cls, ctx, g_scal, g_rows, g_td):
         *ins, td, rows, scal = ctx.saved_tensors
         (H, B), N = ins[0].shape, ins[1].shape[0]
         g = g_scal.contiguous()
         need = ctx.needs_input_grad
         dsim, dq1, dq2, drp = (torch.empty_like(ins[i]) if need[i] else None for i in range(4))
-        call("tdmpc_drnn_sim_loss_backward", _DssmSimFusedLoss._args(ins, H, N, B, ctx.coefs), td, rows, scal,
-             g.data_ptr() + 16, ptr(dsim), ptr(dq1), ptr(dq2), ptr(drp), torch.cuda.current_stream().cuda_stream)
+        call(cls.ABI + "loss_backward", cls._args(ins, H, N, B, ctx.coefs), td, rows, scal, g.data_ptr() + 16, ptr(dsim),
+             ptr(dq1), ptr(dq2), ptr(drp), torch.cuda.current_stream().cuda_stream)
         return dsim, dq1, dq2, drp, None, None, None, None, None
+
+
+class _DssmFusedLoss(_StepFusedLoss):
+    """TdICemSimDssm.update's loss composition (tdmpc_icem_similarity_drnn.py:471-485, :497-499, :522-530): coefs =
+    (similarity_coef, reward_coef, value_coef, discount, td_lambda); scal = (mean similarity, mean reward, mean value,
+    mean total, weighted, mean w, mean model_loss, mean td_loss), rows = (similarity, reward, value, clamped priority,
+    model_loss, td_loss) per batch row, td = the TD-lambda targets."""
+    ABI, ARGS, ROWS, SCAL = "tdmpc_drnn_", DrnnLossArgs, 6, 8
+
+
+class _DssmSimFusedLoss(_StepFusedLoss):
+    """TdMpcSimDssm.update's loss composition (tdmpc_similarity_drnn.py:447-471): q1 .. nq over the H - W shoot steps;
+    coefs = (similarity_coef, reward_coef, value_coef, discount); scal = (mean similarity, mean reward, mean value,
+    mean total, weighted = mean(total) mean(w), mean w), rows = (similarity, reward, value, clamped priority, total) per
+    batch row, td = the one-step TD targets."""
+    ABI, ARGS, ROWS, SCAL, SHOOT = "tdmpc_drnn_sim_", DrnnSimLossArgs, 5, 6, True
+
+    @classmethod
+    def _args(cls, ins, H, N, B, coefs):
+        return cls.ARGS(*[t.data_ptr() for t in ins], H, H - N, B, *[float(c) for c in coefs])
 
 
 def new_rms_state(device):
@@ -266,66 +254,49 @@ def intrinsic_finish(loss, rms, coef, reward):
     return intrinsic, reward_pi
 
 
-class DssmTrainStep:
-    """Differentiable `DSSM.next` (train mode) and `similarity_loss` on HIP for `model` (a `tdmpc_amd.dssm.DSSM` on the
-    GPU, fp32). max_rows: the largest batch of `next`; max_loss_rows: of `similarity_loss` (default
-    min(4096, max_rows * max_steps): the reference concatenates the per-step predictions)."""
+class LossStep:
+    """What the train steps of the similarity learners share (`DssmTrainStep`; `icem_learner.IcemTrainStep`): the
+    reference's `similarity_loss` on HIP, differentiable in the queries and `_predictor`'s parameters (entry points
+    LOSS_ABI + fwd / bwd), with its saved-activation pool and workspace; the checks of every pass's operands; the
+    workspaces of the segmented intrinsic-reward passes."""
 
-    LOSS_ABI = "tdmpc_drnn_simloss_"   # _LossFn's entry points (tdmpc_amd.icem_learner.IcemTrainStep: the tdmpc_dims ones)
+    LOSS_ABI = None
 
-    def __init__(self, model, max_rows: int, max_steps: int | None = None, max_loss_rows: int | None = None,
-                 max_losses: int = 2):
-        cfg = model.cfg
-        dev = next(model.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("DssmTrainStep: the model must be on the GPU (there is no CPU path)")
-        self.model, self.cfg = model, cfg
-        self.L, self.A, self.Hd = int(cfg.latent_dim), int(cfg.action_dim), int(cfg.hidden_dim)
-        self.max_rows = int(max_rows)
-        self.max_steps = int(max_steps if max_steps is not None else cfg.horizon + 1)
-        self.max_loss_rows = int(max_loss_rows if max_loss_rows is not None
-                                 else min(_lib.DT_MAX_ROWS, self.max_rows * self.max_steps))
-        self.dims = drnn_dims_from_cfg(cfg)
-        _lib.lib()
-        if _lib.lib().tdmpc_drnn_train_version() != _lib.DRNN_TRAIN_VERSION:
-            raise RuntimeError("libtdmpc_hip: tdmpc_drnn_train_version mismatch")
-        sn, sl = DrnnTrainSizes(), DrnnTrainSizes()
-        call("tdmpc_drnn_train_sizes_for", self.dims, self.max_rows, sn)
-        call("tdmpc_drnn_train_sizes_for", self.dims, self.max_loss_rows, sl)
-        named = dict(model.named_parameters())
+    def __init__(self, model, dims, max_loss_rows):
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__}: the model must be on the GPU (there is no CPU path)")
+        self.model, self.cfg, self.dims = model, model.cfg, dims
+        self.L, self.A = int(model.cfg.latent_dim), int(model.cfg.action_dim)
+        self.max_loss_rows = int(max_loss_rows)
+        self._loss_params = self._params(LOSS_PARAMS)
         bufs = dict(model.named_buffers())
-        self._next_params = tuple(named[k] for k in NEXT_PARAMS)
-        self._loss_params = tuple(named[k] for k in LOSS_PARAMS)
-        for p in self._next_params + self._loss_params:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("DssmTrainStep: the model's parameters must be contiguous float32")
-        self._next_stats = (bufs["_dynamics.prior_mlp.1.running_mean"], bufs["_dynamics.prior_mlp.1.running_var"])
         self._loss_stats = (bufs["_predictor.1.running_mean"], bufs["_predictor.1.running_var"])
-        self._next_pool = _Pool(self.max_steps, sn.next_saved_floats, dev, "max_steps")
-        self._loss_pool = _Pool(int(max_losses), sl.loss_saved_floats, dev, "max_losses")
-        self._ws = torch.empty(max(sn.workspace_floats, sl.workspace_floats), dtype=torch.float32, device=dev)
-        self._iws = {}   # (segments, rows per segment) -> the workspace of intrinsic_loss
-        self._cws = {}   # likewise of intrinsic_chain_loss
-        self.chain_mode = int(os.environ.get("TDMPC_DSSM_CHAIN_MODE", CHAIN_MODE))
+        self._seg_ws = {}   # (entry point, segments, rows per segment) -> the workspace of a segmented pass
+
+    def _params(self, names):
+        named = dict(self.model.named_parameters())
+        params = tuple(named[k] for k in names)
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"{type(self).__name__}: the model's parameters must be contiguous float32")
+        return params
+
+    def _loss_buffers(self, max_losses, saved_floats, workspace_floats):
+        self._loss_pool = _Pool(int(max_losses), saved_floats, self.device, "max_losses")
+        self._ws = torch.empty(workspace_floats, dtype=torch.float32, device=self.device)
 
     def _check(self, what, rows, cap, *shaped):
+        name = type(self).__name__
         if not self.model.training:
-            raise RuntimeError(f"DssmTrainStep.{what}: the model is in eval() mode; these passes run the BatchNorms on "
+            raise RuntimeError(f"{name}.{what}: the model is in eval() mode; these passes run the BatchNorms on "
                                "batch statistics (model.train()). For inference use DrnnPlanner.next")
         if rows > cap:
-            raise ValueError(f"DssmTrainStep.{what}: {rows} rows, sized for {cap}")
-        for name, t, width in shaped:
+            raise ValueError(f"{name}.{what}: {rows} rows, sized for {cap}")
+        for arg, t, width in shaped:
             if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != width or not t.is_cuda:
-                raise ValueError(f"DssmTrainStep.{what}: {name} must be a GPU tensor of shape [{rows}, {width}], got "
+                raise ValueError(f"{name}.{what}: {arg} must be a GPU tensor of shape [{rows}, {width}], got "
                                  f"{tuple(t.shape)} on {t.device}")
-
-    def next(self, z, a, h):
-        """`DSSM.next(z, a, h)` under `model.train()`: (z' [R, L], h' [R, Hd], r [R, 1]), differentiable in z, a, h and
-        the 20 parameter tensors of `_dynamics` and `_reward`. Moves prior_mlp's running statistics."""
-        self._check("next", z.shape[0], self.max_rows, ("z", z, self.L), ("a", a, self.A), ("h", h, self.Hd))
-        zo, ho, ro = _NextFn.apply(self, z, a, h, *self._next_params)
-        self.model._dynamics.prior_mlp[1].num_batches_tracked += 1
-        return zo, ho, ro.unsqueeze(1)
 
     def similarity_loss(self, queries, keys):
         """The reference's `similarity_loss(queries, keys)` -> [R]: 2 - 2 cos(_predictor(queries), keys) per row, the
@@ -340,27 +311,72 @@ class DssmTrainStep:
         self.model._predictor[1].num_batches_tracked += 1
         return loss
 
+    def _segments(self, what, z, a, keys, segments):
+        """The operands of a segmented pass over the row blocks [s B, (s + 1) B) of z [S B, L], a [S B, A] and keys
+        [S B, L], checked -> (z, a, keys as contiguous float32, S, B)."""
+        R, S = z.shape[0], int(segments)
+        if S < 1 or R % S:
+            raise ValueError(f"{type(self).__name__}.{what}: {R} rows do not split into {S} segments")
+        self._check(what, R, _lib.DT_MAX_ROWS, ("z", z, self.L), ("a", a, self.A), ("keys", keys, self.L))
+        return _f32c(z), _f32c(a), _f32c(keys), S, R // S
+
+    def _segment_workspace(self, entry, S, B):
+        """The workspace of a pass over S segments of B rows, sized by the entry point `entry` and kept."""
+        ws = self._seg_ws.get((entry, S, B))
+        if ws is None:
+            n = C.c_size_t()
+            call(entry, self.dims, S, B, C.byref(n))
+            ws = self._seg_ws[(entry, S, B)] = torch.empty(n.value, dtype=torch.float32, device=self.device)
+        return ws
+
+
+class DssmTrainStep(LossStep):
+    """Differentiable `DSSM.next` (train mode) and `similarity_loss` on HIP for `model` (a `tdmpc_amd.dssm.DSSM` on the
+    GPU, fp32). max_rows: the largest batch of `next`; max_loss_rows: of `similarity_loss` (default
+    min(4096, max_rows * max_steps): the reference concatenates the per-step predictions)."""
+
+    LOSS_ABI = "tdmpc_drnn_simloss_"
+
+    def __init__(self, model, max_rows: int, max_steps: int | None = None, max_loss_rows: int | None = None,
+                 max_losses: int = 2):
+        cfg = model.cfg
+        self.max_rows = int(max_rows)
+        self.max_steps = int(max_steps if max_steps is not None else cfg.horizon + 1)
+        super().__init__(model, drnn_dims_from_cfg(cfg), max_loss_rows if max_loss_rows is not None
+                         else min(_lib.DT_MAX_ROWS, self.max_rows * self.max_steps))
+        self.Hd = int(cfg.hidden_dim)
+        if _lib.lib().tdmpc_drnn_train_version() != _lib.DRNN_TRAIN_VERSION:
+            raise RuntimeError("libtdmpc_hip: tdmpc_drnn_train_version mismatch")
+        sn, sl = DrnnTrainSizes(), DrnnTrainSizes()
+        call("tdmpc_drnn_train_sizes_for", self.dims, self.max_rows, sn)
+        call("tdmpc_drnn_train_sizes_for", self.dims, self.max_loss_rows, sl)
+        self._next_params = self._params(NEXT_PARAMS)
+        bufs = dict(model.named_buffers())
+        self._next_stats = (bufs["_dynamics.prior_mlp.1.running_mean"], bufs["_dynamics.prior_mlp.1.running_var"])
+        self._next_pool = _Pool(self.max_steps, sn.next_saved_floats, self.device, "max_steps")
+        self._loss_buffers(max_losses, sl.loss_saved_floats, max(sn.workspace_floats, sl.workspace_floats))
+        self.chain_mode = int(os.environ.get("TDMPC_DSSM_CHAIN_MODE", CHAIN_MODE))
+
+    def next(self, z, a, h):
+        """`DSSM.next(z, a, h)` under `model.train()`: (z' [R, L], h' [R, Hd], r [R, 1]), differentiable in z, a, h and
+        the 20 parameter tensors of `_dynamics` and `_reward`. Moves prior_mlp's running statistics."""
+        self._check("next", z.shape[0], self.max_rows, ("z", z, self.L), ("a", a, self.A), ("h", h, self.Hd))
+        zo, ho, ro = _NextFn.apply(self, z, a, h, *self._next_params)
+        self.model._dynamics.prior_mlp[1].num_batches_tracked += 1
+        return zo, ho, ro.unsqueeze(1)
+
     @torch.no_grad()
     def intrinsic_loss(self, z, a, keys, segments):
         """`segments` independent `next(z, a, 0)` + `similarity_loss(z', keys)` passes over the row blocks
         [s B, (s + 1) B) of z [S B, L], a [S B, A], keys [S B, L] as one launch chain -> loss [S B]. Forward only. Each
         segment normalises both BatchNorms over its own B rows and moves their running statistics once, in segment
         order: bitwise what S pairs of `next` / `similarity_loss` calls on the segments give."""
-        R = z.shape[0]
-        S = int(segments)
-        if S < 1 or R % S:
-            raise ValueError(f"DssmTrainStep.intrinsic_loss: {R} rows do not split into {S} segments")
-        self._check("intrinsic_loss", R, _lib.DT_MAX_ROWS, ("z", z, self.L), ("a", a, self.A), ("keys", keys, self.L))
-        z, a, keys = _f32c(z), _f32c(a), _f32c(keys)
-        ws = self._iws.get((S, R // S))
-        if ws is None:
-            n = C.c_size_t()
-            call("tdmpc_drnn_intrinsic_workspace_floats", self.dims, S, R // S, C.byref(n))
-            ws = self._iws[(S, R // S)] = torch.empty(n.value, dtype=torch.float32, device=z.device)
-        loss = z.new_empty(R)
+        z, a, keys, S, B = self._segments("intrinsic_loss", z, a, keys, segments)
+        ws = self._segment_workspace("tdmpc_drnn_intrinsic_workspace_floats", S, B)
+        loss = z.new_empty(S * B)
         ntab, nn_ = _table(self._next_params, self._next_stats)
         ltab, nl = _table(self._loss_params, self._loss_stats)
-        call("tdmpc_drnn_intrinsic_fwd", self.dims, ntab, nn_, ltab, nl, z, a, keys, S, R // S, loss, ws, ws.numel(),
+        call("tdmpc_drnn_intrinsic_fwd", self.dims, ntab, nn_, ltab, nl, z, a, keys, S, B, loss, ws, ws.numel(),
              torch.cuda.current_stream().cuda_stream)
         self.model._dynamics.prior_mlp[1].num_batches_tracked += S
         self.model._predictor[1].num_batches_tracked += S
@@ -382,21 +398,11 @@ class DssmTrainStep:
         the recurrence as a launch chain (bitwise S `next` calls + `similarity_loss` on the later segments), 1 in one
         launch; default `self.chain_mode`. hidden=True: -> (loss, h_out [B, Hd], every segment's hidden state
         [S, B, Hd], a view of the workspace that the next call overwrites)."""
-        R = z.shape[0]
-        S, W = int(segments), int(warm)
-        if S < 1 or R % S:
-            raise ValueError(f"DssmTrainStep.intrinsic_chain_loss: {R} rows do not split into {S} segments")
+        z, a, keys, S, B = self._segments("intrinsic_chain_loss", z, a, keys, segments)
+        R, W = S * B, int(warm)
         if not 0 <= W < S:
             raise ValueError(f"DssmTrainStep.intrinsic_chain_loss: warm={W} is not in [0, {S})")
-        self._check("intrinsic_chain_loss", R, _lib.DT_MAX_ROWS, ("z", z, self.L), ("a", a, self.A),
-                    ("keys", keys, self.L))
-        z, a, keys = _f32c(z), _f32c(a), _f32c(keys)
-        B = R // S
-        ws = self._cws.get((S, B))
-        if ws is None:
-            n = C.c_size_t()
-            call("tdmpc_drnn_intrinsic_chain_workspace_floats", self.dims, S, B, C.byref(n))
-            ws = self._cws[(S, B)] = torch.empty(n.value, dtype=torch.float32, device=z.device)
+        ws = self._segment_workspace("tdmpc_drnn_intrinsic_chain_workspace_floats", S, B)
         loss, h_out = z.new_empty(R), z.new_empty(B, self.Hd)
         ntab, nn_ = _table(self._next_params, self._next_stats)
         ltab, nl = _table(self._loss_params, self._loss_stats)

@@ -21,6 +21,9 @@ eager updates (which also create Adam's state), one whole update -- the device r
 grad-norm clipping, Adam (capturable, foreach), the priority write-back, the policy update -- is captured
 into ONE HIP graph per (buffer fill, EMA) shape and replayed: no Python in the loop, no host sync, the RNG
 (philox, graph-safe) advancing exactly as the eager calls would. The EMA of the target is one foreach lerp.
+
+The warm-up / capture / replay sequence is `GraphLearner`, the base of `Learner` and of the DSSM and MLP iCEM learners
+(tdmpc_amd/drnn_learner.py, icem_learner.py).
 """
 from __future__ import annotations
 
@@ -29,6 +32,8 @@ import os
 
 import torch
 import torch.nn.functional as F
+
+from . import learner_engine
 
 METRICS = ("consistency_loss", "reward_loss", "value_loss", "pi_loss", "total_loss", "weighted_loss", "grad_norm")
 
@@ -135,19 +140,95 @@ def _l1(pred, target):
     return F.l1_loss(pred, target, reduction="none")
 
 
-class Learner:
-    """Owns the optimisers and (in graph mode) the captured update graphs of one TDMPC agent."""
+class GraphLearner:
+    """The update driver of every learner here (`Learner`; `drnn_learner.DssmLearner` and its subclasses): `update` runs
+    `self.step(buffer, noise)` under full float32 matmul precision -- eagerly for the first `warmup` calls (the last of
+    them on a side stream) and whenever the buffer is not graph-safe or explicit noise is given, otherwise as one HIP
+    graph per (buffer.idx, buffer._full), captured once and replayed --, then the EMA every `update_freq` steps and
+    `model.eval()`. A subclass provides `step` and may override `_before_capture`, `_after_update` and `ema`."""
 
-    def __init__(self, agent, graph: bool = True, warmup: int = 3):
+    def __init__(self, agent, graph: bool, warmup: int):
         self.agent = agent
         self.cfg = agent.cfg
         self.graph = graph
         self.warmup = warmup
-        model = agent.model
-        self.params = list(model.parameters())
-        self.pi_params = list(model._pi.parameters())
+        self.params = list(agent.model.parameters())
+        self.pi_params = list(agent.model._pi.parameters())
         self.target_params = list(agent.model_target.parameters())
-        from . import learner_engine
+        self.calls = 0
+        self._graphs = {}
+
+    @torch.no_grad()
+    def ema(self):
+        """helper.py:48-52: target <- lerp(target, model, tau)."""
+        torch._foreach_lerp_(self.target_params, self.params, self.cfg.tau)
+
+    def _before_capture(self):
+        """What must exist before `step` is captured into a graph."""
+
+    def _after_update(self):
+        # parameters changed in place (a graph replay does not bump tensor versions): repack for planning
+        planner = getattr(self.agent, "planner", None)
+        if planner is not None:
+            planner._packed_key = None
+
+    def _capturable(self, buffer):
+        return self.graph and getattr(buffer, "graph_safe", False)
+
+    def update(self, buffer, step, noise=None):
+        """One update -> what `step` returns, on the device (no sync)."""
+        # the hipBLASLt products follow torch's process-wide fp32 matmul setting: pin full fp32 around every eager pass
+        # and capture, whatever the caller set (ADVICE r5)
+        prec = torch.get_float32_matmul_precision()
+        tf32 = torch.backends.cuda.matmul.allow_tf32
+        torch.set_float32_matmul_precision("highest")
+        torch.backends.cuda.matmul.allow_tf32 = False
+        try:
+            return self._update(buffer, step, noise)
+        finally:
+            torch.set_float32_matmul_precision(prec)
+            torch.backends.cuda.matmul.allow_tf32 = tf32
+
+    def _update(self, buffer, step, noise=None):
+        self.agent.model.train()
+        if noise is not None or not self._capturable(buffer) or self.calls < self.warmup:
+            if self._capturable(buffer) and self.calls == self.warmup - 1:
+                # the last warm-up runs on a side stream, as graph capture requires of lazily created state
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    m = self.step(buffer, noise)
+                torch.cuda.current_stream().wait_stream(s)
+            else:
+                m = self.step(buffer, noise)
+        else:
+            key = (buffer.idx, buffer._full)
+            g = self._graphs.get(key)
+            if g is None:
+                if len(self._graphs) >= 2:   # the buffer grew: drop the stale captures
+                    self._graphs.clear()
+                self._before_capture()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    out = self.step(buffer)
+                g = self._graphs[key] = (graph, out)
+                # capture recorded the kernels without running them: run this call's update
+            g[0].replay()
+            m = g[1]
+        self.calls += 1
+        if step % self.cfg.update_freq == 0:
+            self.ema()
+        self.agent.model.eval()
+        self._after_update()
+        return m
+
+
+class Learner(GraphLearner):
+    """Owns the optimisers and (in graph mode) the captured update graphs of one TDMPC agent. `update` has TDMPC.update's
+    semantics -> metrics tensor [7] on the device."""
+
+    def __init__(self, agent, graph: bool = True, warmup: int = 3):
+        super().__init__(agent, graph, warmup)
         self.engine = None
         # (TDMPC_LEARNER_ENGINE=0: the autograd path with PyTorch's kernels, the bench's comparison leg)
         if (str(agent.device).startswith("cuda") and learner_engine.supported(self.cfg) and
@@ -160,8 +241,6 @@ class Learner:
             # tdmpc.py:62-63 (Adam over all TOLD parameters; the policy's own Adam, both at cfg.lr)
             agent.optim = torch.optim.Adam(self.params, lr=self.cfg.lr, capturable=graph, fused=True)
             agent.pi_optim = torch.optim.Adam(self.pi_params, lr=self.cfg.lr, capturable=graph, fused=True)
-        self.calls = 0
-        self._graphs = {}
         self._live_pack = False   # the last update repacked the planner's weights itself (repack_live)
         H = self.cfg.horizon
         # rho^t, t = 0..H, as float32 like the reference's Python-float scalar multiplies (tdmpc.py:212, 179)
@@ -260,64 +339,14 @@ class Learner:
 
     @torch.no_grad()
     def ema(self):
-        """helper.py:48-52: target <- lerp(target, model, tau)."""
+        return self.engine.ema(self.cfg.tau) if self.engine is not None else super().ema()
+
+    def _before_capture(self):
         if self.engine is not None:
-            return self.engine.ema(self.cfg.tau)
-        torch._foreach_lerp_(self.target_params, self.params, self.cfg.tau)
+            # the captured update repacks the planner from the engine's buffer (repack_live): pack once now so the
+            # planner holds the live tensors and the pack's job table exists before the capture
+            self.agent.planner.pack(self.agent.model)
 
-    # ------------------------------------------------------------------ graph driver
-    def _capturable(self, buffer):
-        return self.graph and getattr(buffer, "graph_safe", False)
-
-    def update(self, buffer, step, noise=None):
-        """TDMPC.update semantics -> metrics tensor [7] on the device (no sync)."""
-        # the engine's hipBLASLt products (learner_engine.mm) follow torch's process-wide fp32 matmul setting: pin
-        # full fp32 around every eager pass and capture, whatever the caller set (ADVICE r5)
-        prec = torch.get_float32_matmul_precision()
-        tf32 = torch.backends.cuda.matmul.allow_tf32
-        torch.set_float32_matmul_precision("highest")
-        torch.backends.cuda.matmul.allow_tf32 = False
-        try:
-            return self._update(buffer, step, noise)
-        finally:
-            torch.set_float32_matmul_precision(prec)
-            torch.backends.cuda.matmul.allow_tf32 = tf32
-
-    def _update(self, buffer, step, noise=None):
-        self.agent.model.train()
-        if noise is not None or not self._capturable(buffer) or self.calls < self.warmup:
-            if self._capturable(buffer) and self.calls == self.warmup - 1:
-                # the last warm-up runs on a side stream, as graph capture requires of lazily created state
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    m = self.step(buffer, noise)
-                torch.cuda.current_stream().wait_stream(s)
-            else:
-                m = self.step(buffer, noise)
-        else:
-            key = (buffer.idx, buffer._full)
-            g = self._graphs.get(key)
-            if g is None:
-                if len(self._graphs) >= 2:   # the buffer grew: drop the stale captures
-                    self._graphs.clear()
-                if self.engine is not None:
-                    # the captured update repacks the planner from the engine's buffer (repack_live): pack once now
-                    # so the planner holds the live tensors and the pack's job table exists before the capture
-                    self.agent.planner.pack(self.agent.model)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    out = self.step(buffer)
-                g = self._graphs[key] = (graph, out)
-                # capture recorded the kernels without running them: run this call's update
-            g[0].replay()
-            m = g[1]
-        self.calls += 1
-        if step % self.cfg.update_freq == 0:
-            self.ema()
-        self.agent.model.eval()
-        # parameters changed in place (a graph replay does not bump tensor versions): repack for planning, unless
-        # the update itself repacked from the engine's buffer (repack_live)
-        if not self._live_pack:
-            self.agent.planner._packed_key = None
-        return m
+    def _after_update(self):
+        if not self._live_pack:   # (the update itself repacked from the engine's buffer, repack_live)
+            super()._after_update()

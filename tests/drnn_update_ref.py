@@ -65,6 +65,10 @@ def batch(cfg, seed):
     return obs, next_obses, action, reward, idxs, weights
 
 
+def case_batch(name):
+    return batch(case_cfg(name), CASES[name][7])
+
+
 def draws(cfg, seed):
     """2H + 1 [B, A] standard normal draws of one update (cases without a recording)."""
     rs = np.random.RandomState(seed)

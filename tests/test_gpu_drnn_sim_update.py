@@ -45,6 +45,7 @@ import torch
 
 import drnn_sim_update_ref as U
 import drnn_train_ref as R
+from update_gpu import gpu_learner, hold, same, snap, yardstick
 
 pytestmark = pytest.mark.gpu
 
@@ -204,9 +205,6 @@ def test_fused_sim_loss_matches_float64_autograd(H, W):
     torch.cuda.synchronize()
     assert tuple(td.shape) == (N, B) and tuple(rows.shape) == (5, B) and tuple(scal.shape) == (6,)
 
-    def same(tag, got, ref):
-        got, ref = got.detach().double().cpu().reshape(-1), ref.detach().double().reshape(-1)
-        torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-6 * float(ref.abs().max()), msg=lambda m: f"{tag}: {m}")
     same("td", td, want["td"])
     for i, k in enumerate(("sim", "rew", "val", "prio", "total")):
         same(k, rows[i], want[k])
@@ -219,46 +217,9 @@ def test_fused_sim_loss_matches_float64_autograd(H, W):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4, 5
-_WANT = {}
-
-
-def _want(name):
-    """The float64 yardstick's two updates (snapshots and zero-mean scales), once per case."""
-    if name not in _WANT:
-        _WANT[name] = U.run_ref(name, torch.float64, U.case_noise(name), scales=True)
-    return _WANT[name]
-
-
-def _gpu_learner(name, graph=False, warmup=3, **cfg_over):
+def _gpu_learner(name, **kw):
     from tdmpc_amd.drnn_learner import DssmSimLearner
-    cfg = U.case_cfg(name)
-    for k, v in cfg_over.items():
-        setattr(cfg, k, v)
-    model, target = U.make_models(cfg, name, device="cuda")
-    agent = SimpleNamespace(cfg=cfg, model=model, model_target=target, device=torch.device("cuda"), planner=None)
-    learner = DssmSimLearner(agent, graph=graph, warmup=warmup)
-    assert learner.hip
-    buf = U.FakeBuffer(tuple(t.cuda() for t in U.case_batch(name)))
-    return cfg, agent, learner, buf
-
-
-def _snap(cfg, agent, learner, buf, m):
-    torch.cuda.synchronize()
-    r = dict(metrics=np.array(m.tolist()), prio=buf.prios[-1].cpu().numpy(),
-             intrinsic=learner.last["intrinsic"].cpu().numpy(), rms=learner.rms.cpu().numpy(),
-             grads=U.grads_of(agent.model))
-    return U.snapshot(r, agent.model, agent.model_target, cfg)
-
-
-def _hold(tag, got, want, scales, cfg, floors, k):
-    figs = U.figures(got, want, scales, cfg.lr, cfg.tau)
-    over = {}
-    for cls, (f, where) in figs.items():
-        b = U.bound(floors, cls, k)
-        print(f"{tag} {cls}: gpu {f:.3e} ({where}), bound {b:.2e}")
-        if not f <= b:
-            over[cls] = (f, where, b)
-    assert not over, (tag, over)
+    return gpu_learner(U, DssmSimLearner, name, **kw)
 
 
 def _nbt(model):
@@ -268,7 +229,7 @@ def _nbt(model):
 @pytest.mark.parametrize("mode", [1, 0])
 @pytest.mark.parametrize("name", ["cheetah", "tiny", "wide"])
 def test_two_consecutive_updates_match_float64(name, mode):
-    want, scales = _want(name)
+    want, scales = yardstick(U, name)
     cfg, agent, learner, buf = _gpu_learner(name)
     learner.train_step.chain_mode = mode
     noise = [([n.cuda() for n in eps], [n.cuda() for n in aug]) for eps, aug in U.case_noise(name)]
@@ -276,8 +237,8 @@ def test_two_consecutive_updates_match_float64(name, mode):
     for k, step in enumerate(U.STEPS):
         m, coef = learner.update(buf, step, noise[k])
         assert not agent.model.training and coef > 0
-        _hold(f"{name} mode {mode} update {k}", _snap(cfg, agent, learner, buf, m), want[k], scales[k], cfg,
-              FLOORS[(group(name), k)], k)
+        hold(U, f"{name} mode {mode} update {k}", snap(U, agent, learner, buf, m.tolist(), cfg), want[k], scales[k],
+             cfg, FLOORS[(group(name), k)], k)
         assert _nbt(agent.model) == [1000 + (k + 1) * (2 * H + 1), 1000 + (k + 1) * (H + 3 - W)]
         assert not learner.last["intrinsic"][:W].any()
     assert len(learner.train_step._next_pool.free) == H and len(learner.train_step._loss_pool.free) == 2
@@ -299,7 +260,7 @@ def test_graph_replay_matches_eager_and_eager_is_reproducible():
         snaps = []
         for k, step in enumerate(U.STEPS):
             m, _ = learner.update(buf, step, eager if k and not replay else None)
-            snaps.append(_snap(cfg, agent, learner, buf, m))
+            snaps.append(snap(U, agent, learner, buf, m.tolist(), cfg))
         runs.append((snaps, learner))
     (a, la), (b, lb) = runs
     assert lb._graphs and not la._graphs, "the second update was not captured"

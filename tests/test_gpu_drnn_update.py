@@ -41,6 +41,7 @@ import pytest
 import torch
 
 import drnn_update_ref as U
+from update_gpu import gpu_learner, hold, same, snap, yardstick
 
 pytestmark = pytest.mark.gpu
 
@@ -183,9 +184,6 @@ def test_fused_loss_matches_float64_autograd(lam):
     (scal[4] * up).backward()
     torch.cuda.synchronize()
 
-    def same(tag, got, ref):
-        got, ref = got.detach().double().cpu().reshape(-1), ref.detach().double().reshape(-1)
-        torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-6 * float(ref.abs().max()), msg=lambda m: f"{tag}: {m}")
     same("td", td, want["td"])
     for i, k in enumerate(("sim", "rew", "val", "prio", "model", "tdl")):
         same(k, rows[i], want[k])
@@ -198,59 +196,22 @@ def test_fused_loss_matches_float64_autograd(lam):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4, 5
-_WANT = {}
-
-
-def _want(name):
-    """The float64 yardstick's two updates (snapshots and zero-mean scales), once per case."""
-    if name not in _WANT:
-        _WANT[name] = U.run_ref(name, torch.float64, U.case_noise(name), scales=True)
-    return _WANT[name]
-
-
-def _gpu_learner(name, graph=False, warmup=3, **cfg_over):
+def _gpu_learner(name, **kw):
     from tdmpc_amd.drnn_learner import DssmLearner
-    cfg = U.case_cfg(name)
-    for k, v in cfg_over.items():
-        setattr(cfg, k, v)
-    model, target = U.make_models(cfg, name, device="cuda")
-    agent = SimpleNamespace(cfg=cfg, model=model, model_target=target, device=torch.device("cuda"), planner=None)
-    learner = DssmLearner(agent, graph=graph, warmup=warmup)
-    assert learner.hip
-    buf = U.FakeBuffer(tuple(t.cuda() for t in U.batch(cfg, U.CASES[name][7])))
-    return cfg, agent, learner, buf
-
-
-def _snap(agent, learner, buf, m, coef):
-    torch.cuda.synchronize()
-    r = dict(metrics=np.array(m.tolist() + [coef]), prio=buf.prios[-1].cpu().numpy(),
-             intrinsic=learner.last["intrinsic"].cpu().numpy(), rms=learner.rms.cpu().numpy(),
-             grads=U.grads_of(agent.model))
-    return U.snapshot(r, agent.model, agent.model_target)
-
-
-def _hold(tag, got, want, scales, cfg, floors, k):
-    figs = U.figures(got, want, scales, cfg.lr, cfg.tau)
-    over = {}
-    for cls, (f, where) in figs.items():
-        b = U.bound(floors, cls, k)
-        print(f"{tag} {cls}: gpu {f:.3e} ({where}), bound {b:.2e}")
-        if not f <= b:
-            over[cls] = (f, where, b)
-    assert not over, (tag, over)
+    return gpu_learner(U, DssmLearner, name, **kw)
 
 
 @pytest.mark.parametrize("name", ["cheetah", "tiny", "wide"])
 def test_two_consecutive_updates_match_float64(name):
-    want, scales = _want(name)
+    want, scales = yardstick(U, name)
     cfg, agent, learner, buf = _gpu_learner(name)
     noise = [[n.cuda() for n in nz] for nz in U.case_noise(name)]
     H = cfg.horizon
     for k, step in enumerate(U.STEPS):
         m, coef = learner.update(buf, step, noise[k])
         assert not agent.model.training
-        _hold(f"{name} update {k}", _snap(agent, learner, buf, m, coef), want[k], scales[k], cfg,
-              FLOORS[(group(name), k)], k)
+        hold(U, f"{name} update {k}", snap(U, agent, learner, buf, m.tolist() + [coef]), want[k], scales[k],
+             cfg, FLOORS[(group(name), k)], k)
         assert int(agent.model._dynamics.prior_mlp[1].num_batches_tracked) == 1000 + (k + 1) * (2 * H + 1)
         assert int(agent.model._predictor[1].num_batches_tracked) == 1000 + (k + 1) * (H + 2)
     assert len(learner.train_step._next_pool.free) == H and len(learner.train_step._loss_pool.free) == 1
@@ -270,7 +231,7 @@ def test_graph_replay_matches_eager_and_eager_is_reproducible():
         snaps = []
         for k, step in enumerate(U.STEPS):
             m, coef = learner.update(buf, step, eager if k and not replay else None)
-            snaps.append(_snap(agent, learner, buf, m, coef))
+            snaps.append(snap(U, agent, learner, buf, m.tolist() + [coef]))
         runs.append((snaps, learner))
     (a, la), (b, lb) = runs
     assert lb._graphs and not la._graphs, "the second update was not captured"
@@ -280,7 +241,7 @@ def test_graph_replay_matches_eager_and_eager_is_reproducible():
     for k in ("consistency_loss", "reward_loss", "value_loss", "total_loss", "weighted_loss"):
         assert a[0]["metrics"][k] == b[0]["metrics"][k], k
     zero = {k: 1.0 for k in U.ZERO_MEAN}   # (grad0 against a float32 reference: absolute, the bound is 1e-6)
-    _hold("graph replay against eager, update 1", b[1], a[1], zero, U.case_cfg("cheetah"), FLOORS[("rest", 1)], 1)
+    hold(U, "graph replay against eager, update 1", b[1], a[1], zero, U.case_cfg("cheetah"), FLOORS[("rest", 1)], 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6
