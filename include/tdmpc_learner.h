@@ -98,7 +98,9 @@ int tdmpc_lg_gemm(const tdmpc_lg_job* jobs, int32_t njobs, int32_t tile, void* s
  * min(out_0[r], out_1[r]) (TDMPC._td_target, tdmpc.py:184-190).
  * Backward, per head: d = tail ? dq[r] * w3 : x (dA, ldx); d *= act'(yact); ln: d = layer_norm backward (xhat, rstd,
  * g) -> y (dP, ldy). part != null: per-workgroup column sums [nwg][..] of (ln: d*xhat, d) then (tail: dq*yact, dq),
- * i.e. the partial gradients of the LayerNorm affine and of the scalar output layer. pi mode (q1 != null): dq of
+ * i.e. the partial gradients of the LayerNorm affine and of the scalar output layer. Every one of the nwg workgroups
+ * writes its slice: a workgroup that owns no row (rows < nwg * waves per workgroup) writes zeros, so tdmpc_lg_finalize
+ * may sum all nwg slices whatever the row count (tests/test_gpu_lg_rows.py pins it). pi mode (q1 != null): dq of
  * head h is d(-sum_t rho^t mean_b min(q1, q2)) / dq_h (ties split in half, as torch.min's backward). */
 typedef struct tdmpc_lg_rowhead {
     const float* x; float* y; float* xhat; float* rstd; const float* yact;

@@ -61,11 +61,15 @@ def Q(p, cfg, z, a):
     return _q(p, x, "_Q1", cfg.mlp_dim), _q(p, x, "_Q2", cfg.mlp_dim)
 
 
-def pi(p, z, std):
+def pi(p, z, std, noise=None):
+    """noise: a list of standard normal draws [B, A]; the next one is consumed in place of normal_()."""
     mu = torch.tanh(_mlp(p, z, "_pi"))
     if std > 0:
         scale = torch.ones_like(mu) * std
-        eps = torch.empty(mu.shape, dtype=mu.dtype, device=mu.device).normal_()
+        if noise is not None:
+            eps = noise.pop(0).to(mu.dtype).clone()
+        else:
+            eps = torch.empty(mu.shape, dtype=mu.dtype, device=mu.device).normal_()
         eps *= scale
         eps = torch.clamp(eps, -0.3, 0.3)
         x = mu + eps
@@ -89,12 +93,17 @@ def _clip_grad_norm_19(params, max_norm):
     return total
 
 class RefLearner:
-    """model / target parameters as leaf tensors in state_dict order; Adam like the reference (tdmpc.py:62-63)."""
+    """model / target parameters as leaf tensors in state_dict order; Adam like the reference (tdmpc.py:62-63).
+    dtype: parameters, target and batch in that dtype (float64: the yardstick the GPU learner's tests measure fp32
+    against). update(noise=...): the 2H + 1 standard normal draws [B, A] of one update in draw order (H in
+    `_td_target`, one per horizon step, then H + 1 in `update_pi`), used in place of the global generator."""
 
-    def __init__(self, cfg, sd_model, sd_target):
+    def __init__(self, cfg, sd_model, sd_target, dtype=torch.float32):
         self.cfg = cfg
-        self.p = {k: v.detach().clone().float().requires_grad_(True) for k, v in sd_model.items()}
-        self.pt = {k: v.detach().clone().float() for k, v in sd_target.items()}
+        self.dtype = dtype
+        self._noise = None
+        self.p = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in sd_model.items()}
+        self.pt = {k: v.detach().clone().to(dtype) for k, v in sd_target.items()}
         self.params = list(self.p.values())
         self.pi_params = [v for k, v in self.p.items() if k.startswith("_pi.")]
         self.q_params = [v for k, v in self.p.items() if k.startswith("_Q1.") or k.startswith("_Q2.")]
@@ -105,7 +114,7 @@ class RefLearner:
     def _td_target(self, next_obs, reward):
         cfg = self.cfg
         next_z = h(self.p, cfg, next_obs)
-        return reward + cfg.discount * torch.min(*Q(self.pt, cfg, next_z, pi(self.p, next_z, cfg.min_std)))
+        return reward + cfg.discount * torch.min(*Q(self.pt, cfg, next_z, pi(self.p, next_z, cfg.min_std, self._noise)))
 
     def update_pi(self, zs):
         cfg = self.cfg
@@ -114,7 +123,7 @@ class RefLearner:
             v.requires_grad_(False)
         pi_loss = 0
         for t, z in enumerate(zs):
-            a = pi(self.p, z, cfg.min_std)
+            a = pi(self.p, z, cfg.min_std, self._noise)
             q = torch.min(*Q(self.p, cfg, z, a))
             pi_loss += -q.mean() * (cfg.rho ** t)
         pi_loss.backward()
@@ -124,10 +133,14 @@ class RefLearner:
             v.requires_grad_(True)
         return pi_loss.item()
 
-    def update(self, batch, step):
+    def update(self, batch, step, noise=None):
         """One reference `TDMPC.update` on a sampled batch -> (metrics dict, new priorities [B, 1])."""
         cfg = self.cfg
         obs, next_obses, action, reward, idxs, weights = batch
+        if self.dtype != torch.float32:
+            obs, next_obses, action, reward, weights = (x.to(self.dtype) for x in
+                                                        (obs, next_obses, action, reward, weights))
+        self._noise = None if noise is None else list(noise)
         self.optim.zero_grad(set_to_none=True)
         z = h(self.p, cfg, obs)
         zs = [z.detach()]

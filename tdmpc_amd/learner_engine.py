@@ -34,7 +34,7 @@ EPI_NONE, EPI_ELU, EPI_PI, EPI_ELU_BWD, EPI_PI_BWD, EPI_RELU_BWD = 0, 1, 2, 3, 4
 CONV_K = (7, 5, 3, 3)                       # helper.enc's pixel convolutions (stride 2, no padding)
 CONV_NAMES = ("_encoder.1", "_encoder.3", "_encoder.5", "_encoder.7")
 LIN_NAME = "_encoder.10"                    # Flatten -> Linear(32 * 3 * 3 -> L)
-NBLK = 2048         # capacity of the norm partials (one per lg_finalize workgroup of 2048 gradients)
+NBLK = 2048         # least capacity of the norm partials (one per lg_finalize workgroup; Engine.nblk)
 ROWS_NWG = 256      # lg_rows_bwd workgroups (column-sum partials per head)
 TILE_EXACT = 0x100  # TDMPC_LG_TILE_EXACT (include/tdmpc_learner.h)
 
@@ -117,7 +117,12 @@ class Engine:
         params = dict(agent.model.named_parameters())
         self.opt_main = _Adam([params[k] for k in names if not k.startswith("_pi.")], 0, self.n_main, lr, self.dev)
         self.opt_pi = _Adam([params[k] for k in names if k.startswith("_pi.")], self.n_main, total, lr, self.dev)
-        self.normp = torch.zeros(2, NBLK, device=self.dev)
+        # lg_finalize runs a workgroup per 2048 gradients of a tensor, and per 64 of one summed from 32 slices on (the
+        # row kernels' and the convs' partials: tensors of at most 16384 elements). mlp_dim 1024 has 5.6 M parameters,
+        # more than NBLK workgroups
+        sizes = [sd[k].numel() for k in names]
+        self.nblk = max(NBLK, sum(-(-n // 2048) + (-(-n // 64) if n <= 16384 else 0) for n in sizes))
+        self.normp = torch.zeros(2, self.nblk, device=self.dev)
         self.rho = torch.tensor([cfg.rho ** t for t in range(self.H + 1)], dtype=torch.float32, device=self.dev)
         self.gw = torch.full((1,), 1.0, dtype=torch.float32, device=self.dev) * (1 / self.H)   # the 1/H hook
         self._bufs = {}
@@ -676,10 +681,10 @@ class Engine:
         which = 0 if opt is self.opt_main else 1
         normp = _p(self.normp[which])
         st = self._stream()
-        _lib.check(self.lib.tdmpc_lg_finalize(arr, len(names), _p(self.G, opt.lo), normp, NBLK, _p(opt.step_t), st),
+        _lib.check(self.lib.tdmpc_lg_finalize(arr, len(names), _p(self.G, opt.lo), normp, self.nblk, _p(opt.step_t), st),
                    "tdmpc_lg_finalize")
         _lib.check(self.lib.tdmpc_lg_adam(_p(self.P, opt.lo), _p(self.G, opt.lo), _p(opt.exp_avg),
-                                          _p(opt.exp_avg_sq), opt.hi - opt.lo, normp, NBLK, _p(opt.step_t),
+                                          _p(opt.exp_avg_sq), opt.hi - opt.lo, normp, self.nblk, _p(opt.step_t),
                                           opt.lr, 0.9, 0.999, 1e-8, float(self.cfg.grad_clip_norm), norm_out, st),
                    "tdmpc_lg_adam")
 

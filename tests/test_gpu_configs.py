@@ -67,12 +67,16 @@ def test_plan_fullsize_configs(name, B):
         assert q_k.startswith("chain_kernel" if l512 else "wide_heads_kernel"), q_k
 
 
-def _plan_calls_match_oracle(name, cfg, agent, B):
+def _plan_calls_match_oracle(name, cfg, agent, B, inputs=None, ref_cache=None):
     """Cold, warm and (B > 1) mixed-t0 plan() calls of `agent` (synthetic weights of seed 21), every env against the
-    oracle on the same noise: the comparison and tolerances of the module docstring."""
+    oracle on the same noise: the comparison and tolerances of the module docstring. inputs: call index -> (obs [B, ..],
+    [NoiseBundle] * B), in place of the draws seeded here; ref_cache: a dict that keeps the oracle's plans of these
+    inputs, for callers that compare several agents on the same ones. Returns, per compared call and env, whether
+    every iteration's elite set agreed (compare_iterations)."""
     told = tdmpc_ref.RefTOLD(synthetic_state_dict(cfg, 21), cfg)
     states = [tdmpc_ref.PlanState(0.05) for _ in range(B)]
     diverged = [False] * B        # an env whose elite set swapped on a near tie is not compared while warm
+    sames = []
     rs = np.random.RandomState(5)
     torch.manual_seed(8)
     np.random.seed(8)
@@ -80,15 +84,24 @@ def _plan_calls_match_oracle(name, cfg, agent, B):
     if B > 1:
         calls.append([e % 2 == 0 for e in range(B)])   # mixed: even envs restart, odd envs warm-start
     for ci, t0s in enumerate(calls):
-        obs = _obs(cfg, rs, B)
-        noises = [tdmpc_ref.draw_noise(cfg, 10**6, False) for _ in range(B)]
+        if inputs is not None:
+            obs, noises = inputs(ci)
+        else:
+            obs = _obs(cfg, rs, B)
+            noises = [tdmpc_ref.draw_noise(cfg, 10**6, False) for _ in range(B)]
         tr = {}
         a, m = agent._plan_envs(obs, False, 10**6, t0s, trace=tr, noise=noises)
         a = a.cpu().numpy()
         for e in range(B):
-            rtr = {}
-            ra, rm = tdmpc_ref.plan(told, cfg, states[e], obs[e], noises[e], eval_mode=False, step=10**6,
-                                    t0=t0s[e], trace=rtr)
+            if ref_cache is not None and (ci, e) in ref_cache:
+                ra, rm, rtr, ref_pm = ref_cache[(ci, e)]
+            else:
+                rtr = {}
+                ra, rm = tdmpc_ref.plan(told, cfg, states[e], obs[e], noises[e], eval_mode=False, step=10**6,
+                                        t0=t0s[e], trace=rtr)
+                ref_pm = states[e].prev_mean.numpy().copy()
+                if ref_cache is not None:
+                    ref_cache[(ci, e)] = (ra, rm, rtr, ref_pm)
             if t0s[e]:
                 diverged[e] = False
             if diverged[e]:
@@ -96,6 +109,7 @@ def _plan_calls_match_oracle(name, cfg, agent, B):
             ref_vals = torch.stack(rtr["value"]).squeeze(-1).numpy()
             same = compare_iterations(tr["value"][e].cpu().numpy(), ref_vals, cfg.num_elites)
             record(same, f"{name}/B{B}/call{ci}/env{e}")
+            sames.append(same)
             if not same:
                 diverged[e] = True
                 continue
@@ -105,7 +119,8 @@ def _plan_calls_match_oracle(name, cfg, agent, B):
             np.testing.assert_allclose([m[e]["external_reward_mean"], m[e]["current_std"]],
                                        [rm["external_reward_mean"], rm["current_std"]], atol=2e-5, rtol=1e-4)
             pm = agent.planner.prev_mean_view(cfg.horizon, B)[e].cpu().numpy()
-            np.testing.assert_allclose(pm, states[e].prev_mean.numpy(), atol=2e-5, rtol=0)
+            np.testing.assert_allclose(pm, ref_pm, atol=2e-5, rtol=0)
+    return sames
 
 
 def test_latent512_folded_rollout_accuracy():

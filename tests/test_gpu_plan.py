@@ -70,10 +70,15 @@ def test_plan_matches_reference_golden(name, path):
 def test_estimate_value_fullsize(task, ov, path):
     """TDMPC.estimate_value at BASELINE sizes (T=768, H=5) vs the oracle's CPU fp32 TOLD, both kernel paths."""
     cfg = make_cfg(task, **ov)
-    agent = _agent(cfg, 7, path=path)
+    _estimate_value_matches_oracle(cfg, _agent(cfg, 7, path=path), 5)
+
+
+def _estimate_value_matches_oracle(cfg, agent, H):
+    """estimate_value of `agent` (synthetic weights of seed 7) over H steps: the final latent, the last reward and the
+    value of every row against the oracle, within ATOL + RTOL |ref|."""
     pl = agent.planner
     pl.pack(agent.model)
-    H, T, A, L = 5, pl.T, cfg.action_dim, cfg.latent_dim
+    T, A, L = pl.T, cfg.action_dim, cfg.latent_dim
     g = torch.Generator().manual_seed(3)
     z0 = torch.randn(1, L, generator=g)
     actions = torch.rand(1, H, T, A, generator=g) * 2 - 1

@@ -65,6 +65,7 @@ def _params_close(got, want, lr):
 
 @pytest.mark.gpu
 def test_gpu_update_matches_oracle():
+    from test_gpu_learner_widths import check_against_float64, gpu_snapshot
     from tdmpc_amd.tdmpc import TDMPC
     cfg = learner_cfg()
     agent = TDMPC(cfg)
@@ -79,6 +80,8 @@ def test_gpu_update_matches_oracle():
     torch.manual_seed(0)
     for k, step in enumerate((1, 2)):
         m = agent.update(buf, step, noise=noise[k])
+        if k == 0:   # the first update's gradients, per tensor, against the float64 oracle (8 x the float32 CPU floor)
+            check_against_float64("golden-cartpole", 0, gpu_snapshot(agent, buf, m), classes=("grad",))
         rm, rprio = ref.update(b, step)
         np.testing.assert_allclose([m[n] for n in METRICS], [rm[n] for n in METRICS], rtol=2e-5, atol=1e-7)
         np.testing.assert_allclose(buf.prio.cpu().numpy(), rprio.numpy(), rtol=2e-5, atol=1e-6)
@@ -91,7 +94,9 @@ def test_gpu_update_matches_oracle():
 @pytest.mark.parametrize("task", ["humanoid", "dog", "cheetah"])
 def test_gpu_update_matches_oracle_full_size(task):
     """The bench's learner shape (batch 512, horizon 5, mlp 512; humanoid L100 A21 / dog L100 A38 obs 223 / cheetah L50 A6):
-    two updates (EMA on the second) against the oracle, same batch and TruncatedNormal draws, same tolerances."""
+    two updates (EMA on the second) against the oracle, same batch and TruncatedNormal draws, same tolerances; the
+    first update's gradients per tensor against the float64 oracle (tests/test_gpu_learner_widths.py)."""
+    from test_gpu_learner_widths import check_against_float64, gpu_snapshot
     from tdmpc_amd.config import make_cfg
     from tdmpc_amd.tdmpc import TDMPC
     cfg = make_cfg(task, num_samples=64, num_elites=32, iterations=3, horizon=5, batch_size=512)
@@ -108,6 +113,8 @@ def test_gpu_update_matches_oracle_full_size(task):
     torch.manual_seed(1)
     for k, step in enumerate((1, 2)):
         m = agent.update(buf, step, noise=noise[k])
+        if k == 0:
+            check_against_float64(f"full-{task}", 0, gpu_snapshot(agent, buf, m), classes=("grad",))
         rm, rprio = ref.update(b, step)
         np.testing.assert_allclose([m[n] for n in METRICS], [rm[n] for n in METRICS], rtol=2e-5, atol=1e-7)
         np.testing.assert_allclose(buf.prio.cpu().numpy(), rprio.numpy(), rtol=2e-5, atol=1e-6)
