@@ -4,6 +4,7 @@ The drop-in names:
 
     from tdmpc_amd import TDMPC            # src/algorithm/tdmpc.py:53 (agent: plan / update / save / load)
     from tdmpc_amd import TOLD             # src/algorithm/tdmpc.py:9 (same module tree and state_dict keys)
+    from tdmpc_amd import TdMpcSim         # src/algorithm/tdmpc_similarity.py:75 (TDMPCSIM: TDMPC's plan, the similarity update)
     from tdmpc_amd import ReplayBuffer     # src/algorithm/helper.py:434 (device prioritized replay)
     from tdmpc_amd import TdICEM           # src/algorithm/tdmpc_icem_similarity_mlp.py:116 (iCEM planner)
     from tdmpc_amd import TdIcemMlp        # src/algorithm/tdmpc_icem_similarity_mlp.py:77 (the same agent with its update)
@@ -27,6 +28,8 @@ _EXPORTS = {
     "TdIcemMlp": "icem_mlp",
     "IcemMlpModel": "icem_mlp",
     "IcemMlpLearner": "icem_learner",
+    "TdMpcSim": "tdmpc_sim",
+    "SimLearner": "sim_learner",
     "TdMpcDrnn": "drnn",
     "TdIcemDrnn": "drnn_icem",
     "DSSM": "dssm",

@@ -43,11 +43,15 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             # include/tdmpc_icem_learner.h
             "tdmpc_icem_learner_version", "tdmpc_icem_intrinsic_workspace_floats", "tdmpc_icem_intrinsic_fwd",
             "tdmpc_icem_simloss_sizes_for", "tdmpc_icem_simloss_fwd", "tdmpc_icem_simloss_bwd",
-            "tdmpc_icem_loss_forward", "tdmpc_icem_loss_backward")
+            "tdmpc_icem_loss_forward", "tdmpc_icem_loss_backward",
+            # include/tdmpc_sim_learner.h
+            "tdmpc_sim_learner_version", "tdmpc_sim_loss_forward", "tdmpc_sim_loss_backward",
+            "tdmpc_sim_bn_part_floats", "tdmpc_sim_bn_fwd", "tdmpc_sim_bn_bwd", "tdmpc_sim_cos_fwd", "tdmpc_sim_cos_bwd")
 DRNN_VERSION = 2
 DRNN_TRAIN_VERSION = 1
 ICEM_LEARNER_VERSION = 1
 ICEM_DYN_TENSORS = 6   # include/tdmpc_icem_learner.h
+SIM_LEARNER_VERSION = 1
 DT_NEXT_TENSORS, DT_LOSS_TENSORS, DT_MAX_ROWS = 22, 8, 4096   # include/tdmpc_drnn_learner.h
 NOISE_MAX_JOBS, NOISE_MAX_SPECTRA = 17, 4
 
@@ -189,6 +193,12 @@ class IcemLossArgs(C.Structure):   # tdmpc_icem_loss_args (include/tdmpc_icem_le
                [(n, C.c_float) for n in ("sim_coef", "reward_coef", "value_coef", "discount")] + [("rho", C.c_double)]
 
 
+class SimLossArgs(C.Structure):   # tdmpc_sim_loss_args (include/tdmpc_sim_learner.h)
+    _fields_ = [(n, C.c_void_p) for n in ("sim", "q1", "q2", "rp", "rw", "td", "w")] + \
+               [("H", C.c_int32), ("B", C.c_int32)] + \
+               [(n, C.c_float) for n in ("sim_coef", "reward_coef", "value_coef")] + [("rho", C.c_double)]
+
+
 class Sizes(C.Structure):
     _fields_ = [("packed_weight_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t),
                 ("noise_floats_per_env", C.c_size_t)]
@@ -294,6 +304,13 @@ def lib():
     L.tdmpc_icem_simloss_bwd.argtypes = [pd, pv, i32, vp, vp, i32, vp, sz, vp, vp, pv, vp, sz, vp]
     L.tdmpc_icem_loss_forward.argtypes = [C.POINTER(IcemLossArgs), vp, vp, vp, vp]
     L.tdmpc_icem_loss_backward.argtypes = [C.POINTER(IcemLossArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tdmpc_sim_loss_forward.argtypes = [C.POINTER(SimLossArgs), vp, vp, vp]
+    L.tdmpc_sim_loss_backward.argtypes = [C.POINTER(SimLossArgs), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tdmpc_sim_bn_part_floats.argtypes = [i32, C.POINTER(sz)]
+    L.tdmpc_sim_bn_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.tdmpc_sim_bn_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.tdmpc_sim_cos_fwd.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.tdmpc_sim_cos_bwd.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     for name in EXPORTED:
         if not hasattr(L, name) and not (name.startswith("tdmpc_debug_") and os.environ.get("TDMPC_LIB_PATH")):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")

@@ -30,7 +30,8 @@
 //     steps W..H-1 (the similarity term over all H), forward and backward; instantiated a second time, with rho ** t and
 //     the 1 / horizon hook, for the MLP iCEM agent's update.
 // predictor_fwd is `_predictor` and the cosine loss behind every similarity loss and intrinsic-reward pass.
-// The MLP iCEM agent's update (TdICemSimMlp.update) is icem_learner.inc, included at the end.
+// The MLP iCEM agent's update (TdICemSimMlp.update) is icem_learner.inc, included at the end; after it
+// sim_learner.inc, the similarity TD-MPC agent's (TDMPCSIM.update).
 // Every reduction runs in a fixed order: wave butterflies, LDS sums over waves in wave order, partials in index order.
 #include <hip/hip_runtime.h>
 
@@ -44,6 +45,7 @@
 #include "../../include/tdmpc_drnn_learner.h"
 #include "../../include/tdmpc_icem_learner.h"
 #include "../../include/tdmpc_learner.h"
+#include "../../include/tdmpc_sim_learner.h"
 
 namespace tdmpc_internal {
 void set_error(const char* msg);
@@ -666,8 +668,9 @@ __global__ void __launch_bounds__(64 * CWAVES) dt_gru_chain(const ChainArgs a) {
 }
 
 // ---- The loss composition with one-step TD targets, every term under the priority weights: TdMpcSimDssm.update's
-// (tdmpc_drnn_sim_loss_*: the reward / value / priority sums over the N = H - W shoot steps) and TdICemSimMlp.update's
-// (tdmpc_icem_loss_*: N = H, those sums weighted by rho ** t, and the 1 / horizon gradient hook in the backward). RHO and
+// (tdmpc_drnn_sim_loss_*: the reward / value / priority sums over the N = H - W shoot steps), TdICemSimMlp.update's
+// (tdmpc_icem_loss_*: N = H, those sums weighted by rho ** t, and the 1 / horizon gradient hook in the backward) and
+// TDMPCSIM.update's (tdmpc_sim_loss_*: the MLP iCEM agent's over TD targets that the caller computed). RHO and
 // HOOK choose the expressions at compile time: each caller keeps its own contraction into FMAs.
 struct StepLossArgs {
     const float *sim, *q1, *q2, *rp, *rw, *rwpi, *nq, *w;
@@ -679,7 +682,8 @@ struct StepLossArgs {
 // (float)(rho ** t): the power in double, rounded once (a float32 tensor times a Python float).
 __device__ __forceinline__ float rho_pow(double rho, int t) { return t == 0 ? 1.f : (float)pow(rho, (double)t); }
 
-template <bool RHO>
+// TDIN: td is given (tdmpc_sim_loss_*: the learner engine's row kernel wrote it) and not written; rwpi / nq are not read.
+template <bool RHO, bool TDIN = false>
 __global__ void __launch_bounds__(256) sl_loss_rows(const StepLossArgs a, float* td, float* rows) {
     const int b = blockIdx.x * 256 + threadIdx.x, H = a.H, N = a.N, B = a.B;
     if (b >= B) return;
@@ -687,9 +691,9 @@ __global__ void __launch_bounds__(256) sl_loss_rows(const StepLossArgs a, float*
     for (int t = 0; t < H; ++t) sim += a.sim[(size_t)t * B + b];
     for (int t = 0; t < N; ++t) {
         const size_t i = (size_t)t * B + b;
-        const float tg = a.rwpi[i] + a.discount * a.nq[i];
+        const float tg = TDIN ? td[i] : a.rwpi[i] + a.discount * a.nq[i];
         const float dr = a.rp[i] - a.rw[i], d1 = a.q1[i] - tg, d2 = a.q2[i] - tg;
-        td[i] = tg;
+        if (!TDIN) td[i] = tg;
         if (RHO) {
             const float r = rho_pow(a.rho, t);
             rew += (dr * dr) * r;
@@ -1060,11 +1064,12 @@ StepLossArgs sim_step_args(const tdmpc_drnn_sim_loss_args* a) {
                         a->sim_coef, a->reward_coef, a->value_coef, a->discount, 1.0};
 }
 
-// The one-step loss family's launches over checked args (tdmpc_drnn_sim_loss_* and tdmpc_icem_loss_*).
-template <bool RHO>
+// The one-step loss family's launches over checked args (tdmpc_drnn_sim_loss_*, tdmpc_icem_loss_* and, with TDIN,
+// tdmpc_sim_loss_*).
+template <bool RHO, bool TDIN = false>
 int step_loss_forward(const StepLossArgs& a, float* td, float* rows, float* scal, void* stream) {
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sl_loss_rows<RHO>, dim3((a.B + 255) / 256), dim3(256), 0, st, a, td, rows);
+    hipLaunchKernelGGL((sl_loss_rows<RHO, TDIN>), dim3((a.B + 255) / 256), dim3(256), 0, st, a, td, rows);
     if (int rc = launched("step loss_rows")) return rc;
     hipLaunchKernelGGL(sl_loss_means, dim3(1), dim3(512), 0, st, rows, a.w, a.B, scal);
     return launched("step loss_means");
@@ -1538,3 +1543,4 @@ int tdmpc_drnn_simloss_bwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t
 }  // extern "C"
 
 #include "icem_learner.inc"
+#include "sim_learner.inc"

@@ -72,6 +72,18 @@ class _Adam:
 
 
 class Engine:
+    # hooks of the engines built on this one (tdmpc_amd/sim_engine.py): the flat layout's module order, the tensors it
+    # holds, the policy optimiser's learning rate, and in `update` the encoder's passes, the loss and further weight
+    # gradients
+    ORDER = ("_encoder", "_dynamics", "_reward", "_Q1", "_Q2", "_pi")
+
+    def _tensors(self, model):
+        """{name: tensor} of what the flat buffers hold (TOLD: its whole state_dict)."""
+        return model.state_dict()
+
+    def _pi_lr(self):
+        return float(self.cfg.lr)
+
     def __init__(self, agent):
         self.agent = agent
         cfg = self.cfg = agent.cfg
@@ -89,10 +101,9 @@ class Engine:
         self.LA = self.L + self.A
         # X0 / Xtd rows padded to a multiple of 4 floats: their products take 16-byte loads
         self.LAP = (self.LA + 3) & ~3
-        order = ["_encoder", "_dynamics", "_reward", "_Q1", "_Q2", "_pi"]
         self.off = {}
-        sd = agent.model.state_dict()
-        names = [k for pre in order for k in sd if k.startswith(pre + ".")]
+        sd = self._tensors(agent.model)
+        names = [k for pre in self.ORDER for k in sd if k.startswith(pre + ".")]
         assert len(names) == len(sd), "unexpected TOLD parameters"
         # every tensor starts on a 16-byte boundary (the scalar heads' 1-float biases would leave the next weights
         # misaligned and their products on 4-byte loads); the gaps hold zeros in P, PT, G and the Adam moments
@@ -116,7 +127,8 @@ class Engine:
         lr = float(cfg.lr)
         params = dict(agent.model.named_parameters())
         self.opt_main = _Adam([params[k] for k in names if not k.startswith("_pi.")], 0, self.n_main, lr, self.dev)
-        self.opt_pi = _Adam([params[k] for k in names if k.startswith("_pi.")], self.n_main, total, lr, self.dev)
+        self.opt_pi = _Adam([params[k] for k in names if k.startswith("_pi.")], self.n_main, total, self._pi_lr(),
+                            self.dev)
         # lg_finalize runs a workgroup per 2048 gradients of a tensor, and per 64 of one summed from 32 slices on (the
         # row kernels' and the convs' partials: tensors of at most 16384 elements). mlp_dim 1024 has 5.6 M parameters,
         # more than NBLK workgroups
@@ -289,13 +301,14 @@ class Engine:
 
     def rows(self, heads, n, bwd=False, **kw):
         a = _lib.LgRows()
+        m = kw.get("m", self.M)   # the rows' width (the heads': mlp_dim)
         for i, h in enumerate(heads):
             H = a.hd[i]
             for f in ("x", "y", "xhat", "rstd", "yact", "g", "beta", "w3", "b3", "out", "dq", "part"):
                 setattr(H, f, h.get(f))
-            H.ldx, H.ldy = h.get("ldx", self.M), h.get("ldy", self.M)
+            H.ldx, H.ldy = h.get("ldx", m), h.get("ldy", m)
             H.ln, H.act, H.tail = int(h.get("ln", 0)), h["act"], int(h.get("tail", 0))
-        a.nh, a.rows, a.m, a.bsz = len(heads), n, self.M, kw.get("bsz", 1)
+        a.nh, a.rows, a.m, a.bsz = len(heads), n, m, kw.get("bsz", 1)
         a.reward, a.td, a.gamma = kw.get("reward"), kw.get("td"), kw.get("gamma", 0.0)
         a.q1, a.q2, a.rho = kw.get("q1"), kw.get("q2"), kw.get("rho")
         if bwd:
@@ -387,7 +400,12 @@ class Engine:
         """tdmpc.py:184-190 for all H steps: online encoder + pi (TruncatedNormal draws `eps`), target Q, and the
         target encoder's next_z (tdmpc.py:206-207) -> b["TD"], b["NZ"]. A generator: yields after each launch
         (see _pair)."""
-        O, E, L, A, M, LA, LAP = self.O, self.E, self.L, self.A, self.M, self.LA, self.LAP
+        yield from self._enc_td_steps(b, nxo_t, R)
+        yield from self._td_head_steps(b, rew, R, eps)
+
+    def _enc_td_steps(self, b, nxo_t, R):
+        """The target and the online encoder on the H next observations -> b["NZ"], b["Xtd"][:, :L]."""
+        O, E, L, LAP = self.O, self.E, self.L, self.LAP
         w, wt = self.w, (lambda k: self.w(k, True))
         nxo = _p(nxo_t)
         if self.pix:   # the conv stacks of both encoders, then their Linear
@@ -410,6 +428,11 @@ class Engine:
                        dict(segs=[_seg(_p(b["Yo1"]), E, w("_encoder.2.weight"), E, E)], m=R, n=L, c=_p(b["Xtd"]),
                             ldc=LAP, bias=w("_encoder.2.bias"))])
             yield
+
+    def _td_head_steps(self, b, rew, R, eps):
+        """The online policy and the target Q heads on b["Xtd"] -> b["TD"] (tdmpc.py:184-190)."""
+        L, A, M, LA, LAP = self.L, self.A, self.M, self.LA, self.LAP
+        w, wt = self.w, (lambda k: self.w(k, True))
         self.prod([([(b["Xtd"][:, :L], 0, L)], "_pi.0.weight", b["T1"], "_pi.0.bias", False, False, EPI_ELU, None)])
         yield
         self.prod([([(b["T1"], 0, M)], "_pi.2.weight", b["T2"], "_pi.2.bias", False, False, EPI_ELU, None)])
@@ -435,8 +458,17 @@ class Engine:
     def _fwd_steps(self, b, obs, action, B):
         """The update's forward (tdmpc.py:199-213): encoder, latent rollout, heads over the H B rollout rows. A
         generator: yields after each launch (see _pair)."""
-        H, O, E, L, M, LA, LAP = self.H, self.O, self.E, self.L, self.M, self.LA, self.LAP
+        H, L, M, LA, LAP = self.H, self.L, self.M, self.LA, self.LAP
         R = H * B
+        w, X0 = self.w, b["X0"]
+        yield from self._enc_fwd_steps(b, obs, B)
+        X0.view(H + 1, B, LAP)[:H, :, L:LA].copy_(action[:H])
+        yield
+        yield from self._head_fwd_steps(b, B)
+
+    def _enc_fwd_steps(self, b, obs, B):
+        """The online encoder on obs -> z_0 in b["X0"][:B, :L], its activations saved for the backward."""
+        O, E, L, LAP = self.O, self.E, self.L, self.LAP
         w, X0 = self.w, b["X0"]
         if self.pix:
             F = self.flat
@@ -452,8 +484,12 @@ class Engine:
             self.gemm([dict(segs=[_seg(_p(b["Ye1"]), E, w("_encoder.2.weight"), E, E)], m=B, n=L, c=_p(X0), ldc=LAP,
                             bias=w("_encoder.2.bias"))])
             yield
-        X0.view(H + 1, B, LAP)[:H, :, L:LA].copy_(action[:H])
-        yield
+
+    def _head_fwd_steps(self, b, B):
+        """The latent rollout from z_0 and the Q / reward heads over its H B rows."""
+        H, L, M, LA, LAP = self.H, self.L, self.M, self.LA, self.LAP
+        R = H * B
+        w, X0 = self.w, b["X0"]
         for t in range(H):
             self.gemm([dict(segs=[_seg(_p(X0, t * B * LAP), LAP, w("_dynamics.0.weight"), LA, LA)], m=B, n=M,
                             c=_p(b["Yd1"], t * B * M), ldc=M, bias=w("_dynamics.0.bias"), epi=EPI_ELU)])
@@ -517,8 +553,8 @@ class Engine:
 
     def update(self, buffer, noise=None):
         """One TDMPC.update without the EMA -> metrics [7] (learner.METRICS order)."""
-        cfg, dev = self.cfg, self.dev
-        H, O, E, L, A, M, LA = self.H, self.O, self.E, self.L, self.A, self.M, self.LA
+        dev = self.dev
+        H, L, A, M, LA = self.H, self.L, self.A, self.M, self.LA
         obs, next_obses, action, reward, idxs, weights = buffer.sample()
         B = obs.shape[0]
         R, R1 = H * B, (H + 1) * B
@@ -552,16 +588,9 @@ class Engine:
         PA, PB, Y1, Y2, XH1, XH2, RS1, RS2 = (b[k] for k in ("PA", "PB", "Y1", "Y2", "XH1", "XH2", "RS1", "RS2"))
 
         main.wait_stream(self.side)   # TD / NZ ready
-        # ---- losses (fused HIP loss, include/tdmpc_learner.h) ----
-        la = _lib.LossArgs(_p(b["ZP"]), _p(b["NZ"]), _p(Q[0]), _p(Q[1]), _p(Q[2]), rew, _p(b["TD"]), _p(weights),
-                           _p(self.rho), H, B, L, float(cfg.consistency_coef), float(cfg.reward_coef),
-                           float(cfg.value_coef))
-        st = self._stream()
-        _lib.check(self.lib.tdmpc_loss_forward(C.byref(la), _p(b["lrows"]), _p(b["scal"]), st), "loss_forward")
+        # ---- losses and their backward (-> dq, dZP[B L:]) ----
+        self._loss(b, rew, weights, B)
         dq = b["dq"]
-        _lib.check(self.lib.tdmpc_loss_backward(C.byref(la), _p(b["lrows"]), _p(b["scal"]), _p(self.gw),
-                                                _p(b["dZP"], B * L), _p(dq[0]), _p(dq[1]), _p(dq[2]), st),
-                   "loss_backward")
 
         # ---- backward through the heads ----
         dP2, dA, dP1 = b["dP2"], b["dA"], b["dP1"]
@@ -604,18 +633,7 @@ class Engine:
 
         self._pair(self._rollout_bwd_steps(b, B), side_steps())
         DG, dP2d, dP1d, DZ0 = b["DG"], b["dP2d"], b["dP1d"], b["DZ0"]
-        conv = {}
-        if self.pix:   # Linear backward with the last conv's ReLU mask, then the conv stack's backward
-            F = self.flat
-            self.gemm([dict(segs=[_seg(_p(DZ0), L, w(LIN_NAME + ".weight"), F, L, bmode=1)], m=B, n=F,
-                            c=_p(b["dy"][3]), ldc=F, epi=EPI_RELU_BWD, aux=_p(b["ym"][3]), ldaux=F)])
-            conv = self.conv_backward(b, obs, B)
-            dw_enc = [(LIN_NAME, L, F, [_seg(_p(DZ0), L, _p(b["ym"][3]), F, B, 1, 1, F)], 1)]
-        else:
-            self.gemm([dict(segs=[_seg(_p(DZ0), L, w("_encoder.2.weight"), E, L, bmode=1)], m=B, n=E,
-                            c=_p(b["dP1e"]), ldc=E, epi=EPI_ELU_BWD, aux=_p(b["Ye1"]), ldaux=E)])
-            dw_enc = [("_encoder.2", L, E, [_seg(_p(DZ0), L, _p(b["Ye1"]), E, B, 1, 1, E)], 1),
-                      ("_encoder.0", E, O, [_seg(_p(b["dP1e"]), E, _p(obs), O, B, 1, 1, O)], 1)]
+        dw_enc, conv = self._enc_bwd(b, obs, B)
 
         # ---- the rollout's weight gradients (one grouped launch) ----
         g_dyn3 = ([_seg(_p(DG), L, _p(b["Yd2"]), M, R - B, 1, 1, M)] if H > 1 else []) + \
@@ -623,7 +641,8 @@ class Engine:
         dw = dw_enc + [
               ("_dynamics.4", L, M, g_dyn3, sp),
               ("_dynamics.2", M, M, [_seg(_p(dP2d), M, _p(b["Yd1"]), M, R, 1, 1, M)], sp),
-              ("_dynamics.0", M, LA, [_seg(_p(dP1d), M, _p(X0), self.LAP, R, 1, 1, LA)], sp)]
+              ("_dynamics.0", M, LA, [_seg(_p(dP1d), M, _p(X0), self.LAP, R, 1, 1, LA)], sp)] + \
+            self._main_dw_extra(b, B, sp)
         slots.update(self._dw(b, "main", dw))
         main.wait_stream(self.side)   # the heads' slices ready
         dw += dw_h
@@ -646,6 +665,7 @@ class Engine:
             src[name + ".bias"] = (ptr + 4 * K, 32, 1, K + 1, nsl, 32 * (K + 1))
         src["_reward.4.weight"] = (_p(partr), 1, M, M, ROWS_NWG, PWr)
         src["_reward.4.bias"] = (_p(partr, M), 1, 1, 1, ROWS_NWG, PWr)
+        src.update(self._src_extra(b))
         self._optimise(self.opt_main, src, 0, _p(b["gnorm"]))
         buffer.update_priorities(idxs, b["lrows"][3].view(B, 1))
 
@@ -653,6 +673,47 @@ class Engine:
         pi_loss = self._update_pi(b, X0[:, :L], H + 1, B, _p(eps, R * A), pi_fwd_done=True)
         scal = b["scal"]
         return torch.cat([scal[0:3], pi_loss, scal[3:5], b["gnorm"]])
+
+    def _loss(self, b, rew, weights, B):
+        """The fused loss (include/tdmpc_learner.h) over the forward's buffers -> b["lrows"], b["scal"], and its
+        backward -> b["dq"] and the consistency gradient in b["dZP"][B L:]."""
+        cfg, H, L, Q = self.cfg, self.H, self.L, b["Q"]
+        la = _lib.LossArgs(_p(b["ZP"]), _p(b["NZ"]), _p(Q[0]), _p(Q[1]), _p(Q[2]), rew, _p(b["TD"]), _p(weights),
+                           _p(self.rho), H, B, L, float(cfg.consistency_coef), float(cfg.reward_coef),
+                           float(cfg.value_coef))
+        st = self._stream()
+        _lib.check(self.lib.tdmpc_loss_forward(C.byref(la), _p(b["lrows"]), _p(b["scal"]), st), "loss_forward")
+        dq = b["dq"]
+        _lib.check(self.lib.tdmpc_loss_backward(C.byref(la), _p(b["lrows"]), _p(b["scal"]), _p(self.gw),
+                                                _p(b["dZP"], B * L), _p(dq[0]), _p(dq[1]), _p(dq[2]), st),
+                   "loss_backward")
+
+    def _enc_bwd(self, b, obs, B):
+        """The encoder's backward from b["DZ0"] (the gradient of z_0) -> (its weight-gradient jobs for the `main`
+        grouped launch, the conv stack's weight-gradient slices)."""
+        O, E, L = self.O, self.E, self.L
+        w, DZ0 = self.w, b["DZ0"]
+        conv = {}
+        if self.pix:   # Linear backward with the last conv's ReLU mask, then the conv stack's backward
+            F = self.flat
+            self.gemm([dict(segs=[_seg(_p(DZ0), L, w(LIN_NAME + ".weight"), F, L, bmode=1)], m=B, n=F,
+                            c=_p(b["dy"][3]), ldc=F, epi=EPI_RELU_BWD, aux=_p(b["ym"][3]), ldaux=F)])
+            conv = self.conv_backward(b, obs, B)
+            dw_enc = [(LIN_NAME, L, F, [_seg(_p(DZ0), L, _p(b["ym"][3]), F, B, 1, 1, F)], 1)]
+        else:
+            self.gemm([dict(segs=[_seg(_p(DZ0), L, w("_encoder.2.weight"), E, L, bmode=1)], m=B, n=E,
+                            c=_p(b["dP1e"]), ldc=E, epi=EPI_ELU_BWD, aux=_p(b["Ye1"]), ldaux=E)])
+            dw_enc = [("_encoder.2", L, E, [_seg(_p(DZ0), L, _p(b["Ye1"]), E, B, 1, 1, E)], 1),
+                      ("_encoder.0", E, O, [_seg(_p(b["dP1e"]), E, _p(obs), O, B, 1, 1, O)], 1)]
+        return dw_enc, conv
+
+    def _main_dw_extra(self, b, B, sp):
+        """Further weight-gradient jobs (name, out, in, segments, splits) of the `main` grouped launch."""
+        return []
+
+    def _src_extra(self, b):
+        """Further tdmpc_lg_finalize sources {tensor: (ptr, rows, cols, ld, slices, slice stride)}."""
+        return {}
 
     def _dw(self, b, tag, dw):
         """One grouped launch of every weight gradient of a pass -> {name: slot pointer}."""
