@@ -294,7 +294,8 @@ int tdmpc_cem_iter(const tdmpc_dims* dims, const tdmpc_plan_params* params, cons
  *     2 = latency 32x64, 3 = throughput LDS tile, 0 = any) and prologue `pro` (0 plain, 1 LayerNorm, -1 any),
  *     restricted to K == N == kdim when kdim > 0 (the hidden kdim x kdim layers);
  *   cfg 4 / 5 / 6: chain_kernel launches of the TOLD.next step / pi / Q heads;
- * in both cases restricted to launches over exactly `rows` rows when rows > 0 (e.g. batch * num_samples:
+ *   cfg 8: the persistent one-env plan's launch (plan1_kernel; no FLOP count);
+ * in the first two cases restricted to launches over exactly `rows` rows when rows > 0 (e.g. batch * num_samples:
  * the CEM rollout). tdmpc_profile_end waits for the events and returns the launch count, the summed kernel
  * time in ms and the summed algorithmic FLOPs (2*M*N*K per GEMM problem; for a chain launch 2 * rows * the
  * head's MACs per row at the real, unpadded widths). Eager use only (events are not graph-capturable). */

@@ -3852,7 +3852,15 @@ int step_next(const Ctx& c, int t, int rows, RowMap map, float disc, int first, 
         if ((rc = flush_split(c))) return rc;
     {
         const bool z0c = t == 0 && c.z0c_ready && map.G % 32 == 0;
-        if (!nowide && use_wide(c, rows, map, z0c)) {
+        bool wide = !nowide && use_wide(c, rows, map, z0c);
+        // A folded rollout (Ctx::fold_ok) runs every step of a row on the same kernel: its launch over all T rows is
+        // split by role below at t = 0 too where the whole launch's z0c form does not fit the wide kernel (T % 128 != 0
+        // with T % 32 == 0; each part carries its own z0c). Without this, t = 0 took the chain kernel and left z' where
+        // the folded first layers of t = 1 read h2.
+        if (!nowide && !wide && z0c && c.fold_ok && c.P > 0 && c.N + c.P == c.T && map.G == c.T && map.S == c.T &&
+            map.O == 0 && rows % c.T == 0)
+            wide = use_wide(c, rows, map, false) && use_wide(c, rows / c.T * c.N, RowMap{c.N, c.T, 0}, true);
+        if (wide) {
             if ((rc = flush_split(c))) return rc;
             // Iteration 0's fused launch over all T = N + P rows of every env is 1.5 rounds of workgroups at B = 32
             // (384 blocks on 256 CUs): the sampled rows of every env run on the wide kernel (one whole round) and the
@@ -4447,11 +4455,17 @@ int plan1_launch(const Ctx& c, const tdmpc_plan_params* prm, const float* noise,
                        P1_NG * 64 + 64);
     HIPCHK(hipGetLastError());
     const size_t lds = p1_lds_bytes(c.H, a.K, w.A, c.T);
+    // diagnostic timer (tdmpc_profile_begin cfg 8: the persistent plan, one launch per call)
+    Profiler& pf = g_prof;
+    const bool prof = prof_armed() && pf.cfg == 8;
+    if (prof) snprintf(pf.kernel, sizeof pf.kernel, "plan1_kernel<%d>", p1_ks(w));
+    HIPCHK(prof_begin(prof, c.s));
 #define PLAN1_LAUNCH(KS) \
     if (p1_ks(w) == KS) hipLaunchKernelGGL(plan1_kernel<KS>, dim3(P1_NG * P1_WPG), dim3(P1_NT), lds, c.s, a);
     PLAN1_FOR_EACH(PLAN1_LAUNCH)
 #undef PLAN1_LAUNCH
     HIPCHK(hipGetLastError());
+    HIPCHK(prof_end(prof, c.s, 0.0));
     return 0;
 }
 

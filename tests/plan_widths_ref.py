@@ -64,10 +64,9 @@ def calls_of(B):
     return calls
 
 
-def min_gap_ratio(shape, seed, pattern):
+def gap_ratio(cfg, told, seed, pattern):
     """The oracle's trace of one env over the calls of `pattern` (its t0 flags): the smallest ratio, over every
     iteration of every call, of (K-th best value - next best) to 2 (1e-5 + 1e-4 max |v|). Above 1: no near tie."""
-    cfg, told = shape_cfg(shape), told_of(shape)
     state, worst = tdmpc_ref.PlanState(0.05), np.inf
     for (obs, nb), t0 in zip(env_inputs(cfg, seed), pattern):
         tr = {}
@@ -79,11 +78,16 @@ def min_gap_ratio(shape, seed, pattern):
     return worst
 
 
-def find_seeds(shape, n, start=0):
-    """The first n seeds from `start` on that pass both patterns (how SEEDS was filled)."""
+def min_gap_ratio(shape, seed, pattern):
+    return gap_ratio(shape_cfg(shape), told_of(shape), seed, pattern)
+
+
+def find_seeds(shape, n, start=0, ratio=min_gap_ratio):
+    """The first n seeds from `start` on that pass both patterns (how SEEDS was filled); ratio: the shape family's
+    min_gap_ratio (tests/plan_shapes_ref.py passes its own)."""
     out, s = [], start
     while len(out) < n:
-        if all(min_gap_ratio(shape, s, p) > 1.5 for p in PATTERNS):   # (a margin over the test's 1.0)
+        if all(ratio(shape, s, p) > 1.5 for p in PATTERNS):   # (a margin over the test's 1.0)
             out.append(s)
         s += 1
     return out

@@ -56,6 +56,35 @@ def test_bad_dims_rejected():
     assert _lib.lib().tdmpc_sizes_for(None, C.byref(s)) == -3
 
 
+def _sizes_rc(latent_dim, action_dim):
+    """tdmpc_sizes_for at mlp_dim 512 and tests/plan_shapes_ref.py's plan size (128 samples, 16 elites, horizon 3)."""
+    import plan_shapes_ref
+    cfg = make_cfg("humanoid", latent_dim=latent_dim, **plan_shapes_ref.SIZE)
+    cfg.action_dim = action_dim
+    d = _lib.dims_from_cfg(cfg, max_batch=3)
+    assert (d.mlp_dim, d.latent_dim, d.action_dim) == (512, latent_dim, action_dim)
+    return _lib.lib().tdmpc_sizes_for(C.byref(d), C.byref(_lib.Sizes()))
+
+
+def test_sizes_for_width_limits():
+    """check_dims' limits on the planner's widths, one past and one inside each: the first layer's K
+    Kx = rup(A, 8) + rup(L, 8) <= 1024, latent_dim <= 1024 (with the action columns in Kx: 1016 at most), action_dim
+    <= 256. One past is TDMPC_E_DIMS (-1)."""
+    E_DIMS = -1
+    assert _sizes_rc(1001, 21) == E_DIMS      # Kx = 24 + 1008 = 1032
+    assert _sizes_rc(1000, 21) == 0           # Kx = 1024: shape l of tests/test_gpu_plan_shapes.py
+    assert _sizes_rc(1025, 1) == E_DIMS       # latent_dim itself
+    assert _sizes_rc(1017, 1) == E_DIMS       # Kx = 8 + 1024
+    assert _sizes_rc(1016, 8) == 0            # the widest latent: Kx = 8 + 1016
+    assert _sizes_rc(8, 257) == E_DIMS        # action_dim itself (Kx = 272)
+    assert _sizes_rc(8, 256) == 0
+    import plan_shapes_ref
+    for shape, (task, A, L, E) in plan_shapes_ref.SHAPES.items():
+        d = _lib.dims_from_cfg(plan_shapes_ref.shape_cfg(shape), max_batch=32)
+        assert (d.action_dim, d.latent_dim, d.enc_dim) == (A, L, E)
+        assert _lib.lib().tdmpc_sizes_for(C.byref(d), C.byref(_lib.Sizes())) == 0, shape
+
+
 @pytest.mark.parametrize("sched", ["linear(2, 5, 25000, 0)", "linear(0.5, 0.05, 25000, 0)", "0.3", 1.5])
 def test_linear_schedule(sched):
     for step in [0, 1, 100, 12500, 24999, 25000, 10**6]:

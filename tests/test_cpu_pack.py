@@ -5,15 +5,23 @@ import ctypes as C
 
 import pytest
 
+import plan_shapes_ref
 from tdmpc_amd import _lib
 from tdmpc_amd.config import make_cfg
 from tdmpc_amd.told import TOLD
 
 
 @pytest.mark.parametrize("task,kw", [("humanoid", {}), ("dog", {}), ("cheetah", {}), ("quadruped", {}),
-                                     ("humanoid", {"latent_dim": 512}), ("cheetah", {"modality": "pixels"})])
+                                     ("humanoid", {"latent_dim": 512}), ("cheetah", {"modality": "pixels"})] +
+                         # tests/test_gpu_plan_shapes.py's twelve shapes (action_dim: set on the cfg after make_cfg)
+                         [(t, {"action_dim": A, "latent_dim": L, "enc_dim": E})
+                          for t, A, L, E in plan_shapes_ref.SHAPES.values()])
 def test_pack_jobs_in_bounds(task, kw):
+    kw = dict(kw)
+    action_dim = kw.pop("action_dim", None)
     cfg = make_cfg(task, **kw)
+    if action_dim is not None:
+        cfg.action_dim = action_dim
     sd = TOLD(cfg).state_dict()
     L = _lib.lib()
     dims = _lib.dims_from_cfg(cfg, max_batch=1)
