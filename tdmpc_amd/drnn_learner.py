@@ -21,9 +21,12 @@ The HIP path (the model on the GPU) orders one update for the device:
   * the H-step rollout through `DssmTrainStep.next`, Q1 / Q2 on (z_t, a_t) for all t in one pass, `similarity_loss`
     over the H B concatenated rows, the loss composition with its TD-lambda recursion as `_DssmFusedLoss`;
   * backward, `clip_grad_norm_19`, the optimiser step, the priority write-back, and `update_pi` over the H + 1 latents in
-    one pass.
+    one pass: `learner.GraphLearner`'s `_optimize`, `_finish` and `_update_pi`, which every learner's update ends with.
+The first three items are `_hip_prelude`, which `icem_learner.IcemMlpLearner` runs as it stands; `DssmSimLearner`, whose
+warm-up steps come between the encoders and the intrinsic rewards, takes its two parts `_encode_next` and
+`_min_target_q`.
 Nothing synchronises with the host. After `warmup` eager updates one update per (buffer.idx, buffer._full) is captured
-into a HIP graph and replayed by `learner.GraphLearner`, the driver shared with the TOLD learner; the explore coefficient
+into a HIP graph and replayed by `learner.GraphLearner`, the base shared with the TOLD learner; the explore coefficient
 changes every step, so it lives in a device scalar that `update` writes before each replay. The encoder, Q and pi MLPs
 run on PyTorch-ROCm autograd here (float32 matmul precision pinned); moving them onto tdmpc_lg_gemm / tdmpc_lg_rows_* is the follow-up.
 
@@ -43,8 +46,8 @@ steps only, the similarity sum over all H, and every term under the priority wei
 reference admits 1 <= warmup_len <= horizon - 1 (it raises on an empty `torch.cat` at either end) and this class
 refuses the rest, and similarity_horizon != 1, by name.
 
-Optimisers: the reference builds them with rlpyt's `create_optimizer(model, optim_id, lr)`, a package that is not
-available to check its defaults against. Here `cfg.optim_id` 'adam' gives `torch.optim.Adam` and 'adamw'
+Optimisers (`learner.make_optimizer`, called by `GraphLearner`): the reference builds them with rlpyt's
+`create_optimizer(model, optim_id, lr)`, a package that is not available to check its defaults against. Here `cfg.optim_id` 'adam' gives `torch.optim.Adam` and 'adamw'
 `torch.optim.AdamW`, with lr = cfg.lr (model) / cfg.pi_lr (policy), weight_decay = getattr(cfg, 'weight_decay', 0.0)
 (cfgs/default.yaml: 0.0, at which AdamW and Adam take the same step) and torch's other defaults; `capturable=graph`.
 """
@@ -60,34 +63,27 @@ from . import _lib
 from .config import linear_schedule
 from .dssm import check_dssm_cfg
 from .dssm_train import DssmTrainStep, _DssmFusedLoss, _DssmSimFusedLoss, new_rms_state
-from .learner import GraphLearner, clip_grad_norm_19
+from .learner import GraphLearner, check_batch_size, check_optim_id
 
 METRICS = ("consistency_loss", "reward_loss", "value_loss", "pi_loss", "total_loss", "weighted_loss", "grad_norm",
            "intrinsic_batch_reward_mean")
 
 
 def check_update_cfg(cfg, who):
-    """Raise for what no similarity learner covers (`who`: the class the message names)."""
+    """Raise for what no similarity learner with intrinsic rewards covers (`who`: the class the message names)."""
     B, H = int(cfg.batch_size), int(cfg.horizon)
-    if B < 2:
-        raise ValueError(f"{who}: batch_size={B} is not supported (train-mode BatchNorm needs two rows)")
+    check_batch_size(cfg, who)
     if (H + 1) * B > _lib.DT_MAX_ROWS:
         raise ValueError(f"{who}: (horizon + 1) * batch_size = {(H + 1) * B} rows exceed {_lib.DT_MAX_ROWS} "
                          f"(horizon={H}, batch_size={B}): the intrinsic-reward pass and its normalisation take at most "
                          f"that many rows")
-    if str(getattr(cfg, "optim_id", "adamw")).lower() not in ("adam", "adamw"):
-        raise ValueError(f"{who}: optim_id={cfg.optim_id!r} is not supported ('adam' or 'adamw')")
+    check_optim_id(cfg, who)
 
 
 def check_learner_cfg(cfg):
     """Raise for what the DSSM learner does not cover, each setting named, before anything touches the device."""
     check_dssm_cfg(cfg)
     check_update_cfg(cfg, "DssmLearner")
-
-
-def make_optimizer(params, cfg, lr, capturable=False):
-    cls = torch.optim.AdamW if str(getattr(cfg, "optim_id", "adamw")).lower() == "adamw" else torch.optim.Adam
-    return cls(params, lr=lr, weight_decay=float(getattr(cfg, "weight_decay", 0.0)), capturable=capturable)
 
 
 class RewardRms:
@@ -139,6 +135,7 @@ class DssmLearner(GraphLearner):
     """Owns the optimisers, the RunningMeanStd state and (in graph mode) the captured update graphs of one DSSM iCEM
     agent (`agent`: cfg, model, model_target, device and, when it plans, planner)."""
 
+    METRICS = METRICS
     MAX_LOSSES = 1   # live similarity_loss calls of one update
     HIP_ENV = "TDMPC_DSSM_LEARNER_HIP"   # "0": the PyTorch path on the GPU
     check_cfg = staticmethod(check_learner_cfg)
@@ -146,46 +143,22 @@ class DssmLearner(GraphLearner):
     def __init__(self, agent, graph: bool = True, warmup: int = 3):
         cfg = agent.cfg
         self.check_cfg(cfg)
-        model = agent.model
-        p0 = next(model.parameters())
-        self.device, self.dtype = p0.device, p0.dtype
-        on_gpu = self.device.type == "cuda"
-        self.hip = on_gpu and os.environ.get(self.HIP_ENV, "1") != "0"
-        super().__init__(agent, bool(graph) and on_gpu, warmup)
-        agent.optim = make_optimizer(self.params, cfg, cfg.lr, capturable=self.graph)
-        agent.pi_optim = make_optimizer(self.pi_params, cfg, cfg.pi_lr, capturable=self.graph)
+        super().__init__(agent, graph, warmup)
+        self.hip = self.on_gpu and os.environ.get(self.HIP_ENV, "1") != "0"
         self.rms = new_rms_state(self.device)
         self.reward_rms = RewardRms(self.rms)
         self.coef = torch.zeros(1, dtype=torch.float32 if self.hip else self.dtype, device=self.device)
         self.train_step = None
         if self.hip:
-            self.train_step = self._make_train_step(model, int(cfg.batch_size), int(cfg.horizon))
-        self.last = {}   # the last eager step's intermediate results (tests): intrinsic, priorities
+            self.train_step = self._make_train_step(agent.model, int(cfg.batch_size), int(cfg.horizon))
 
     def _make_train_step(self, model, B, H):
         return DssmTrainStep(model, max_rows=B, max_steps=H, max_loss_rows=H * B, max_losses=self.MAX_LOSSES)
 
-    # ------------------------------------------------------------------ the policy update (:367-384)
     def update_pi(self, zs, eps=None):
-        """-> pi_loss (tensor). zs: the H + 1 detached latents; eps: optional H + 1 [B, A] TruncatedNormal draws."""
-        a, cfg, m = self.agent, self.cfg, self.agent.model
-        a.pi_optim.zero_grad(set_to_none=True)
-        m.track_q_grad(False)
-        if self.hip:   # one pass over the (H + 1) B rows; no rho, as the reference's live line
-            n = len(zs)
-            Z = torch.cat(list(zs))
-            act = m.pi(Z, cfg.min_std, eps=None if eps is None else torch.cat(list(eps[:n])))
-            pi_loss = (-torch.min(*m.Q(Z, act)).view(n, -1).mean(dim=1)).sum()
-        else:
-            pi_loss = 0
-            for t, z in enumerate(zs):
-                act = m.pi(z, cfg.min_std, eps=None if eps is None else eps[t])
-                pi_loss += -torch.min(*m.Q(z, act)).mean()
-        pi_loss.backward()
-        clip_grad_norm_19(self.pi_params, cfg.grad_clip_norm)
-        a.pi_optim.step()
-        m.track_q_grad(True)
-        return pi_loss.detach()
+        """:367-384 -> pi_loss (tensor). zs: the detached latents; eps: optional [B, A] TruncatedNormal draws, one per
+        latent. No rho, as the reference's live line; the HIP path takes the latents in one pass."""
+        return self._update_pi(zs, eps, batched=self.hip)
 
     # ------------------------------------------------------------------ one update
     def step(self, buffer, noise=None):
@@ -194,31 +167,53 @@ class DssmLearner(GraphLearner):
         The explore coefficient is read from `self.coef` (`update` writes it)."""
         return self._step_hip(buffer, noise) if self.hip else self._step_torch(buffer, noise)
 
-    def _finish(self, buffer, idxs, prio, zs, noise, H, means, weighted, grad_norm, intrinsic):
-        buffer.update_priorities(idxs, prio)
-        pi_loss = self.update_pi(zs, eps=None if noise is None else noise[H:])
-        self.last = dict(intrinsic=intrinsic, prio=prio)
-        return torch.stack([means[0], means[1], means[2], pi_loss.to(weighted.dtype), means[3], weighted.detach(),
-                            grad_norm, intrinsic.mean()]).detach()
+    @torch.no_grad()
+    def _encode_next(self, next_obses):
+        """The online and the target encoder on the H + 1 next observations, once each -> two [(H + 1) B, L]."""
+        flat = next_obses.reshape(next_obses.shape[0] * next_obses.shape[1], -1)
+        return self.agent.model.h(flat), self.agent.model_target.h(flat)
+
+    @torch.no_grad()
+    def _min_target_q(self, nz_on, lo, hi, B, eps):
+        """The min target Q at the online next latents of steps [lo, hi) under the online policy, every step at once
+        -> [hi - lo, B]. eps: the steps' explicit draws or None."""
+        m, n = self.agent.model, hi - lo
+        x = nz_on[lo * B:hi * B]
+        act = m.pi(x, self.cfg.min_std, eps=None if eps is None else torch.cat(list(eps[:n])))
+        return torch.min(*self.agent.model_target.Q(x, act)).view(n, B)
+
+    def _intrinsic_kw(self):
+        return {}
+
+    def _hip_prelude(self, buffer, noise):
+        """What the HIP paths of the two iCEM learners do before their rollouts -> (the batch, z = h(obs) with grad, the
+        target encodings [(H + 1) B, L], intrinsic [(H + 1) B], reward_pi [(H + 1) B], next_q [H, B])."""
+        a, H = self.agent, int(self.cfg.horizon)
+        batch = buffer.sample()
+        obs, next_obses, action, reward = batch[:4]
+        B = obs.shape[0]
+        a.optim.zero_grad(set_to_none=True)
+        z = a.model.h(obs)
+        nz_on, nz_tg = self._encode_next(next_obses)
+        with torch.no_grad():
+            # rollout t starts at z_traj[t] = (z, online next latents)[t] and is compared with target[t]
+            z_traj = torch.cat([z.detach(), nz_on[:H * B]])
+            intrinsic, reward_pi = self.train_step.intrinsic_rewards(
+                z_traj, action.reshape((H + 1) * B, -1), nz_tg, H + 1, self.rms, self.coef, reward.reshape(-1),
+                **self._intrinsic_kw())
+        return batch, z, nz_tg, intrinsic, reward_pi, self._min_target_q(nz_on, 0, H, B, noise)
+
+    def _finish_hip(self, buffer, idxs, scal, rows, zs, noise, n, grad_norm, intrinsic):
+        """`_finish` on a fused loss's outputs: scal = (the four means, weighted, ...), rows[3] the priorities."""
+        B = rows.shape[1]
+        return self._finish(buffer, idxs, rows[3].view(B, 1), [t.detach() for t in zs], noise, n,
+                            (scal[0], scal[1], scal[2], scal[3]), scal[4], grad_norm, intrinsic.view(-1, B, 1))
 
     def _step_hip(self, buffer, noise):
-        a, cfg, m, mt, ts = self.agent, self.cfg, self.agent.model, self.agent.model_target, self.train_step
+        cfg, m, ts = self.cfg, self.agent.model, self.train_step
         H = int(cfg.horizon)
-        obs, next_obses, action, reward, idxs, weights = buffer.sample()
-        B, L = obs.shape[0], int(cfg.latent_dim)
-        a.optim.zero_grad(set_to_none=True)
-        z = m.h(obs)
-        with torch.no_grad():
-            flat = next_obses.reshape((H + 1) * B, -1)
-            nz_on, nz_tg = m.h(flat), mt.h(flat)                    # [(H + 1) B, L]: online, target
-            # :421-443: rollout t starts at z_traj[t] = (z, online next latents)[t] and is compared with target[t]
-            z_traj = torch.cat([z.detach(), nz_on[:H * B]])
-            intrinsic, reward_pi = ts.intrinsic_rewards(z_traj, action.reshape((H + 1) * B, -1), nz_tg, H + 1,
-                                                        self.rms, self.coef, reward.reshape(-1))
-            # :475-478: min target Q at the online next latents under the online policy, every step at once
-            x = nz_on[:H * B]
-            act = m.pi(x, cfg.min_std, eps=None if noise is None else torch.cat(list(noise[:H])))
-            next_q = torch.min(*mt.Q(x, act)).view(H, B)
+        (obs, _, action, reward, idxs, weights), z, nz_tg, intrinsic, reward_pi, next_q = self._hip_prelude(buffer, noise)
+        B = obs.shape[0]
         hidden = m.init_hidden_state(B, z.device)
         zt, zs, rps = z, [z], []
         for t in range(H):
@@ -233,13 +228,8 @@ class DssmLearner(GraphLearner):
             reward_pi.view(H + 1, B)[:H], next_q, weights,
             (float(cfg.similarity_coef), float(cfg.reward_coef), float(cfg.value_coef), float(cfg.discount),
              float(cfg.td_lambda)))
-        weighted = scal[4]
-        weighted.register_hook(lambda grad: grad * (1 / H))
-        weighted.backward()
-        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
-        a.optim.step()
-        return self._finish(buffer, idxs, rows[3].view(B, 1), [t.detach() for t in zs], noise, H,
-                            (scal[0], scal[1], scal[2], scal[3]), weighted, grad_norm, intrinsic.view(H + 1, B, 1))
+        grad_norm = self._optimize(scal[4])
+        return self._finish_hip(buffer, idxs, scal, rows, zs, noise, H, grad_norm, intrinsic)
 
     def _rollout_one(self, z, a):
         """One `next` from a fresh hidden state -> the predicted latent."""
@@ -262,11 +252,11 @@ class DssmLearner(GraphLearner):
         return loss.reshape(n, self.cfg.batch_size, -1).sum(dim=0)
 
     def _step_torch(self, buffer, noise):
-        a, cfg, m, mt = self.agent, self.cfg, self.agent.model, self.agent.model_target
+        cfg, m, mt = self.cfg, self.agent.model, self.agent.model_target
         H = int(cfg.horizon)
         obs, next_obses, action, reward, idxs, weights = buffer.sample()
         B = obs.shape[0]
-        a.optim.zero_grad(set_to_none=True)
+        self.agent.optim.zero_grad(set_to_none=True)
         z = m.h(obs)
         next_zs = mt.h(next_obses)
         online_next_zs = m.h(next_obses)
@@ -305,10 +295,7 @@ class DssmLearner(GraphLearner):
         td_loss = cfg.value_coef * value_loss.clamp(max=1e4)
         total_loss = model_loss + td_loss
         weighted = (model_loss * weights).mean() + td_loss.mean()   # the reference's [B, B] broadcast, literally
-        weighted.register_hook(lambda grad: grad * (1 / H))
-        weighted.backward()
-        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
-        a.optim.step()
+        grad_norm = self._optimize(weighted)
         return self._finish(buffer, idxs, priority_loss.clamp(max=1e4).detach(), zs, noise, H,
                             (similarity_loss.mean(), reward_loss.mean(), value_loss.mean(), total_loss.mean()),
                             weighted, grad_norm, intrinsic)
@@ -317,9 +304,7 @@ class DssmLearner(GraphLearner):
         """`TdICemSimDssm.update` semantics -> (metrics tensor [8] on the device, explore_coef); no synchronisation."""
         coef = linear_schedule(self.cfg.explore_schedule, step)
         self.coef.fill_(coef)
-        # (on the CPU nothing follows the matmul precision the driver pins)
-        run = super().update if self.device.type == "cuda" else self._update
-        return run(buffer, step, noise), coef
+        return super().update(buffer, step, noise), coef
 
 
 def check_sim_learner_cfg(cfg):
@@ -352,19 +337,17 @@ class DssmSimLearner(DssmLearner):
         return None, list((torch.randn(H, B, L, dtype=self.dtype, device=self.device) * self.AUG_SCALE).unbind(0))
 
     def _step_hip(self, buffer, noise):
-        a, cfg, m, mt, ts = self.agent, self.cfg, self.agent.model, self.agent.model_target, self.train_step
+        cfg, m, ts = self.cfg, self.agent.model, self.train_step
         H, W = int(cfg.horizon), int(cfg.warmup_len)
         N = H - W
         obs, next_obses, action, reward, idxs, weights = buffer.sample()
         B = obs.shape[0]
         eps, aug = self._draws(noise, B)
-        a.optim.zero_grad(set_to_none=True)
+        self.agent.optim.zero_grad(set_to_none=True)
         # the latents the gradient reaches: obs and next_obses[:W] (zs_traj[0 .. W]); the later online encodings feed
         # only no_grad consumers
         zg = m.h(torch.cat([obs.unsqueeze(0), next_obses[:W]]).reshape((W + 1) * B, -1)).view(W + 1, B, -1)
-        with torch.no_grad():
-            flat = next_obses.reshape((H + 1) * B, -1)
-            nz_on, nz_tg = m.h(flat), mt.h(flat)                    # [(H + 1) B, L]: online, target
+        nz_on, nz_tg = self._encode_next(next_obses)               # [(H + 1) B, L]: online, target
         # :428-434: the closed-loop warm-up and its similarity loss
         hidden = m.init_hidden_state(B, obs.device)
         queries = []
@@ -377,10 +360,7 @@ class DssmSimLearner(DssmLearner):
             z_traj = torch.cat([zg[0].detach(), nz_on[:H * B]])
             intrinsic, reward_pi = ts.intrinsic_chain_rewards(z_traj, action.reshape((H + 1) * B, -1), nz_tg, H + 1, W,
                                                               self.rms, self.coef, reward.reshape(-1))
-            # :339-344: min target Q at the online next latents under the online policy, the shoot steps at once
-            x = nz_on[W * B:H * B]
-            act = m.pi(x, cfg.min_std, eps=None if eps is None else torch.cat(list(eps[:N])))
-            next_q = torch.min(*mt.Q(x, act)).view(N, B)
+        next_q = self._min_target_q(nz_on, W, H, B, eps)            # :339-344, the shoot steps at once
         # :443-455: the open-loop shoot
         zt, zin, zout, rps = zg[W], [], [], []
         for t in range(W, H):
@@ -396,13 +376,8 @@ class DssmSimLearner(DssmLearner):
             torch.cat([sim_w, sim_s]).view(H, B), Q1, Q2, torch.stack(rps).view(N, B), reward[W:H].reshape(N, B),
             reward_pi.view(H + 1, B)[W:H], next_q, weights,
             (float(cfg.similarity_coef), float(cfg.reward_coef), float(cfg.value_coef), float(cfg.discount)))
-        weighted = scal[4]
-        weighted.register_hook(lambda grad: grad * (1 / H))
-        weighted.backward()
-        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
-        a.optim.step()
-        return self._finish(buffer, idxs, rows[3].view(B, 1), [zg[W].detach()] + [t.detach() for t in zout], eps, N,
-                            (scal[0], scal[1], scal[2], scal[3]), weighted, grad_norm, intrinsic.view(H + 1, B, 1))
+        grad_norm = self._optimize(scal[4])
+        return self._finish_hip(buffer, idxs, scal, rows, [zg[W]] + zout, eps, N, grad_norm, intrinsic)
 
     def _intrinsic_torch(self, obs, next_obses, action):
         """:373-402 call by call at similarity_horizon 1, the RunningMeanStd by `rms_update`."""
@@ -424,13 +399,13 @@ class DssmSimLearner(DssmLearner):
             return rms_normalize(self.rms, raw)
 
     def _step_torch(self, buffer, noise):
-        a, cfg, m, mt = self.agent, self.cfg, self.agent.model, self.agent.model_target
+        cfg, m, mt = self.cfg, self.agent.model, self.agent.model_target
         H, W = int(cfg.horizon), int(cfg.warmup_len)
         N = H - W
         obs, next_obses, action, reward, idxs, weights = buffer.sample()
         B = obs.shape[0]
         eps, aug = self._draws(noise, B)
-        a.optim.zero_grad(set_to_none=True)
+        self.agent.optim.zero_grad(set_to_none=True)
         z = m.h(obs)
         online_next_zs = m.h(next_obses)
         target_next_zs = mt.h(next_obses)
@@ -466,10 +441,7 @@ class DssmSimLearner(DssmLearner):
         total_loss = cfg.similarity_coef * similarity_loss.clamp(max=1e4) + \
             cfg.reward_coef * reward_loss.clamp(max=1e4) + cfg.value_coef * value_loss.clamp(max=1e4)
         weighted = (total_loss * weights).mean()                    # the reference's [B, B] broadcast, literally
-        weighted.register_hook(lambda grad: grad * (1 / H))
-        weighted.backward()
-        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
-        a.optim.step()
+        grad_norm = self._optimize(weighted)
         return self._finish(buffer, idxs, priority_loss.clamp(max=1e4).detach(), zs, eps, N,
                             (similarity_loss.mean(), reward_loss.mean(), value_loss.mean(), total_loss.mean()),
                             weighted, grad_norm, intrinsic)

@@ -9,10 +9,11 @@ priority terms weighted by `rho ** t`, the similarity term and `update_pi` not; 
 .mean()`, a mean over the [B, B] broadcast (= mean(total) * mean(weights)); the gradient of the weighted loss divided by
 the horizon; intrinsic rewards normalised by a running mean / std.
 
-`IcemMlpLearner(DssmLearner)` shares the optimisers, `update_pi`, the EMA, the RunningMeanStd state, the graph driver and
-the PyTorch path's intrinsic-reward and similarity code with the DSSM learners (tdmpc_amd/drnn_learner.py) and has their
-two paths; `IcemTrainStep(LossStep)` and `_IcemFusedLoss(_StepFusedLoss)` are its variants of their HIP wrappers
-(tdmpc_amd/dssm_train.py).
+`IcemMlpLearner(DssmLearner)` shares the optimisers, `update_pi`, the EMA, the RunningMeanStd state, the graph driver, the
+update's tail (`learner.GraphLearner`), the HIP path's prelude up to the rollout (`DssmLearner._hip_prelude`: the first
+three items below) and the PyTorch path's intrinsic-reward and similarity code with the DSSM learners
+(tdmpc_amd/drnn_learner.py) and has their two paths; `IcemTrainStep(LossStep)` and `_IcemFusedLoss(_StepFusedLoss)` are
+its variants of their HIP wrappers (tdmpc_amd/dssm_train.py).
 
 The HIP path (the model on the GPU) orders one update for the device:
   * the online encoder on `obs` with grad; the online and target encoders on `next_obses` once, without grad (the
@@ -45,7 +46,7 @@ from . import _lib
 from ._lib import IcemLossArgs, IcemSimlossSizes, call, dims_from_cfg, ptr
 from .drnn_learner import DssmLearner, check_update_cfg
 from .dssm_train import LossStep, _StepFusedLoss, _table, intrinsic_finish
-from .learner import clip_grad_norm_19
+from .learner import check_state_ln
 
 DYN_PARAMS = tuple(f"_dynamics.{k}" for k in ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias"))
 SEGMENTED = True   # `step`'s intrinsic pass: one segmented call (the faster form) or S one-segment calls
@@ -53,13 +54,7 @@ SEGMENTED = True   # `step`'s intrinsic pass: one segmented call (the faster for
 
 def check_icem_learner_cfg(cfg):
     """Raise for what the MLP iCEM learner does not cover, each setting named, before anything touches the device."""
-    if getattr(cfg, "modality", "state") != "state":
-        raise NotImplementedError(f"IcemMlpLearner: modality={cfg.modality!r} is not supported (state observations only)")
-    if not getattr(cfg, "normalize", True):
-        raise NotImplementedError("IcemMlpLearner: normalize=False is not supported (the BatchNorm-free predictor and "
-                                  "the plain encoder)")
-    if getattr(cfg, "norm_type", "ln") != "ln":
-        raise NotImplementedError(f"IcemMlpLearner: norm_type={cfg.norm_type!r} is not supported ('ln' only)")
+    check_state_ln(cfg, "IcemMlpLearner")
     L, M = int(cfg.latent_dim), int(cfg.mlp_dim)
     if M != 512:
         raise ValueError(f"IcemMlpLearner: mlp_dim={M} is not supported (512 only)")
@@ -132,24 +127,15 @@ class IcemMlpLearner(DssmLearner):
     def _make_train_step(self, model, B, H):
         return IcemTrainStep(model, max_loss_rows=H * B, max_losses=self.MAX_LOSSES)
 
+    def _intrinsic_kw(self):
+        return dict(segmented=SEGMENTED)
+
     def _step_hip(self, buffer, noise):
-        a, cfg, m, mt, ts = self.agent, self.cfg, self.agent.model, self.agent.model_target, self.train_step
+        cfg, m, ts = self.cfg, self.agent.model, self.train_step
         H = int(cfg.horizon)
-        obs, next_obses, action, reward, idxs, weights = buffer.sample()
+        # (:323-335 the intrinsic rewards, :286-292 the min target Q)
+        (obs, _, action, reward, idxs, weights), z, nz_tg, intrinsic, reward_pi, next_q = self._hip_prelude(buffer, noise)
         B = obs.shape[0]
-        a.optim.zero_grad(set_to_none=True)
-        z = m.h(obs)
-        with torch.no_grad():
-            flat = next_obses.reshape((H + 1) * B, -1)
-            nz_on, nz_tg = m.h(flat), mt.h(flat)                    # [(H + 1) B, L]: online, target
-            # :323-335: rollout t starts at z_traj[t] = (z, online next latents)[t] and is compared with target[t]
-            z_traj = torch.cat([z.detach(), nz_on[:H * B]])
-            intrinsic, reward_pi = ts.intrinsic_rewards(z_traj, action.reshape((H + 1) * B, -1), nz_tg, H + 1,
-                                                        self.rms, self.coef, reward.reshape(-1), segmented=SEGMENTED)
-            # :286-292: min target Q at the online next latents under the online policy, every step at once
-            x = nz_on[:H * B]
-            act = m.pi(x, cfg.min_std, eps=None if noise is None else torch.cat(list(noise[:H])))
-            next_q = torch.min(*mt.Q(x, act)).view(H, B)
         zs = [z]
         for t in range(H):
             zs.append(m._dynamics(torch.cat([zs[-1], action[t]], dim=-1)))
@@ -160,22 +146,17 @@ class IcemMlpLearner(DssmLearner):
             sim.view(H, B), Q1, Q2, rp, reward[:H].reshape(H, B), reward_pi.view(H + 1, B)[:H], next_q, weights,
             (float(cfg.similarity_coef), float(cfg.reward_coef), float(cfg.value_coef), float(cfg.discount),
              float(cfg.rho)))
-        weighted = scal[4]
-        weighted.backward()                                          # (the 1 / H hook is in the kernel)
-        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
-        a.optim.step()
-        return self._finish(buffer, idxs, rows[3].view(B, 1), [t.detach() for t in zs], noise, H,
-                            (scal[0], scal[1], scal[2], scal[3]), weighted, grad_norm, intrinsic.view(H + 1, B, 1))
+        grad_norm = self._optimize(scal[4], hook=False)              # (the 1 / H hook is in the kernel)
+        return self._finish_hip(buffer, idxs, scal, rows, zs, noise, H, grad_norm, intrinsic)
 
     def _rollout_one(self, z, a):
         return self.agent.model.next(z, a)[0]
 
     def _step_torch(self, buffer, noise):
-        a, cfg, m, mt = self.agent, self.cfg, self.agent.model, self.agent.model_target
+        cfg, m, mt = self.cfg, self.agent.model, self.agent.model_target
         H = int(cfg.horizon)
         obs, next_obses, action, reward, idxs, weights = buffer.sample()
-        B = obs.shape[0]
-        a.optim.zero_grad(set_to_none=True)
+        self.agent.optim.zero_grad(set_to_none=True)
         z = m.h(obs)
         next_zs = mt.h(next_obses)
         online_next_zs = m.h(next_obses)
@@ -202,10 +183,7 @@ class IcemMlpLearner(DssmLearner):
         total_loss = cfg.similarity_coef * similarity_loss.clamp(max=1e4) + \
             cfg.reward_coef * reward_loss.clamp(max=1e4) + cfg.value_coef * value_loss.clamp(max=1e4)
         weighted = (total_loss * weights).mean()                    # the reference's [B, B] broadcast, literally
-        weighted.register_hook(lambda grad: grad * (1 / H))
-        weighted.backward()
-        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
-        a.optim.step()
+        grad_norm = self._optimize(weighted)
         return self._finish(buffer, idxs, priority_loss.clamp(max=1e4).detach(), zs, noise, H,
                             (similarity_loss.mean(), reward_loss.mean(), value_loss.mean(), total_loss.mean()),
                             weighted, grad_norm, intrinsic)

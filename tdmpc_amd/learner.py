@@ -22,8 +22,16 @@ grad-norm clipping, Adam (capturable, foreach), the priority write-back, the pol
 into ONE HIP graph per (buffer fill, EMA) shape and replayed: no Python in the loop, no host sync, the RNG
 (philox, graph-safe) advancing exactly as the eager calls would. The EMA of the target is one foreach lerp.
 
-The warm-up / capture / replay sequence is `GraphLearner`, the base of `Learner` and of the DSSM and MLP iCEM learners
-(tdmpc_amd/drnn_learner.py, icem_learner.py).
+What the five learners share is here, once. `GraphLearner` is the base of all of them (`Learner`; drnn_learner's
+`DssmLearner` and `DssmSimLearner`; icem_learner's `IcemMlpLearner`; sim_learner's `SimLearner`): device, dtype and the
+two optimisers; the warm-up / capture / replay driver with its CPU escape; `_optimize` (the 1 / horizon hook, backward,
+`clip_grad_norm_19`, the optimiser step), `_finish` (priorities, `update_pi`, `last`, the metrics in METRICS order) and
+`_update_pi` (the batched or the looped body, with or without rho). `EngineLearner(GraphLearner)` is the base of `Learner`
+and `SimLearner` and owns everything done with an engine: choosing it or the optimisers, `td_target`, the engine branch
+of `step` with the planner's live repack, `ema`, and dropping a pack the planner made before the engine moved the
+parameters into its flat buffer (a `plan()` ahead of the first `update()`, the reference's train.py order: without the
+drop the planner stays on the old storages for good). The cfg-check clauses the learners' `check_*_cfg`
+functions compose are here as well. The rollout loops stay per learner: each is pinned to its own reference file.
 """
 from __future__ import annotations
 
@@ -38,7 +46,6 @@ from . import learner_engine
 METRICS = ("consistency_loss", "reward_loss", "value_loss", "pi_loss", "total_loss", "weighted_loss", "grad_norm")
 
 
-
 def clip_grad_norm_19(params, max_norm):
     """clip_grad_norm_(params, max_norm, error_if_nonfinite=False) as the reference's pinned torch 1.9 runs it
     (/root/reference/environment.yaml:6; tdmpc.py:178, 228): `if clip_coef < 1: grad.mul_(clip_coef)`, so a NaN norm
@@ -50,6 +57,7 @@ def clip_grad_norm_19(params, max_norm):
     coef = torch.where(coef < 1, coef, torch.ones_like(coef))
     torch._foreach_mul_(grads, coef)
     return total
+
 
 class RandomShiftsAug(torch.nn.Module):
     """helper.py:250-283: random-shift augmentation of pixel observations (identity for state). The shifts are
@@ -140,27 +148,121 @@ def _l1(pred, target):
     return F.l1_loss(pred, target, reduction="none")
 
 
+# ---------------------------------------------------------------------- the cfg-check clauses, each written once
+def check_state_ln(cfg, who, why=""):
+    """The similarity models this package trains: state observations, the normalised encoder, LayerNorm."""
+    if getattr(cfg, "modality", "state") != "state":
+        raise NotImplementedError(f"{who}: modality={cfg.modality!r} is not supported (state observations only{why})")
+    if not getattr(cfg, "normalize", True):
+        raise NotImplementedError(f"{who}: normalize=False is not supported (the BatchNorm-free predictor and the "
+                                  f"plain encoder)")
+    if getattr(cfg, "norm_type", "ln") != "ln":
+        raise NotImplementedError(f"{who}: norm_type={cfg.norm_type!r} is not supported ('ln' only)")
+
+
+def check_batch_size(cfg, who):
+    if int(cfg.batch_size) < 2:
+        raise ValueError(f"{who}: batch_size={int(cfg.batch_size)} is not supported (train-mode BatchNorm needs two "
+                         f"rows)")
+
+
+def check_optim_id(cfg, who):
+    if str(getattr(cfg, "optim_id", "adamw")).lower() not in ("adam", "adamw"):
+        raise ValueError(f"{who}: optim_id={cfg.optim_id!r} is not supported ('adam' or 'adamw')")
+
+
+def make_optimizer(params, cfg, lr, capturable=False):
+    cls = torch.optim.AdamW if str(getattr(cfg, "optim_id", "adamw")).lower() == "adamw" else torch.optim.Adam
+    return cls(params, lr=lr, weight_decay=float(getattr(cfg, "weight_decay", 0.0)), capturable=capturable)
+
+
 class GraphLearner:
-    """The update driver of every learner here (`Learner`; `drnn_learner.DssmLearner` and its subclasses): `update` runs
-    `self.step(buffer, noise)` under full float32 matmul precision -- eagerly for the first `warmup` calls (the last of
-    them on a side stream) and whenever the buffer is not graph-safe or explicit noise is given, otherwise as one HIP
-    graph per (buffer.idx, buffer._full), captured once and replayed --, then the EMA every `update_freq` steps and
-    `model.eval()`. A subclass provides `step` and may override `_before_capture`, `_after_update` and `ema`."""
+    """The base of every learner here: the optimisers, the update driver and the tail every update ends with.
+
+    `update` runs `self.step(buffer, noise)` under full float32 matmul precision -- eagerly for the first `warmup` calls
+    (the last of them on a side stream) and whenever the buffer is not graph-safe or explicit noise is given, otherwise
+    as one HIP graph per (buffer.idx, buffer._full), captured once and replayed --, then the EMA every `update_freq`
+    steps and `model.eval()`. On the CPU nothing follows the matmul precision, and nothing is captured.
+
+    A subclass provides `step` and `update_pi`, builds them from `_optimize`, `_finish` and `_update_pi`, and may
+    override `_optimizers`, `_before_capture`, `_after_update` and `ema`. METRICS names what `step` returns."""
+
+    METRICS = METRICS
 
     def __init__(self, agent, graph: bool, warmup: int):
         self.agent = agent
         self.cfg = agent.cfg
-        self.graph = graph
+        p0 = next(agent.model.parameters())
+        self.device, self.dtype = p0.device, p0.dtype
+        self.on_gpu = self.device.type == "cuda"
+        self.graph = bool(graph) and self.on_gpu
         self.warmup = warmup
         self.params = list(agent.model.parameters())
         self.pi_params = list(agent.model._pi.parameters())
         self.target_params = list(agent.model_target.parameters())
         self.calls = 0
         self._graphs = {}
+        self.last = {}   # the last eager step's intermediate results (tests): priorities, intrinsic rewards
+        agent.optim, agent.pi_optim = self._optimizers()
 
+    def _optimizers(self):
+        """-> (the model's optimiser at cfg.lr, the policy's at cfg.pi_lr), as the reference's `create_optimizer`."""
+        cfg = self.cfg
+        return (make_optimizer(self.params, cfg, cfg.lr, capturable=self.graph),
+                make_optimizer(self.pi_params, cfg, cfg.pi_lr, capturable=self.graph))
+
+    # ------------------------------------------------------------------ what every update ends with
+    def _optimize(self, loss, hook=True, pi=False):
+        """Backward, `clip_grad_norm_19` and the optimiser step on `loss` -> grad_norm: the model's parameters and
+        optimiser, or with pi the policy's. hook: the reference's division of the weighted loss's gradient by the horizon
+        (False where the loss's own backward kernel carries it, and for the policy loss)."""
+        if hook:
+            H = self.cfg.horizon
+            loss.register_hook(lambda grad: grad * (1 / H))
+        loss.backward()
+        grad_norm = clip_grad_norm_19(self.pi_params if pi else self.params, self.cfg.grad_clip_norm)
+        (self.agent.pi_optim if pi else self.agent.optim).step()
+        return grad_norm
+
+    def _finish(self, buffer, idxs, prio, zs, noise, n, means, weighted, grad_norm, intrinsic=None):
+        """The priority write-back, the policy update on the detached latents `zs` (its explicit draws: noise[n:], or
+        noise = None) and the metrics tensor in METRICS order; means = (similarity or consistency, reward, value,
+        total)."""
+        buffer.update_priorities(idxs, prio)
+        pi_loss = self.update_pi(zs, eps=None if noise is None else noise[n:])
+        self.last = dict(prio=prio) if intrinsic is None else dict(intrinsic=intrinsic, prio=prio)
+        m = [means[0], means[1], means[2], pi_loss.to(weighted.dtype), means[3], weighted.detach(), grad_norm]
+        if "intrinsic_batch_reward_mean" in self.METRICS:
+            m.append(intrinsic.mean())
+        return torch.stack(m).detach()
+
+    def _update_pi(self, zs, eps, batched, rho=None):
+        """The reference's `update_pi` -> pi_loss (tensor). batched: the latents in one pass, sum_t -mean(min Q_t) [*
+        rho[t], rho a float32 tensor]; otherwise the reference's loop, latent by latent [* rho ** t, rho a Python
+        float]. rho = None: no multiply at all."""
+        a, cfg, m = self.agent, self.cfg, self.agent.model
+        a.pi_optim.zero_grad(set_to_none=True)
+        m.track_q_grad(False)
+        n = len(zs)
+        if batched:
+            Z = torch.cat(list(zs))
+            act = m.pi(Z, cfg.min_std, eps=None if eps is None else torch.cat(list(eps[:n])))
+            pi_loss = -torch.min(*m.Q(Z, act)).view(n, -1).mean(dim=1)
+            pi_loss = (pi_loss if rho is None else pi_loss * rho[:n].view(n)).sum()
+        else:
+            pi_loss = 0
+            for t, z in enumerate(zs):
+                act = m.pi(z, cfg.min_std, eps=None if eps is None else eps[t])
+                loss = -torch.min(*m.Q(z, act)).mean()
+                pi_loss += loss if rho is None else loss * (rho ** t)
+        self._optimize(pi_loss, hook=False, pi=True)
+        m.track_q_grad(True)
+        return pi_loss.detach()
+
+    # ------------------------------------------------------------------ the driver
     @torch.no_grad()
     def ema(self):
-        """helper.py:48-52: target <- lerp(target, model, tau)."""
+        """helper.py:48-52: target <- lerp(target, model, tau) over the parameters."""
         torch._foreach_lerp_(self.target_params, self.params, self.cfg.tau)
 
     def _before_capture(self):
@@ -177,6 +279,8 @@ class GraphLearner:
 
     def update(self, buffer, step, noise=None):
         """One update -> what `step` returns, on the device (no sync)."""
+        if not self.on_gpu:
+            return self._update(buffer, step, noise)
         # the hipBLASLt products follow torch's process-wide fp32 matmul setting: pin full fp32 around every eager pass
         # and capture, whatever the caller set (ADVICE r5)
         prec = torch.get_float32_matmul_precision()
@@ -223,31 +327,32 @@ class GraphLearner:
         return m
 
 
-class Learner(GraphLearner):
-    """Owns the optimisers and (in graph mode) the captured update graphs of one TDMPC agent. `update` has TDMPC.update's
-    semantics -> metrics tensor [7] on the device."""
+class EngineLearner(GraphLearner):
+    """A learner with two paths: an engine (explicit forward and backward HIP passes over flat parameters, its two Adam
+    states standing in for the optimisers) on the GPU for the cfgs `ENGINE.supported` admits, unless the environment
+    variable ENGINE_ENV is "0"; otherwise `_step_torch` and `_torch_update_pi` on autograd, with `_torch_optimizers`.
+    `path` names the one in use. Everything done with the engine is done here; `agent.planner` may be absent."""
 
-    def __init__(self, agent, graph: bool = True, warmup: int = 3):
-        super().__init__(agent, graph, warmup)
+    ENGINE_ENV = None       # "0": the PyTorch path on the GPU
+    ENGINE = None           # the engine's module: `supported(cfg)` and the class named ENGINE_CLASS
+    ENGINE_CLASS = None
+    _torch_optimizers = GraphLearner._optimizers
+
+    def _optimizers(self):
+        """Build the engine where it applies (`engine`, `path`) -> its two Adam states, or the PyTorch optimisers."""
         self.engine = None
-        # (TDMPC_LEARNER_ENGINE=0: the autograd path with PyTorch's kernels, the bench's comparison leg)
-        if (str(agent.device).startswith("cuda") and learner_engine.supported(self.cfg) and
-                os.environ.get("TDMPC_LEARNER_ENGINE", "1") != "0"):
-            # explicit forward / backward kernels over flat parameters (tdmpc_amd/learner_engine.py); its two
-            # Adam states stand in for the reference's optimisers
-            self.engine = learner_engine.Engine(agent)
-            agent.optim, agent.pi_optim = self.engine.opt_main, self.engine.opt_pi
-        else:
-            # tdmpc.py:62-63 (Adam over all TOLD parameters; the policy's own Adam, both at cfg.lr)
-            agent.optim = torch.optim.Adam(self.params, lr=self.cfg.lr, capturable=graph, fused=True)
-            agent.pi_optim = torch.optim.Adam(self.pi_params, lr=self.cfg.lr, capturable=graph, fused=True)
         self._live_pack = False   # the last update repacked the planner's weights itself (repack_live)
-        H = self.cfg.horizon
-        # rho^t, t = 0..H, as float32 like the reference's Python-float scalar multiplies (tdmpc.py:212, 179)
-        self._rho = torch.tensor([self.cfg.rho ** t for t in range(H + 1)], dtype=torch.float32,
-                                 device=agent.device).view(H + 1, 1, 1)
+        if self.on_gpu and self.ENGINE.supported(self.cfg) and os.environ.get(self.ENGINE_ENV, "1") != "0":
+            self.engine = getattr(self.ENGINE, self.ENGINE_CLASS)(self.agent)
+            planner = getattr(self.agent, "planner", None)
+            if planner is not None:
+                # the engine moved every parameter into its flat buffer: a pack made before (a plan() ahead of the first
+                # update) holds the old tensors, and so do the pointers repack_live would read
+                planner._packed_key = None
+                planner._ptr_arr = None
+        self.path = "engine" if self.engine is not None else "torch"
+        return (self.engine.opt_main, self.engine.opt_pi) if self.engine is not None else self._torch_optimizers()
 
-    # ------------------------------------------------------------------ reference math
     @torch.no_grad()
     def td_target(self, next_obs, reward, eps=None):
         """tdmpc.py:184-190."""
@@ -256,33 +361,67 @@ class Learner(GraphLearner):
         return reward + cfg.discount * torch.min(*a.model_target.Q(next_z, a.model.pi(next_z, cfg.min_std, eps=eps)))
 
     def update_pi(self, zs, eps=None):
-        """tdmpc.py:165-182 -> pi_loss (tensor): the H+1 latents in one pass, sum_t -mean(min Q_t) rho^t."""
-        a, cfg = self.agent, self.cfg
-        if self.engine is not None:
-            return self.engine.update_pi(zs, eps)
-        a.pi_optim.zero_grad(set_to_none=True)
-        a.model.track_q_grad(False)
-        n = len(zs)
-        Z = torch.cat(zs)
-        act = a.model.pi(Z, cfg.min_std, eps=None if eps is None else torch.cat(list(eps[:n])))
-        q = torch.min(*a.model.Q(Z, act)).view(n, -1)
-        pi_loss = (-q.mean(dim=1) * self._rho[:n].view(n)).sum()
-        pi_loss.backward()
-        clip_grad_norm_19(self.pi_params, cfg.grad_clip_norm)
-        a.pi_optim.step()
-        a.model.track_q_grad(True)
-        return pi_loss.detach()
+        """tdmpc.py:165-182 -> pi_loss (tensor). zs: the detached latents; eps: optional [B, A] draws, one per latent."""
+        return self.engine.update_pi(zs, eps) if self.engine is not None else self._torch_update_pi(zs, eps)
 
     def step(self, buffer, noise=None):
-        """One TDMPC.update without the EMA (tdmpc.py:192-241) -> metrics tensor [7] (METRICS order).
-        noise: optional list of 2H+1 [B, A] TruncatedNormal draws (H for the TD targets, H+1 for update_pi)."""
-        if self.engine is not None:
-            m = self.engine.update(buffer, noise)
+        """One update without the EMA -> metrics tensor [7] (METRICS order), no synchronisation. noise: optional list of
+        2H + 1 [B, A] TruncatedNormal draws (H for the TD targets, H + 1 for update_pi)."""
+        if self.engine is None:
+            return self._step_torch(buffer, noise)
+        m = self.engine.update(buffer, noise)
+        self._after_engine_step()
+        planner = getattr(self.agent, "planner", None)
+        if planner is not None:
             from .tdmpc import repack_live
             # the planner's packed weights straight from the engine's flat buffer (one fused launch, inside the
             # captured graph when this step is captured); without a live pack the next plan() repacks
-            self._live_pack = repack_live(self.agent.planner, self.agent.model)
-            return m
+            self._live_pack = repack_live(planner, self.agent.model)
+        return m
+
+    def _after_engine_step(self):
+        """What an engine update leaves to the module (nothing by default)."""
+
+    @torch.no_grad()
+    def ema(self):
+        return self.engine.ema(self.cfg.tau) if self.engine is not None else super().ema()
+
+    def _before_capture(self):
+        if self.engine is not None and getattr(self.agent, "planner", None) is not None:
+            # the captured update repacks the planner from the engine's buffer (repack_live): pack once now so the
+            # planner holds the live tensors and the pack's job table exists before the capture
+            self.agent.planner.pack(self.agent.model)
+
+    def _after_update(self):
+        if not self._live_pack:   # (the update itself repacked from the engine's buffer, repack_live)
+            super()._after_update()
+
+
+class Learner(EngineLearner):
+    """Owns the optimisers and (in graph mode) the captured update graphs of one TDMPC agent. `update` has TDMPC.update's
+    semantics -> metrics tensor [7] on the device. TDMPC_LEARNER_ENGINE=0: the autograd path with PyTorch's kernels (the
+    bench's comparison leg), which every cfg `learner_engine.supported` does not admit takes as well."""
+
+    ENGINE_ENV, ENGINE, ENGINE_CLASS = "TDMPC_LEARNER_ENGINE", learner_engine, "Engine"
+
+    def __init__(self, agent, graph: bool = True, warmup: int = 3):
+        super().__init__(agent, graph, warmup)
+        H = self.cfg.horizon
+        # rho^t, t = 0..H, as float32 like the reference's Python-float scalar multiplies (tdmpc.py:212, 179)
+        self._rho = torch.tensor([self.cfg.rho ** t for t in range(H + 1)], dtype=torch.float32,
+                                 device=agent.device).view(H + 1, 1, 1)
+
+    def _torch_optimizers(self):
+        # tdmpc.py:62-63 (Adam over all TOLD parameters; the policy's own Adam, both at cfg.lr)
+        return (torch.optim.Adam(self.params, lr=self.cfg.lr, capturable=self.graph, fused=True),
+                torch.optim.Adam(self.pi_params, lr=self.cfg.lr, capturable=self.graph, fused=True))
+
+    def _torch_update_pi(self, zs, eps):
+        """The H + 1 latents in one pass, sum_t -mean(min Q_t) rho^t."""
+        return self._update_pi(zs, eps, batched=True, rho=self._rho)
+
+    def _step_torch(self, buffer, noise):
+        """tdmpc.py:192-241 on autograd."""
         a, cfg = self.agent, self.cfg
         m = a.model
         H = cfg.horizon
@@ -329,24 +468,5 @@ class Learner(GraphLearner):
             means = (consistency_loss.mean(), reward_loss.mean(), value_loss.mean(), total_loss.mean())
             prio = priority_loss.clamp(max=1e4).detach()
         zs = [zz.detach() for zz in zs]
-        weighted_loss.register_hook(lambda grad: grad * (1 / H))
-        weighted_loss.backward()
-        grad_norm = clip_grad_norm_19(self.params, cfg.grad_clip_norm)
-        a.optim.step()
-        buffer.update_priorities(idxs, prio)
-        pi_loss = self.update_pi(zs, eps=None if noise is None else noise[H:])
-        return torch.stack([means[0], means[1], means[2], pi_loss, means[3], weighted_loss, grad_norm]).detach()
-
-    @torch.no_grad()
-    def ema(self):
-        return self.engine.ema(self.cfg.tau) if self.engine is not None else super().ema()
-
-    def _before_capture(self):
-        if self.engine is not None:
-            # the captured update repacks the planner from the engine's buffer (repack_live): pack once now so the
-            # planner holds the live tensors and the pack's job table exists before the capture
-            self.agent.planner.pack(self.agent.model)
-
-    def _after_update(self):
-        if not self._live_pack:   # (the update itself repacked from the engine's buffer, repack_live)
-            super()._after_update()
+        grad_norm = self._optimize(weighted_loss)
+        return self._finish(buffer, idxs, prio, zs, noise, H, means, weighted_loss, grad_norm)

@@ -73,6 +73,49 @@ def test_train_loop_plans_with_updated_weights():
 
 
 @pytest.mark.gpu
+def test_first_plan_before_the_learner_exists():
+    """The reference's train.py order: the first plan() comes before the first update, so the planner has packed the
+    model's tensors before the learner engine moves every parameter into its flat buffer. The learner drops that pack:
+    the plans after the first update (eager) and after the fourth (the default warmup = 3: two eager updates, the
+    side-stream one, then capture and replay) run on the agent's current weights."""
+    from tdmpc_amd.replay import ReplayBuffer
+    from tdmpc_amd.tdmpc import TDMPC
+    cfg = learner_cfg()
+    rc = SimpleNamespace(**{**vars(cfg), "device": "cuda", "train_steps": 2000, "max_buffer_size": 10**6,
+                            "episode_length": 200, "env_horizon": cfg.horizon})
+    rs = np.random.RandomState(3)
+    agent = TDMPC(cfg)
+    agent.model.load_state_dict(synthetic_state_dict(cfg, 41))
+    agent.model_target.load_state_dict(synthetic_state_dict(cfg, 42))
+    buf = ReplayBuffer(rc, latent_plan=True)
+    for _ in range(3):
+        buf.add(SimpleNamespace(obs=torch.from_numpy(rs.standard_normal((201, 5)).astype(np.float32)),
+                                action=torch.from_numpy(rs.uniform(-1, 1, (200, 1)).astype(np.float32)),
+                                reward=torch.from_numpy(rs.standard_normal(200).astype(np.float32))))
+    w0 = [p.detach().clone() for p in agent.model.parameters()]
+    obs = rs.standard_normal(cfg.obs_shape).astype(np.float32)
+    torch.manual_seed(0)
+    np.random.seed(0)
+    step = 10**6
+    errs = {}
+    for k in range(4):
+        a, m = agent.plan(obs, step=step, t0=(k == 0))
+        assert torch.isfinite(a).all()
+        agent.update(buf, k + 1)
+        lrn = agent.learner()
+        if lrn.engine is None:
+            pytest.skip("learner engine not used for this config")
+        if k in (0, 3):
+            v_gpu, v_ref = _oracle_first_values(agent, cfg, obs, step)
+            errs[k] = ((v_gpu - v_ref).abs().max().item(), 1e-4 * (1 + v_ref.abs().max().item()))
+            print(f"plan after update {k + 1}: max|dG| {errs[k][0]:.3e}, bound {errs[k][1]:.3e}")
+    assert lrn._graphs, "the learner never replayed its captured graph"
+    assert any(not torch.equal(p, q) for p, q in zip(agent.model.parameters(), w0)), "no update reached the model"
+    for k, (err, bound) in errs.items():
+        assert err < bound, f"plan after update {k + 1} of a learner made after the first plan: max|dG| {err}"
+
+
+@pytest.mark.gpu
 def test_update_pi_then_plan_repacks():
     """TDMPC.update_pi (tdmpc.py:165-182) on the learner engine writes the policy weights in place (no tensor version
     bump); the next plan() must plan with them: its first-iteration values equal the oracle's on the agent's
