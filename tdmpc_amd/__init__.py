@@ -6,6 +6,7 @@ The drop-in names:
     from tdmpc_amd import TOLD             # src/algorithm/tdmpc.py:9 (same module tree and state_dict keys)
     from tdmpc_amd import TdMpcSim         # src/algorithm/tdmpc_similarity.py:75 (TDMPCSIM: TDMPC's plan, the similarity update)
     from tdmpc_amd import ReplayBuffer     # src/algorithm/helper.py:434 (device prioritized replay)
+    from tdmpc_amd import RolloutBuffer    # src/algorithm/helper.py:537 (the same for episodes of differing length)
     from tdmpc_amd import TdICEM           # src/algorithm/tdmpc_icem_similarity_mlp.py:116 (iCEM planner)
     from tdmpc_amd import TdIcemMlp        # src/algorithm/tdmpc_icem_similarity_mlp.py:77 (the same agent with its update)
     from tdmpc_amd import TdMpcDrnn        # src/algorithm/tdmpc_similarity_drnn.py:87 (GRU-dynamics DSSM planner)
@@ -24,6 +25,7 @@ _EXPORTS = {
     "load_checkpoint": "tdmpc",
     "TOLD": "told",
     "ReplayBuffer": "replay",
+    "RolloutBuffer": "replay",
     "TdICEM": "icem",
     "TdIcemMlp": "icem_mlp",
     "IcemMlpModel": "icem_mlp",

@@ -22,7 +22,8 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_debug_pack_check",
             "tdmpc_profile_begin", "tdmpc_profile_end", "tdmpc_profile_kernel", "tdmpc_icem_sizes_for", "tdmpc_plan_icem",
             # include/tdmpc_replay.h
-            "tdmpc_replay_workspace_bytes", "tdmpc_replay_add_priorities", "tdmpc_replay_update_priorities",
+            "tdmpc_replay_workspace_bytes", "tdmpc_replay_add_priorities", "tdmpc_replay_add_priorities_len",
+            "tdmpc_replay_update_priorities",
             "tdmpc_replay_sample",
             # include/tdmpc_learner.h
             "tdmpc_loss_forward", "tdmpc_loss_backward", "tdmpc_random_shift", "tdmpc_random_shift_scaled",
@@ -247,6 +248,7 @@ def lib():
     L.tdmpc_replay_workspace_bytes.argtypes = [C.POINTER(ReplayDims)]
     L.tdmpc_replay_workspace_bytes.restype = sz
     L.tdmpc_replay_add_priorities.argtypes = [C.POINTER(ReplayDims), vp, i32, i32, vp, sz, vp]
+    L.tdmpc_replay_add_priorities_len.argtypes = [C.POINTER(ReplayDims), vp, i32, i32, i32, vp, sz, vp]
     L.tdmpc_replay_update_priorities.argtypes = [C.POINTER(ReplayDims), vp, vp, vp, i32, C.c_float, vp, sz, vp]
     L.tdmpc_replay_sample.argtypes = [C.POINTER(ReplayDims), C.POINTER(ReplayStore), i32, i32, C.c_float,
                                       C.c_float, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]

@@ -68,10 +68,16 @@ struct RWork {
     size_t total;
 };
 
+constexpr int RP_MAX_BATCH = 2048;   // rp_norepl_kernel: two items per thread of its one 1024-thread workgroup
+
+// episode_length == 0 is the rollout layout (variable-length episodes, state observations only): no multiple-of-L
+// capacity, no horizon < L, no last_obs.
 bool dims_ok(const tdmpc_replay_dims* d) {
-    if (!d || d->capacity <= 0 || d->episode_length <= 0 || d->capacity % d->episode_length || d->horizon < 0 ||
-        d->horizon >= d->episode_length || d->batch_size <= 0 || d->batch_size > 1024 || d->action_dim <= 0)
+    if (!d || d->capacity <= 0 || d->episode_length < 0 || d->horizon < 0 || d->batch_size <= 0 ||
+        d->batch_size > RP_MAX_BATCH || d->action_dim <= 0)
         return false;
+    if (d->episode_length == 0) return d->modality == 0 && d->obs_dim > 0;
+    if (d->capacity % d->episode_length || d->horizon >= d->episode_length) return false;
     if (d->modality == 0) return d->obs_dim > 0;
     return d->modality == 1 && d->img_hw > 0 && d->frame_stack > 0;
 }
@@ -234,43 +240,68 @@ __global__ void __launch_bounds__(64) rp_choice_kernel(const double* cdf, const 
     if (lane == 0) idx[b] = m ? lo + __ffsll(m) - 1 : hi - 1;
 }
 
-// Ascending bitonic sort of 1024 keys, one per thread of a 1024-thread block, returned in the thread's register
-// (thread t holds the t-th smallest). Partner distances below 64 run in the wave (xor shuffles, no barrier); only
-// the 10 steps with j >= 64 go through LDS (`buf`, 1024 keys).
-template <typename K>
-DEVI K bitonic1024(K v, K* buf, int t) {
-    for (int k = 2; k <= 1024; k <<= 1)
+// The without-replacement workgroup has 1024 threads and IPT (1 or 2) items per thread: item q of thread t is
+// element e = t + 1024 q of a 1024 IPT-element sequence (IPT = 1: element t, one per thread).
+
+// Ascending bitonic sort of 1024 IPT keys in place in the threads' registers (element e ends as the e-th smallest).
+// Partner distances below 64 run in the wave (xor shuffles, no barrier); the steps with 64 <= j < 1024 go through LDS
+// (`buf`, 1024 IPT keys); j = 1024 (IPT = 2 only) pairs a thread's own two keys.
+template <int IPT, typename K>
+DEVI void bitonic_block(K (&v)[IPT], K* buf, int t) {
+    // fully unrolled, so each step's partner distance j is a compile-time constant
+#pragma unroll
+    for (int k = 2; k <= 1024 * IPT; k <<= 1)
+#pragma unroll
         for (int j = k >> 1; j > 0; j >>= 1) {
-            K o;
-            if (j >= 64) {
-                buf[t] = v;
+            K o[IPT];
+            if (j >= 1024) {
+#pragma unroll
+                for (int q = 0; q < IPT; ++q) o[q] = v[q ^ (IPT - 1)];
+            } else if (j >= 64) {
+#pragma unroll
+                for (int q = 0; q < IPT; ++q) buf[t + 1024 * q] = v[q];
                 __syncthreads();
-                o = buf[t ^ j];
+#pragma unroll
+                for (int q = 0; q < IPT; ++q) o[q] = buf[(t ^ j) + 1024 * q];
                 __syncthreads();
             } else {
-                o = __shfl_xor(v, j, 64);
+#pragma unroll
+                for (int q = 0; q < IPT; ++q) o[q] = __shfl_xor(v[q], j, 64);
             }
-            const bool lower = (t & j) == 0, up = (t & k) == 0;
-            // the lower partner keeps the min when ascending, the max when descending
-            v = (lower == up) ? (o < v ? o : v) : (o < v ? v : o);
+#pragma unroll
+            for (int q = 0; q < IPT; ++q) {
+                const int e = t + 1024 * q;
+                const bool lower = (e & j) == 0, up = (e & k) == 0;
+                // the lower partner keeps the min when ascending, the max when descending
+                v[q] = (lower == up) ? (o[q] < v[q] ? o[q] : v[q]) : (o[q] < v[q] ? v[q] : o[q]);
+            }
         }
-    return v;
 }
 
-// Inclusive prefix sum over a 1024-thread block: wave scans by shuffles, then the 16 wave totals (2 barriers).
-template <typename T>
-DEVI T block_scan1024(T v, T* wsum, int t) {
+// Inclusive prefix sum over the 1024 IPT elements, in place; returns their total. Per 1024 elements: wave scans by
+// shuffles, then the 16 wave totals in order (2 barriers); the second 1024 start from the first's total.
+template <int IPT, typename T>
+DEVI T block_scan(T (&v)[IPT], T* wsum, int t) {
     const int lane = t & 63, w = t >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const T u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
+    T carry = 0;
+#pragma unroll
+    for (int q = 0; q < IPT; ++q) {
+        T x = v[q];
+        for (int o = 1; o < 64; o <<= 1) {
+            const T u = __shfl_up(x, o, 64);
+            if (lane >= o) x += u;
+        }
+        if (lane == 63) wsum[w] = x;
+        __syncthreads();
+        T add = carry;   // carry + wsum[0] + ... + wsum[w - 1]: the running total as it stands at wave w
+        for (int i = 0; i < 16; ++i) {
+            if (i == w) add = carry;
+            carry += wsum[i];
+        }
+        __syncthreads();
+        v[q] = x + add;
     }
-    if (lane == 63) wsum[w] = v;
-    __syncthreads();
-    T add = 0;
-    for (int i = 0; i < w; ++i) add += wsum[i];
-    __syncthreads();
-    return v + add;
+    return carry;
 }
 
 // Uniform number k >= n_u of a without-replacement sample whose caller-supplied stream ran out: a splitmix64 hash of
@@ -293,24 +324,34 @@ DEVI double extra_uniform(const double* u, int n_u, int k) {
 // found entry: those have no mass left). n_used: uniforms consumed;
 // -2 when fewer than B entries have non-zero probability (numpy raises "Fewer non-zero entries in p than size";
 // idx is then padded with 0).
+// IPT items per thread: B <= 1024 IPT draws, found entries and hash probes (IPT = 1 for a batch of up to 1024, one
+// per thread; IPT = 2 up to 2048). LDS: 44 KB at IPT = 1, 88 KB at IPT = 2 (of the workgroup's 160 KB).
+template <int IPT>
 __global__ void __launch_bounds__(1024) rp_norepl_kernel(const double* cdf, const double* boff, const double* scal,
                                                          const float* probs, int total, int B, const double* u,
                                                          int n_u, int64_t* idx, int32_t* n_used) {
-    __shared__ int fs[1024];        // found indices, sorted ascending, [0, nf)
-    __shared__ double fm[1024];     // fm[k] = mass of fs[0..k]
-    __shared__ int order[1024];     // found indices in numpy's output order
-    __shared__ int nv[1024];        // this round's draws
-    __shared__ int newv[1024];      // this round's new found values
-    __shared__ int hkey[2048];      // hash set of the round's values
-    __shared__ int hpos[2048];      // smallest draw position per value
-    __shared__ int sk[1024];        // sort exchange buffer
+    constexpr int N = 1024 * IPT;     // most draws / found entries
+    constexpr int HS = 2 * N;         // hash slots
+    constexpr int HSHIFT = IPT == 1 ? 21 : 20;   // 32 - log2(HS): an 11- or 12-bit hash
+    __shared__ int fs[N];           // found indices, sorted ascending, [0, nf)
+    __shared__ double fm[N];        // fm[k] = mass of fs[0..k]
+    __shared__ int order[N];        // found indices in numpy's output order
+    __shared__ int nv[N];           // this round's draws
+    __shared__ int newv[N];         // this round's new found values
+    __shared__ int hkey[HS];        // hash set of the round's values
+    __shared__ int hpos[HS];        // smallest draw position per value
+    __shared__ int sk[N];           // sort exchange buffer
     __shared__ int iws[16];
     __shared__ double dws[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nw = blockDim.x >> 6;
     int n_uniq = 0, used = 0, nf = 0;
     const double last = scal[1];
     bool ok = true;
-    if (t < B) nv[t] = (int)idx[t];   // round 1 (rp_choice_kernel)
+#pragma unroll
+    for (int q = 0; q < IPT; ++q) {
+        const int e = t + 1024 * q;
+        if (e < B) nv[e] = (int)idx[e];   // round 1 (rp_choice_kernel)
+    }
     __syncthreads();
     for (int round = 0; n_uniq < B; ++round) {
         const int m = B - n_uniq;
@@ -347,42 +388,75 @@ __global__ void __launch_bounds__(1024) rp_norepl_kernel(const double* cdf, cons
         used += m;
         // first occurrences (np.unique(return_index)): an LDS hash set of the round's values, each slot keeping
         // the smallest draw position that holds its value
-        hkey[t] = -1; hkey[t + 1024] = -1;
-        hpos[t] = 0x7fffffff; hpos[t + 1024] = 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < 2 * IPT; ++q) {
+            hkey[t + 1024 * q] = -1;
+            hpos[t + 1024 * q] = 0x7fffffff;
+        }
         __syncthreads();
-        int slot = 0;
-        if (t < m) {
-            const int v = nv[t];
-            slot = (int)(((unsigned)v * 2654435761u) >> 21);   // 11 bits
-            while (true) {
-                const int old = atomicCAS(&hkey[slot], -1, v);
-                if (old == -1 || old == v) break;
-                slot = (slot + 1) & 2047;
+        int slot[IPT];
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            const int e = t + 1024 * q;
+            slot[q] = 0;
+            if (e < m) {
+                const int v = nv[e];
+                int s = (int)(((unsigned)v * 2654435761u) >> HSHIFT);
+                while (true) {
+                    const int old = atomicCAS(&hkey[s], -1, v);
+                    if (old == -1 || old == v) break;
+                    s = (s + 1) & (HS - 1);
+                }
+                atomicMin(&hpos[s], e);
+                slot[q] = s;
             }
-            atomicMin(&hpos[slot], t);
         }
         __syncthreads();
-        const bool first = t < m && hpos[slot] == t;
-        const int rank = block_scan1024(first ? 1 : 0, iws, t) - (first ? 1 : 0);
-        int nnew = 0;
-        for (int i = 0; i < 16; ++i) nnew += iws[i];
-        if (first) {
-            order[n_uniq + rank] = nv[t];
-            newv[rank] = nv[t];
+        bool first[IPT];
+        int rank[IPT];
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            const int e = t + 1024 * q;
+            first[q] = e < m && hpos[slot[q]] == e;
+            rank[q] = first[q] ? 1 : 0;
         }
+        const int nnew = block_scan<IPT>(rank, iws, t);   // inclusive ranks in draw order
+#pragma unroll
+        for (int q = 0; q < IPT; ++q)
+            if (first[q]) {
+                const int v = nv[t + 1024 * q];
+                order[n_uniq + rank[q] - 1] = v;
+                newv[rank[q] - 1] = v;
+            }
         n_uniq += nnew;
         __syncthreads();
         if (n_uniq >= B) break;
         // the next round searches cdf - (found masses): found set = previous found + this round's, sorted
-        int v2 = t < nf ? fs[t] : (t < nf + nnew ? newv[t - nf] : 0x7fffffff);
-        v2 = bitonic1024(v2, sk, t);
-        fs[t] = v2;
+        int v2[IPT];
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            const int e = t + 1024 * q;
+            v2[q] = e < nf ? fs[e] : (e < nf + nnew ? newv[e - nf] : 0x7fffffff);
+        }
+        bitonic_block<IPT>(v2, sk, t);
         nf += nnew;
-        const double fmv = block_scan1024(t < nf ? (double)probs[v2] : 0.0, dws, t);
-        fm[t] = fmv;
+        double mass[IPT];
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            const int e = t + 1024 * q;
+            fs[e] = v2[q];
+            mass[q] = e < nf ? (double)probs[v2[q]] : 0.0;
+        }
+        block_scan<IPT>(mass, dws, t);
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) fm[t + 1024 * q] = mass[q];
         __syncthreads();
     }
-    if (t < B) idx[t] = t < n_uniq ? order[t] : 0;
+#pragma unroll
+    for (int q = 0; q < IPT; ++q) {
+        const int e = t + 1024 * q;
+        if (e < B) idx[e] = e < n_uniq ? order[e] : 0;
+    }
     if (t == 0 && n_used) *n_used = ok ? used : -2;
 }
 
@@ -447,7 +521,7 @@ __global__ void __launch_bounds__(256) rp_gather_kernel(const GatherArgs a) {
     }
     const int t = y - 1;
     float* dst = a.o_next + ((size_t)t * a.B + b) * F;
-    if (t == a.H && (i + a.H + 1) % a.L == 0 && i + a.H < a.cap) {
+    if (a.L > 0 && t == a.H && (i + a.H + 1) % a.L == 0 && i + a.H < a.cap) {   // L == 0: rollout layout, no fix-up
         // episode end: the stored final observation (helper.py:525-526)
         const long e = (i + a.H) / a.L;
         if (a.modality == 0) {
@@ -495,7 +569,7 @@ __global__ void __launch_bounds__(1024) rp_add_prio_kernel(float* prio, const fl
         __syncthreads();
     }
     const float maxp = first ? 1.0f : red[0];
-    for (int k = t; k < L; k += 1024) prio[idx + k] = k >= L - H ? 0.f : maxp;
+    for (int k = t; k < L; k += 1024) prio[idx + k] = k >= L - H ? 0.f : maxp;   // L < H: all of them 0
 }
 
 // p[idxs[i]] = v[i] + eps; with duplicate indices the LAST occurrence wins, like a sequential index_put_ (the
@@ -552,9 +626,16 @@ size_t tdmpc_replay_workspace_bytes(const tdmpc_replay_dims* d) {
 
 int tdmpc_replay_add_priorities(const tdmpc_replay_dims* d, float* prio, int32_t idx, int32_t full, void* ws,
                                 size_t ws_bytes, void* stream) {
+    if (!d) return TDMPC_E_NULL;
+    if (!dims_ok(d) || d->episode_length == 0 || idx < 0 || idx % d->episode_length) return TDMPC_E_DIMS;
+    return tdmpc_replay_add_priorities_len(d, prio, idx, d->episode_length, full, ws, ws_bytes, stream);
+}
+
+int tdmpc_replay_add_priorities_len(const tdmpc_replay_dims* d, float* prio, int32_t idx, int32_t len, int32_t full,
+                                    void* ws, size_t ws_bytes, void* stream) {
     if (!d || !prio || !ws) return TDMPC_E_NULL;
     if (!dims_ok(d)) return TDMPC_E_DIMS;
-    if (idx < 0 || idx % d->episode_length || idx + d->episode_length > d->capacity) return TDMPC_E_DIMS;
+    if (idx < 0 || len <= 0 || len > d->capacity - idx) return TDMPC_E_DIMS;
     RWork w;
     make_rwork(d, nullptr, &w);
     if (ws_bytes < w.total) return TDMPC_E_SIZE;
@@ -564,8 +645,8 @@ int tdmpc_replay_add_priorities(const tdmpc_replay_dims* d, float* prio, int32_t
     const int nb = std::max(1, (n + RB - 1) / RB);
     if (n > 0) hipLaunchKernelGGL(rp_max_kernel, dim3(nb), dim3(RT), 0, s, prio, n, w.part);
     RCHK(hipGetLastError());
-    hipLaunchKernelGGL(rp_add_prio_kernel, dim3(1), dim3(1024), 0, s, prio, w.part, n > 0 ? nb : 0, idx,
-                       d->episode_length, d->horizon, (int)(n == 0));
+    hipLaunchKernelGGL(rp_add_prio_kernel, dim3(1), dim3(1024), 0, s, prio, w.part, n > 0 ? nb : 0, idx, len,
+                       d->horizon, (int)(n == 0));
     RCHK(hipGetLastError());
     return 0;
 }
@@ -602,7 +683,7 @@ int tdmpc_replay_sample(const tdmpc_replay_dims* d, const tdmpc_replay_store* st
                         float* obs, float* next_obs, float* action, float* reward, float* probs_out,
                         int32_t* n_used, void* ws, size_t ws_bytes, void* stream) {
     if (!d || !st || !u || !idxs || !weights || !obs || !next_obs || !action || !reward || !ws) return TDMPC_E_NULL;
-    if (!st->obs || !st->last_obs || !st->action || !st->reward || !st->priorities) return TDMPC_E_NULL;
+    if (!st->obs || (!st->last_obs && d->episode_length) || !st->action || !st->reward || !st->priorities) return TDMPC_E_NULL;
     if (!dims_ok(d) || total <= 0 || total > d->capacity) return TDMPC_E_DIMS;
     const int B = d->batch_size;
     if (n_u < B || (full && total < B)) return TDMPC_E_DIMS;
@@ -623,8 +704,9 @@ int tdmpc_replay_sample(const tdmpc_replay_dims* d, const tdmpc_replay_store* st
     hipLaunchKernelGGL(rp_choice_kernel, dim3(B), dim3(64), 0, s, w.cdf, w.boff, w.scal, total, u, w.idx, n_used);
     RCHK(hipGetLastError());
     if (full) {
-        hipLaunchKernelGGL(rp_norepl_kernel, dim3(1), dim3(1024), 0, s, w.cdf, w.boff, w.scal, w.probs, total, B, u,
-                           n_u, w.idx, n_used);
+        const auto norepl = B <= 1024 ? rp_norepl_kernel<1> : rp_norepl_kernel<2>;   // items per thread
+        hipLaunchKernelGGL(norepl, dim3(1), dim3(1024), 0, s, w.cdf, w.boff, w.scal, w.probs, total, B, u, n_u, w.idx,
+                           n_used);
         RCHK(hipGetLastError());
     }
     GatherArgs g;

@@ -12,6 +12,9 @@ Randomness: the reference draws np.random.choice's uniforms from numpy's global 
 from torch's generator on the device (a float64 `uniform_()` buffer), consumed in numpy's order, so a
 given uniform stream selects exactly numpy's indices (tests/test_replay.py) -- but the stream itself is not
 numpy's. Pass `u=` to `sample` to supply it (parity tests).
+
+`RolloutBuffer` is the same device buffer for the reference's variable-length-episode class (helper.py:537-636),
+see its docstring. Both classes share `_DeviceReplay`: everything but the constructor's shapes and `add`.
 """
 from __future__ import annotations
 
@@ -24,22 +27,29 @@ import torch
 from . import _lib
 
 
-class ReplayBuffer:
+class _DeviceReplay:
+    """What `ReplayBuffer` and `RolloutBuffer` share: the device storage behind include/tdmpc_replay.h, and
+    `update_priorities`, `sample`, `uniforms_used` and `check_sample` on it. A subclass's constructor calls
+    `_alloc` with its shapes and layout, and defines `add`."""
     graph_safe = True   # sample() / update_priorities() are sync-free and capturable (tdmpc_amd.learner)
 
-    def __init__(self, cfg, latent_plan: bool = False):
+    def _alloc(self, cfg, obs_shape, horizon: int, episode_length: int):
+        """Storage, dims and output buffers. `obs_shape`: a sampled observation's shape (pixels: the frame stack).
+        `episode_length` 0: the rollout layout (state only; `_obs` zero-filled, `_last_obs` left to the subclass)."""
         self.cfg = deepcopy(cfg)
         self.device = torch.device(cfg.device)
         self.capacity = int(min(cfg.train_steps, cfg.max_buffer_size))
-        L = int(cfg.episode_length)
-        if self.capacity % L:
-            raise ValueError("capacity must be a multiple of episode_length")
+        L = int(episode_length)
         pixels = cfg.modality != "state"
         dtype = torch.uint8 if pixels else torch.float32
-        frame = (3, *cfg.obs_shape[-2:]) if pixels else tuple(cfg.obs_shape)
+        obs_shape = tuple(obs_shape)
+        frame = (3, *obs_shape[-2:]) if pixels else obs_shape
         dev = self.device
-        self._obs = torch.empty((self.capacity + 1, *frame), dtype=dtype, device=dev)
-        self._last_obs = torch.empty((self.capacity // L, *cfg.obs_shape), dtype=dtype, device=dev)
+        if L:
+            self._obs = torch.empty((self.capacity + 1, *frame), dtype=dtype, device=dev)
+            self._last_obs = torch.empty((self.capacity // L, *obs_shape), dtype=dtype, device=dev)
+        else:
+            self._obs = torch.zeros((self.capacity + 1, *frame), dtype=dtype, device=dev)
         self._action = torch.empty((self.capacity, cfg.action_dim), dtype=torch.float32, device=dev)
         self._reward = torch.empty((self.capacity,), dtype=torch.float32, device=dev)
         self._priorities = torch.ones((self.capacity,), dtype=torch.float32, device=dev)
@@ -47,11 +57,11 @@ class ReplayBuffer:
         self._full = False
         self.idx = 0
         self.batch_size = int(cfg.batch_size)
-        self.horizon = int(cfg.horizon if latent_plan else cfg.env_horizon)
+        self.horizon = int(horizon)
         d = _lib.ReplayDims()
         d.modality = 1 if pixels else 0
-        d.obs_dim = 0 if pixels else int(cfg.obs_shape[0])
-        d.img_hw = int(cfg.obs_shape[-1]) if pixels else 0
+        d.obs_dim = 0 if pixels else int(obs_shape[0])
+        d.img_hw = int(obs_shape[-1]) if pixels else 0
         d.frame_stack = int(cfg.frame_stack) if pixels else 1
         d.action_dim = int(cfg.action_dim)
         d.episode_length = L
@@ -65,7 +75,6 @@ class ReplayBuffer:
             raise ValueError("unsupported replay buffer dims")
         self._ws = torch.zeros(ws, dtype=torch.uint8, device=dev)   # zero-filled once (update_priorities' keys)
         B, H = self.batch_size, self.horizon
-        obs_shape = tuple(cfg.obs_shape)
         self._out_idx = torch.empty(B, dtype=torch.int64, device=dev)
         self._out_w = torch.empty(B, dtype=torch.float32, device=dev)
         self._out_obs = torch.empty((B, *obs_shape), dtype=torch.float32, device=dev)
@@ -74,30 +83,20 @@ class ReplayBuffer:
         self._out_reward = torch.empty((H + 1, B), dtype=torch.float32, device=dev)
         self._n_used = torch.zeros(1, dtype=torch.int32, device=dev)
         self._ubuf = torch.empty(4 * B, dtype=torch.float64, device=dev)
-        self._store = _lib.ReplayStore(self._obs.data_ptr(), self._last_obs.data_ptr(), self._action.data_ptr(),
-                                       self._reward.data_ptr(), self._priorities.data_ptr())
+        self._store = _lib.ReplayStore(self._obs.data_ptr(), self._last_obs.data_ptr() if L else None,
+                                       self._action.data_ptr(), self._reward.data_ptr(), self._priorities.data_ptr())
         self.last_probs = None
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def __add__(self, episode):
-        self.add(episode)
-        return self
-
-    def add(self, episode):
-        """helper.py:467-485. `episode` has obs [L+1, *obs_shape], action [L, A], reward [L] (the reference
-        `Episode`, or any object with those attributes)."""
-        L = int(self.cfg.episode_length)
-        obs = torch.as_tensor(episode.obs).to(self.device)
-        self._obs[self.idx:self.idx + L] = obs[:-1] if self.cfg.modality == "state" else obs[:-1, -3:]
-        self._last_obs[self.idx // L] = obs[-1]
-        self._action[self.idx:self.idx + L] = torch.as_tensor(episode.action).to(self.device)
-        self._reward[self.idx:self.idx + L] = torch.as_tensor(episode.reward).to(self.device)
-        _lib.check(self._L.tdmpc_replay_add_priorities(
-            C.byref(self._dims), C.c_void_p(self._priorities.data_ptr()), self.idx, int(self._full),
-            C.c_void_p(self._ws.data_ptr()), self._ws.numel(), self._stream()), "tdmpc_replay_add_priorities")
-        self.idx = (self.idx + L) % self.capacity
+    def _add_priorities(self, n: int):
+        """The priorities of the `n` transitions just written at `idx` (device running max, no host sync), then
+        the reference's advance of `idx` / `_full`."""
+        _lib.check(self._L.tdmpc_replay_add_priorities_len(
+            C.byref(self._dims), C.c_void_p(self._priorities.data_ptr()), self.idx, n, int(self._full),
+            C.c_void_p(self._ws.data_ptr()), self._ws.numel(), self._stream()), "tdmpc_replay_add_priorities_len")
+        self.idx = (self.idx + n) % self.capacity
         self._full = self._full or self.idx == 0
 
     def update_priorities(self, idxs, priorities):
@@ -158,3 +157,84 @@ class ReplayBuffer:
             warnings.warn(f"replay sample consumed {used} uniforms, {n_u} supplied: the rounds past the supplied "
                           "stream used the kernel's hash stream (not numpy's draw for this stream)", RuntimeWarning)
         return used
+
+
+class ReplayBuffer(_DeviceReplay):
+    """The reference's `ReplayBuffer` (module docstring): full-length episodes, `_last_obs` per episode."""
+
+    def __init__(self, cfg, latent_plan: bool = False):
+        L = int(cfg.episode_length)
+        if int(min(cfg.train_steps, cfg.max_buffer_size)) % L:
+            raise ValueError("capacity must be a multiple of episode_length")
+        self._alloc(cfg, cfg.obs_shape, cfg.horizon if latent_plan else cfg.env_horizon, L)
+
+    def __add__(self, episode):
+        self.add(episode)
+        return self
+
+    def add(self, episode):
+        """helper.py:467-485. `episode` has obs [L+1, *obs_shape], action [L, A], reward [L] (the reference
+        `Episode`, or any object with those attributes)."""
+        L = int(self.cfg.episode_length)
+        obs = torch.as_tensor(episode.obs).to(self.device)
+        self._obs[self.idx:self.idx + L] = obs[:-1] if self.cfg.modality == "state" else obs[:-1, -3:]
+        self._last_obs[self.idx // L] = obs[-1]
+        self._action[self.idx:self.idx + L] = torch.as_tensor(episode.action).to(self.device)
+        self._reward[self.idx:self.idx + L] = torch.as_tensor(episode.reward).to(self.device)
+        self._add_priorities(L)
+
+
+class RolloutBuffer(_DeviceReplay):
+    """Drop-in for the reference's `RolloutBuffer` (helper.py:537-636), the buffer of its `train_dyna_episode*`
+    loops: `buffer += episode` with episodes that end early and so differ in length. State modality; observation
+    rows have shape `cfg.buffer_shape`; `horizon = cfg.horizon`; `capacity = min(train_steps, max_buffer_size)` with
+    no multiple-of-anything rule. Same attributes as the reference (`_last_obs` is its Python list of the episodes'
+    final observations: appended to, never read; here it keeps the newest `capacity` rows). Sampling, priorities and the device-side machinery are
+    `ReplayBuffer`'s; the gather has no episode-end fix-up: `next_obs[t] = _obs[idxs + t + 1]` always.
+
+    Two reference behaviours kept on purpose:
+    * `+=` of an episode that does not fit behind `idx` (and `idx != 0`) zeroes `_priorities[idx:]`, sets `idx = 0`
+      and `_full = True`, and DROPS the episode (helper.py:560-569).
+    * An episode's final observation is never stored, so the last window of the newest episode reads row `idx` of
+      `_obs`: the next episode's first row, and in a buffer that is not yet full a row never written. The reference
+      allocates `_obs` with `torch.empty` (that row is garbage there); here `_obs` starts as zeros, so it is 0.
+
+    Pixels: the reference's pixel path cannot run (`sample` takes `.shape` of the `_last_obs` list and stacks frames
+    by `% cfg.episode_length`), so `cfg.modality != 'state'` is refused."""
+
+    def __init__(self, cfg):
+        if cfg.modality != "state":
+            raise NotImplementedError(f"RolloutBuffer: cfg.modality={cfg.modality!r} is not supported (the "
+                                      "reference's pixel path cannot run); only modality='state'")
+        self._alloc(cfg, cfg.buffer_shape, cfg.horizon, 0)
+        self._last_obs = []
+
+    def __add__(self, episode):
+        if len(episode) > self.capacity - self.idx and self.idx != 0:
+            # the reference's notice; the tail is masked and the episode is not stored
+            print("the replay buffer is full, and the sum of transition is :", self.idx)
+            self._priorities[self.idx:] = 0
+            self.idx = 0
+            self._full = True
+        else:
+            self.add(episode)
+        return self
+
+    def add(self, episode):
+        """helper.py:571-589. `episode`: `len(episode)` transitions in obs [>= len, *buffer_shape], action
+        [>= len, A], reward [>= len] (the reference `Episode`, or any object with those and `__len__`)."""
+        n = len(episode)
+        if n <= 0:
+            raise ValueError("empty episode")
+        if n > self.capacity - self.idx:
+            raise ValueError(f"episode of {n} transitions does not fit the {self.capacity - self.idx} left at "
+                             f"idx {self.idx} (capacity {self.capacity})")
+        obs = torch.as_tensor(episode.obs)
+        self._obs[self.idx:self.idx + n] = obs[:n].to(self.device)
+        # the reference appends every episode's final observation and never reads the list; it is bounded here (one
+        # row per episode, the newest `capacity` of them: no buffer holds more episodes than that)
+        self._last_obs.append(obs[-1].clone())
+        del self._last_obs[:-self.capacity]
+        self._action[self.idx:self.idx + n] = torch.as_tensor(episode.action)[:n].to(self.device)
+        self._reward[self.idx:self.idx + n] = torch.as_tensor(episode.reward)[:n].to(self.device)
+        self._add_priorities(n)
