@@ -29,7 +29,7 @@ The HIP path (the model on the GPU) orders one update for the device:
   * backward, `clip_grad_norm_19`, the optimiser step, the priority write-back, `update_pi` over the H + 1 latents.
 Nothing synchronises with the host; after `warmup` eager updates one update per buffer fill is captured into a HIP graph
 and replayed. The encoder, dynamics, reward, Q and pi MLPs run on PyTorch-ROCm autograd (float32 matmul precision
-pinned); moving them onto tdmpc_lg_gemm / tdmpc_lg_rows_* is the follow-up.
+pinned); tdmpc_amd/icem_engine.py runs the same update on tdmpc_lg_gemm / tdmpc_lg_rows_*, opt-in.
 
 The PyTorch path is the reference's own order of operations, call by call. It runs when the model is on the CPU
 (tests/test_icem_update_cpu.py holds it bit for bit to the restatement) and on the GPU with TDMPC_ICEM_LEARNER_HIP=0

@@ -10,9 +10,13 @@ construction order, so that its state_dict has the reference's keys, shapes and 
 `_predictor.*` plays no part in planning) and adds the reference's learning interface -- `update(replay_buffer, step)`,
 `update_pi(zs)`, `optim` / `pi_optim`, `reward_rms`, `explore_coef` (:267-428) -- run by
 `tdmpc_amd.icem_learner.IcemMlpLearner`, which is built on first use: an agent that only plans allocates none of it,
-and a cfg the learner refuses still constructs and plans.
+and a cfg the learner refuses still constructs and plans. `TdIcemMlp(cfg, engine=True)` or the environment variable
+TDMPC_ICEM_LEARNER_ENGINE=1 selects `tdmpc_amd.icem_engine.IcemEngineLearner` instead: the same update as explicit HIP
+passes over flat parameters, `optim` / `pi_optim` the engine's two Adam states.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -112,7 +116,9 @@ class TdIcemMlp(DssmLearning, TdICEM):
 
     LEARNER, LEARNER_MODULE = "IcemMlpLearner", "icem_learner"
 
-    def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", path: str = "auto", graph: bool = True):
+    def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", path: str = "auto", graph: bool = True,
+                 engine: bool = False):
+        self.use_engine = bool(engine)
         if getattr(cfg, "modality", "state") != "state":
             raise NotImplementedError("iCEM drop-in: state observations (the pixel DSSM encoder is rlpyt's)")
         if bool(getattr(cfg, "normalize", False)) and getattr(cfg, "norm_type", "ln") != "ln":
@@ -128,6 +134,15 @@ class TdIcemMlp(DssmLearning, TdICEM):
         self._elite_H = 0
         self.explore_coef = 0
         self._learner = None
+
+    @property
+    def learner(self):
+        """`IcemMlpLearner`, or with engine=True or TDMPC_ICEM_LEARNER_ENGINE=1 when it is first built
+        `icem_engine.IcemEngineLearner` (the update on the learner engine), which raises for a cfg or
+        a device it does not admit: the agent then still plans."""
+        if self._learner is None and (self.use_engine or os.environ.get("TDMPC_ICEM_LEARNER_ENGINE", "0") == "1"):
+            self.LEARNER, self.LEARNER_MODULE = "IcemEngineLearner", "icem_engine"
+        return DssmLearning.learner.fget(self)
 
     def update(self, replay_buffer, step, sync_metrics=True, noise=None):
         """:346-428 -> the reference's metrics dict (floats; sync_metrics=False: 0-d device tensors, no

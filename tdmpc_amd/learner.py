@@ -26,8 +26,9 @@ What the five learners share is here, once. `GraphLearner` is the base of all of
 `DssmLearner` and `DssmSimLearner`; icem_learner's `IcemMlpLearner`; sim_learner's `SimLearner`): device, dtype and the
 two optimisers; the warm-up / capture / replay driver with its CPU escape; `_optimize` (the 1 / horizon hook, backward,
 `clip_grad_norm_19`, the optimiser step), `_finish` (priorities, `update_pi`, `last`, the metrics in METRICS order) and
-`_update_pi` (the batched or the looped body, with or without rho). `EngineLearner(GraphLearner)` is the base of `Learner`
-and `SimLearner` and owns everything done with an engine: choosing it or the optimisers, `td_target`, the engine branch
+`_update_pi` (the batched or the looped body, with or without rho). `EngineLearner(GraphLearner)` is the base of `Learner`,
+`SimLearner` and icem_engine's `IcemEngineLearner` (which has the engine path only) and owns everything done with an
+engine: choosing it or the optimisers, `td_target`, the engine branch
 of `step` with the planner's live repack, `ema`, and dropping a pack the planner made before the engine moved the
 parameters into its flat buffer (a `plan()` ahead of the first `update()`, the reference's train.py order: without the
 drop the planner stays on the old storages for good). The cfg-check clauses the learners' `check_*_cfg`
@@ -338,11 +339,14 @@ class EngineLearner(GraphLearner):
     ENGINE_CLASS = None
     _torch_optimizers = GraphLearner._optimizers
 
+    def _use_engine(self):
+        return self.on_gpu and self.ENGINE.supported(self.cfg) and os.environ.get(self.ENGINE_ENV, "1") != "0"
+
     def _optimizers(self):
         """Build the engine where it applies (`engine`, `path`) -> its two Adam states, or the PyTorch optimisers."""
         self.engine = None
         self._live_pack = False   # the last update repacked the planner's weights itself (repack_live)
-        if self.on_gpu and self.ENGINE.supported(self.cfg) and os.environ.get(self.ENGINE_ENV, "1") != "0":
+        if self._use_engine():
             self.engine = getattr(self.ENGINE, self.ENGINE_CLASS)(self.agent)
             planner = getattr(self.agent, "planner", None)
             if planner is not None:

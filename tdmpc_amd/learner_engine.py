@@ -73,8 +73,8 @@ class _Adam:
 
 class Engine:
     # hooks of the engines built on this one (tdmpc_amd/sim_engine.py): the flat layout's module order, the tensors it
-    # holds, the policy optimiser's learning rate, and in `update` the encoder's passes, the loss and further weight
-    # gradients
+    # holds, the policy optimiser's learning rate, and in `update` the TD pass's share of the batch, the encoder's
+    # passes, the loss and further weight gradients
     ORDER = ("_encoder", "_dynamics", "_reward", "_Q1", "_Q2", "_pi")
 
     def _tensors(self, model):
@@ -570,7 +570,7 @@ class Engine:
             obs = self.agent.aug(obs if obs.dtype == torch.float32 else obs.float(), div=255.0).contiguous()
         else:
             obs = obs.contiguous()
-            nxo_t = next_obses[:H].contiguous()
+            nxo_t = self._td_obs(b, next_obses, action, reward)
         rew_t = reward[:H].contiguous()
         weights = weights.contiguous()
         if noise is None:
@@ -706,6 +706,11 @@ class Engine:
             dw_enc = [("_encoder.2", L, E, [_seg(_p(DZ0), L, _p(b["Ye1"]), E, B, 1, 1, E)], 1),
                       ("_encoder.0", E, O, [_seg(_p(b["dP1e"]), E, _p(obs), O, B, 1, 1, O)], 1)]
         return dw_enc, conv
+
+    def _td_obs(self, b, next_obses, action, reward):
+        """The state observations `_td_steps` encodes: the H next observations of the TD targets. An engine whose TD
+        pass reads more of the batch keeps it in `b` here."""
+        return next_obses[:self.H].contiguous()
 
     def _main_dw_extra(self, b, B, sp):
         """Further weight-gradient jobs (name, out, in, segments, splits) of the `main` grouped launch."""

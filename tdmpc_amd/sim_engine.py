@@ -101,7 +101,8 @@ class SimEngine(Engine):
             heads.append(h)
         return heads
 
-    def _enc_td_steps(self, b, nxo_t, R):
+    def _enc_td_steps(self, b, nxo_t, R, z2=None):
+        """z2: a dense [R, L] second copy of the online latents (an engine built on this one: icem_engine.py)."""
         O, E, L, LAP = self.O, self.E, self.L, self.LAP
         w, wt = self.w, (lambda k: self.w(k, True))
         nxo = _p(nxo_t)
@@ -115,10 +116,11 @@ class SimEngine(Engine):
         self.gemm([dict(segs=[_seg(_p(b["Yt1"]), E, wt("_encoder.3.weight"), E, E)], m=R, n=L, c=_p(b["NZ"]),
                         ldc=L, bias=wt("_encoder.3.bias")),
                    dict(segs=[_seg(_p(b["Yo1"]), E, w("_encoder.3.weight"), E, E)], m=R, n=L, c=_p(b["Xtd"]),
-                        ldc=LAP, bias=w("_encoder.3.bias"))])
+                        ldc=LAP, bias=w("_encoder.3.bias"), c2=z2, ldc2=L)])
         yield
 
-    def _enc_fwd_steps(self, b, obs, B):
+    def _enc_fwd_steps(self, b, obs, B, z2=None):
+        """z2: a dense [B, L] second copy of z_0."""
         O, E, L, LAP = self.O, self.E, self.L, self.LAP
         w = self.w
         self.gemm([dict(segs=[_seg(_p(obs), O, w("_encoder.0.weight"), O, O)], m=B, n=E, c=_p(b["Pe1"]), ldc=E,
@@ -127,7 +129,7 @@ class SimEngine(Engine):
         self.rows(self._ln_heads([(b["Pe1"], b["Ye1"], False)], grad=(b["XHe"], b["RSe"])), B, m=E)
         yield
         self.gemm([dict(segs=[_seg(_p(b["Ye1"]), E, w("_encoder.3.weight"), E, E)], m=B, n=L, c=_p(b["X0"]),
-                        ldc=LAP, bias=w("_encoder.3.bias"))])
+                        ldc=LAP, bias=w("_encoder.3.bias"), c2=z2, ldc2=L)])
         yield
 
     def _enc_bwd(self, b, obs, B):

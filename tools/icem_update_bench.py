@@ -1,7 +1,8 @@
 """Time of the MLP iCEM agent's update on one MI355X: the segmented intrinsic-reward pass against one-segment calls, and
-the whole `IcemMlpLearner` update on its HIP path against its PyTorch path on the same GPU.
+the whole `IcemMlpLearner` update on its HIP path against its PyTorch path and against the learner engine
+(`icem_engine.IcemEngineLearner`) on the same GPU.
 
-    python tools/icem_update_bench.py [--out profiles/r11/icem_update_bench.json] [--reps 7] [--calls 20]   (--out '' writes no file)
+    python tools/icem_update_bench.py [--out profiles/r14/icem_engine_bench.json] [--reps 7] [--calls 20]   (--out '' writes no file)
 
 The humanoid shape (L 100, A 21, mlp_dim 512), B = 512, H = 5, weights synthetic_icem_mlp_state_dict seeds 0 / 1, a
 fixed batch:
@@ -10,7 +11,8 @@ fixed batch:
               compared bitwise before timing.
   update:     `IcemMlpLearner.update` on the HIP path, eagerly launched and as graph replay, against the same class
               built with TDMPC_ICEM_LEARNER_HIP=0 (the reference's order of operations on PyTorch-ROCm, eagerly launched
-              and as graph replay). The parent commit has no update to compare with.
+              and as graph replay), and against `IcemEngineLearner.update` (engine_eager / engine_graph: the same
+              update as explicit HIP passes over flat parameters), all legs in the same process and the same rounds.
 Per leg and side: a warm-up, then `reps` timed batches of `calls` calls between HIP events, the sides alternating batch
 by batch; the median is the figure, min / max the spread. No GPU: it fails.
 """
@@ -116,9 +118,24 @@ def learner(cfg, hip, graph):
     return ln, update
 
 
+def engine_learner(cfg, graph):
+    from tdmpc_amd.icem_engine import IcemEngineLearner
+    model, target = models(cfg)
+    agent = SimpleNamespace(cfg=cfg, model=model, model_target=target, device=torch.device("cuda"), planner=None)
+    ln = IcemEngineLearner(agent, graph=graph, warmup=3)
+    assert ln.path == "engine"
+    buf = FixedBatch(cfg)
+    count = [0]
+
+    def update():
+        count[0] += 1
+        return ln.update(buf, 100000 + count[0])
+    return ln, update
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "r11", "icem_update_bench.json"))
+    ap.add_argument("--out", default=os.path.join("profiles", "r14", "icem_engine_bench.json"))
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--calls", type=int, default=20)
     args = ap.parse_args()
@@ -167,10 +184,16 @@ def main():
     for name, hip, graph in (("hip_eager", True, False), ("hip_graph", True, True), ("torch_eager", False, False),
                              ("torch_graph", False, True)):
         learners[name], sides[name] = learner(cfg, hip, graph)
+    for name, graph in (("engine_eager", False), ("engine_graph", True)):
+        learners[name], sides[name] = engine_learner(cfg, graph)
     res = alternate(sides, args.reps, args.calls)
-    for name in ("hip_graph", "torch_graph"):
+    for name in ("hip_graph", "torch_graph", "engine_graph"):
         assert learners[name]._graphs, f"{name}: never replayed a captured graph"
     out["update"] = {**res,
+                     "hip_eager_over_engine_eager": round(res["hip_eager"]["us_median"] /
+                                                          res["engine_eager"]["us_median"], 3),
+                     "hip_graph_over_engine_graph": round(res["hip_graph"]["us_median"] /
+                                                          res["engine_graph"]["us_median"], 3),
                      "torch_eager_over_hip_eager": round(res["torch_eager"]["us_median"] /
                                                          res["hip_eager"]["us_median"], 3),
                      "torch_graph_over_hip_graph": round(res["torch_graph"]["us_median"] /
