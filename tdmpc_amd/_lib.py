@@ -47,12 +47,16 @@ EXPORTED = ("tdmpc_abi_version", "tdmpc_sizes_for", "tdmpc_noise_floats", "tdmpc
             "tdmpc_icem_loss_forward", "tdmpc_icem_loss_backward",
             # include/tdmpc_sim_learner.h
             "tdmpc_sim_learner_version", "tdmpc_sim_loss_forward", "tdmpc_sim_loss_backward",
-            "tdmpc_sim_bn_part_floats", "tdmpc_sim_bn_fwd", "tdmpc_sim_bn_bwd", "tdmpc_sim_cos_fwd", "tdmpc_sim_cos_bwd")
+            "tdmpc_sim_bn_part_floats", "tdmpc_sim_bn_fwd", "tdmpc_sim_bn_bwd", "tdmpc_sim_cos_fwd", "tdmpc_sim_cos_bwd",
+            # include/tdmpc_drnn_engine.h
+            "tdmpc_drnn_engine_version", "tdmpc_drnn_gate_part_floats", "tdmpc_drnn_gate_fwd", "tdmpc_drnn_gate_bwd")
 DRNN_VERSION = 2
 DRNN_TRAIN_VERSION = 1
 ICEM_LEARNER_VERSION = 1
 ICEM_DYN_TENSORS = 6   # include/tdmpc_icem_learner.h
 SIM_LEARNER_VERSION = 1
+DRNN_ENGINE_VERSION = 1
+DRNN_GATE_PART_ROWS = 32   # include/tdmpc_drnn_engine.h
 DT_NEXT_TENSORS, DT_LOSS_TENSORS, DT_MAX_ROWS = 22, 8, 4096   # include/tdmpc_drnn_learner.h
 NOISE_MAX_JOBS, NOISE_MAX_SPECTRA = 17, 4
 
@@ -313,6 +317,9 @@ def lib():
     L.tdmpc_sim_bn_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.tdmpc_sim_cos_fwd.argtypes = [vp, vp, vp, i32, i32, vp]
     L.tdmpc_sim_cos_bwd.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+    L.tdmpc_drnn_gate_part_floats.argtypes = [i32, i32, C.POINTER(sz)]
+    L.tdmpc_drnn_gate_fwd.argtypes = [vp, vp, vp, pv, vp, vp, vp, vp, i32, i32, vp]
+    L.tdmpc_drnn_gate_bwd.argtypes = [vp, vp, vp, pv, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     for name in EXPORTED:
         if not hasattr(L, name) and not (name.startswith("tdmpc_debug_") and os.environ.get("TDMPC_LIB_PATH")):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")

@@ -31,7 +31,8 @@
 //     the 1 / horizon hook, for the MLP iCEM agent's update.
 // predictor_fwd is `_predictor` and the cosine loss behind every similarity loss and intrinsic-reward pass.
 // The MLP iCEM agent's update (TdICemSimMlp.update) is icem_learner.inc, included at the end; after it
-// sim_learner.inc, the similarity TD-MPC agent's (TDMPCSIM.update).
+// sim_learner.inc, the similarity TD-MPC agent's (TDMPCSIM.update); last drnn_engine.inc, the gate
+// kernels as entry points of their own for an engine that issues the step's products itself.
 // Every reduction runs in a fixed order: wave butterflies, LDS sums over waves in wave order, partials in index order.
 #include <hip/hip_runtime.h>
 
@@ -42,6 +43,7 @@
 
 #include <algorithm>
 
+#include "../../include/tdmpc_drnn_engine.h"
 #include "../../include/tdmpc_drnn_learner.h"
 #include "../../include/tdmpc_icem_learner.h"
 #include "../../include/tdmpc_learner.h"
@@ -164,6 +166,9 @@ __device__ __forceinline__ void ln_row_bwd(const float (&dy)[4], const float (&x
 // Backward of the cell: dhn [R,Hd] = dL/dh' -> dgi, dgh [R,3Hd] (w.r.t. weight_ih / weight_hh's outputs), dhd [R,Hd]
 // (the direct (1 - update) path to h) and part [nwg][6][Hd]: the workgroup's sums over its GROWS rows of the three
 // LayerNorms' (dweight, dbias). Wave w takes rows base + w, base + w + 4, ...; the four waves add in wave order.
+// ZH: the hidden state was zero (dt_gate_fwd<true>): a.gh and a.h are not read, a.dgh and a.dhd not written; newval_h = 0
+// leaves the reset gate without gradient (dgi's reset third and ln_reset's partials are zero).
+template <bool ZH>
 __global__ void __launch_bounds__(256) dt_gate_bwd(const GateArgs a) {
     __shared__ float red[4][6][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, Hd = a.Hd;
@@ -194,9 +199,9 @@ __global__ void __launch_bounds__(256) dt_gate_bwd(const GateArgs a) {
             xr[i] = a.lnx[r3 + cc];
             xu[i] = a.lnx[r3 + Hd + cc];
             xn[i] = a.lnx[r3 + 2 * Hd + cc];
-            ghn[i] = a.gh[r3 + 2 * Hd + cc];
+            ghn[i] = ZH ? 0.f : a.gh[r3 + 2 * Hd + cc];
             dH[i] = a.dhn[r1 + cc];
-            hp[i] = a.h[r1 + cc];
+            hp[i] = ZH ? 0.f : a.h[r1 + cc];
         }
         float dyn[4], dyu[4], dyr[4], dsn[4], dsu[4], dsr[4];
 #pragma unroll
@@ -208,16 +213,22 @@ __global__ void __launch_bounds__(256) dt_gate_bwd(const GateArgs a) {
         ln_row_bwd(dyu, xu, g[1], ok, rstd_u, Hd, dsu, acc[2], acc[3]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) dyr[i] = dsn[i] * ghn[i] * r[i] * (1.f - r[i]);
-        ln_row_bwd(dyr, xr, g[0], ok, rstd_r, Hd, dsr, acc[0], acc[1]);
+        if (ZH) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dsr[i] = 0.f;
+        } else {
+            ln_row_bwd(dyr, xr, g[0], ok, rstd_r, Hd, dsr, acc[0], acc[1]);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = lane + 64 * i;
             if (!ok[i]) continue;
             a.dgi[r3 + c] = dsr[i];
-            a.dgh[r3 + c] = dsr[i];
             a.dgi[r3 + Hd + c] = dsu[i];
-            a.dgh[r3 + Hd + c] = dsu[i];
             a.dgi[r3 + 2 * Hd + c] = dsn[i];
+            if (ZH) continue;
+            a.dgh[r3 + c] = dsr[i];
+            a.dgh[r3 + Hd + c] = dsu[i];
             a.dgh[r3 + 2 * Hd + c] = dsn[i] * r[i];
             a.dhd[r1 + c] = dH[i] * (1.f - u[i]);
         }
@@ -1484,7 +1495,7 @@ int tdmpc_drnn_next_bwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t n_
     g.gate = S.gate; g.lnx = S.lnx; g.lnr = S.lnr;
     g.dhn = W.dhn; g.dgi = W.dgi; g.dgh = W.dgh; g.dhd = W.dhd; g.part = W.lnpart;
     g.rows = R; g.Hd = Hd;
-    hipLaunchKernelGGL(dt_gate_bwd, dim3(gate_wgs(R)), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(dt_gate_bwd<false>, dim3(gate_wgs(R)), dim3(256), 0, st, g);
     if (int rc = launched("gate_bwd")) return rc;
     FinishArgs f;
     memset(&f, 0, sizeof f);
@@ -1544,3 +1555,4 @@ int tdmpc_drnn_simloss_bwd(const tdmpc_drnn_dims* dims, float* const* T, int32_t
 
 #include "icem_learner.inc"
 #include "sim_learner.inc"
+#include "drnn_engine.inc"

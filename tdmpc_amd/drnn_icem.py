@@ -22,9 +22,13 @@ with one normal_, the spectrum normals with another and turns them into every co
 Learning: `update(replay_buffer, step)`, `update_pi(zs)`, `optim` / `pi_optim`, `explore_coef` and `reward_rms` as the
 reference's (:367-384, :421-553), run by `tdmpc_amd.drnn_learner.DssmLearner` through `tdmpc_amd.drnn.DssmLearning`,
 which builds it on first use (an agent that only plans allocates none of it, and a cfg the learner refuses -- the dog
-task's batch of 2048 -- still plans).
+task's batch of 2048 -- still plans). Opt-in, `TdIcemDrnn(cfg, engine=True)` or TDMPC_DSSM_LEARNER_ENGINE=1 when the
+learner is first built: `tdmpc_amd.dssm_engine.DssmEngineLearner`, the same update on the explicit learner engine
+(DESIGN.md §7 f14). `TdMpcDrnn` does not read the variable.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -88,7 +92,8 @@ class TdIcemDrnn(DssmLearning, Agent):
     RNGS = ("reference", "device")
     HIDDEN = True
 
-    def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", graph: bool = True):
+    def __init__(self, cfg, max_batch: int = 1, rng: str = "reference", graph: bool = True, engine: bool = False):
+        self.use_engine = bool(engine)
         check_dssm_cfg(cfg)
         if not 1 <= int(cfg.iterations) <= 16:
             raise ValueError("iCEM: 1..16 iterations")
@@ -111,6 +116,15 @@ class TdIcemDrnn(DssmLearning, Agent):
         self._learner = None
 
     # ------------------------------------------------------------------ learning (:367-384, :421-553)
+    @property
+    def learner(self):
+        """`DssmLearner`, or with engine=True or TDMPC_DSSM_LEARNER_ENGINE=1 when it is first built
+        `dssm_engine.DssmEngineLearner` (the update on the learner engine), which raises for a cfg or
+        a device it does not admit: the agent then still plans."""
+        if self._learner is None and (self.use_engine or os.environ.get("TDMPC_DSSM_LEARNER_ENGINE", "0") == "1"):
+            self.LEARNER, self.LEARNER_MODULE = "DssmEngineLearner", "dssm_engine"
+        return DssmLearning.learner.fget(self)
+
     def update(self, replay_buffer, step, sync_metrics=True, noise=None):
         """:445-553 -> the reference's metrics dict (floats; sync_metrics=False: 0-d device tensors, no
         synchronisation). noise: optional 2H + 1 [B, A] TruncatedNormal draws (parity tests)."""

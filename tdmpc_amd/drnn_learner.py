@@ -28,7 +28,8 @@ warm-up steps come between the encoders and the intrinsic rewards, takes its two
 Nothing synchronises with the host. After `warmup` eager updates one update per (buffer.idx, buffer._full) is captured
 into a HIP graph and replayed by `learner.GraphLearner`, the base shared with the TOLD learner; the explore coefficient
 changes every step, so it lives in a device scalar that `update` writes before each replay. The encoder, Q and pi MLPs
-run on PyTorch-ROCm autograd here (float32 matmul precision pinned); moving them onto tdmpc_lg_gemm / tdmpc_lg_rows_* is the follow-up.
+run on PyTorch-ROCm autograd here (float32 matmul precision pinned); `dssm_engine.DssmEngineLearner` is the same update
+on tdmpc_lg_gemm / tdmpc_lg_rows_* without autograd, opt-in.
 
 The PyTorch path is the reference's own order of operations, call by call, in plain PyTorch. It runs when the model is on
 the CPU (tests/test_drnn_update_cpu.py holds it bit for bit to the restatement) and on the GPU with

@@ -74,17 +74,26 @@ def reason(cfg):
 
 
 class IcemEngine(SimEngine):
+    # hooks of the engine built on this one (tdmpc_amd/dssm_engine.py): what refuses a cfg, and the intrinsic pass's
+    # entry points, dims and dynamics pointer table
+    REASON = staticmethod(reason)
+    INTRINSIC = "tdmpc_icem_intrinsic"   # <INTRINSIC>_workspace_floats, <INTRINSIC>_fwd
+
+    def _intrinsic_setup(self):
+        """-> (the intrinsic pass's dims, its dynamics pointer table over the flat views)."""
+        if self.lib.tdmpc_icem_learner_version() != _lib.ICEM_LEARNER_VERSION:
+            raise RuntimeError("libtdmpc_hip: tdmpc_icem_learner_version mismatch")
+        return (_lib.dims_from_cfg(self.cfg, enc_norm=True),
+                (C.c_void_p * len(DYN_PARAMS))(*[self.w(k) for k in DYN_PARAMS]))
+
     def __init__(self, agent):
-        why = reason(agent.cfg)
+        why = self.REASON(agent.cfg)
         if why is not None:
             raise ValueError(why)
         super().__init__(agent)
-        if self.lib.tdmpc_icem_learner_version() != _lib.ICEM_LEARNER_VERSION:
-            raise RuntimeError("libtdmpc_hip: tdmpc_icem_learner_version mismatch")
         self.rho = torch.ones(self.H + 1, dtype=torch.float32, device=self.dev)   # update_pi: no rho ** t (:267-284)
-        self.dims = _lib.dims_from_cfg(self.cfg, enc_norm=True)
+        self.dims, self.dtab = self._intrinsic_setup()
         w = self.w
-        self.dtab = (C.c_void_p * len(DYN_PARAMS))(*[w(k) for k in DYN_PARAMS])
         loss = [w(k) for k in LOSS_PARAMS]
         # (the BatchNorm's running statistics follow its weight and bias, include/tdmpc_icem_learner.h)
         loss[4:4] = [_p(self.bn_mean), _p(self.bn_var)]
@@ -101,7 +110,7 @@ class IcemEngine(SimEngine):
             S = H + 1
             z = lambda *s: torch.zeros(*s, device=self.dev)  # noqa: E731
             n = C.c_size_t()
-            _lib.call("tdmpc_icem_intrinsic_workspace_floats", self.dims, S, B, C.byref(n))
+            _lib.call(self.INTRINSIC + "_workspace_floats", self.dims, S, B, C.byref(n))
             b.update(
                 # both encoders over all H + 1 next observations
                 Pt1=z(S * B, E), Po1=z(S * B, E), Yt1=z(S * B, E), Yo1=z(S * B, E), NZ=z(S * B, L), Xtd=z(S * B, LAP),
@@ -134,7 +143,7 @@ class IcemEngine(SimEngine):
             yield
         torch.cuda.current_stream(self.dev).wait_event(self._z0)
         ws = b["iws"]
-        _lib.call("tdmpc_icem_intrinsic_fwd", self.dims, self.dtab, len(self.dtab), self.ltab, len(self.ltab), b["ZI"],
+        _lib.call(self.INTRINSIC + "_fwd", self.dims, self.dtab, len(self.dtab), self.ltab, len(self.ltab), b["ZI"],
                   b["act"], b["NZ"], S, B, b["iloss"], ws, ws.numel(), st())
         yield
         _lib.call("tdmpc_drnn_intrinsic_finish", b["iloss"], S * B, self.rms, self.coef, b["rew"], b["intrinsic"],

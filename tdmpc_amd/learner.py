@@ -27,7 +27,7 @@ What the five learners share is here, once. `GraphLearner` is the base of all of
 two optimisers; the warm-up / capture / replay driver with its CPU escape; `_optimize` (the 1 / horizon hook, backward,
 `clip_grad_norm_19`, the optimiser step), `_finish` (priorities, `update_pi`, `last`, the metrics in METRICS order) and
 `_update_pi` (the batched or the looped body, with or without rho). `EngineLearner(GraphLearner)` is the base of `Learner`,
-`SimLearner` and icem_engine's `IcemEngineLearner` (which has the engine path only) and owns everything done with an
+`SimLearner`, icem_engine's `IcemEngineLearner` and dssm_engine's `DssmEngineLearner` (which have the engine path only) and owns everything done with an
 engine: choosing it or the optimisers, `td_target`, the engine branch
 of `step` with the planner's live repack, `ema`, and dropping a pack the planner made before the engine moved the
 parameters into its flat buffer (a `plan()` ahead of the first `update()`, the reference's train.py order: without the

@@ -429,8 +429,9 @@ class Engine:
                             ldc=LAP, bias=w("_encoder.2.bias"))])
             yield
 
-    def _td_head_steps(self, b, rew, R, eps):
-        """The online policy and the target Q heads on b["Xtd"] -> b["TD"] (tdmpc.py:184-190)."""
+    def _td_head_steps(self, b, rew, R, eps, gamma=None):
+        """The online policy and the target Q heads on b["Xtd"] -> b["TD"] = rew + gamma min(Q1', Q2') (tdmpc.py:184-190;
+        gamma: cfg.discount unless given)."""
         L, A, M, LA, LAP = self.L, self.A, self.M, self.LA, self.LAP
         w, wt = self.w, (lambda k: self.w(k, True))
         self.prod([([(b["Xtd"][:, :L], 0, L)], "_pi.0.weight", b["T1"], "_pi.0.bias", False, False, EPI_ELU, None)])
@@ -453,7 +454,8 @@ class Engine:
         yield
         self.rows([dict(x=_p(PA[h]), ln=1, g=wt(f"_Q{h + 1}.4.weight"), beta=wt(f"_Q{h + 1}.4.bias"), act=ELU,
                         tail=1, w3=wt(f"_Q{h + 1}.6.weight"), b3=wt(f"_Q{h + 1}.6.bias"), out=_p(b["TQ"][h]))
-                   for h in range(2)], R, reward=rew, td=_p(b["TD"]), gamma=float(self.cfg.discount))
+                   for h in range(2)], R, reward=rew, td=_p(b["TD"]),
+                  gamma=float(self.cfg.discount if gamma is None else gamma))
 
     def _fwd_steps(self, b, obs, action, B):
         """The update's forward (tdmpc.py:199-213): encoder, latent rollout, heads over the H B rollout rows. A
@@ -464,6 +466,7 @@ class Engine:
         yield from self._enc_fwd_steps(b, obs, B)
         X0.view(H + 1, B, LAP)[:H, :, L:LA].copy_(action[:H])
         yield
+        yield from self._rollout_fwd_steps(b, B)
         yield from self._head_fwd_steps(b, B)
 
     def _enc_fwd_steps(self, b, obs, B):
@@ -485,10 +488,9 @@ class Engine:
                             bias=w("_encoder.2.bias"))])
             yield
 
-    def _head_fwd_steps(self, b, B):
-        """The latent rollout from z_0 and the Q / reward heads over its H B rows."""
+    def _rollout_fwd_steps(self, b, B):
+        """The latent rollout from z_0: step t writes z_{t+1} into block t + 1 of b["X0"] and into b["ZP"]."""
         H, L, M, LA, LAP = self.H, self.L, self.M, self.LA, self.LAP
-        R = H * B
         w, X0 = self.w, b["X0"]
         for t in range(H):
             self.gemm([dict(segs=[_seg(_p(X0, t * B * LAP), LAP, w("_dynamics.0.weight"), LA, LA)], m=B, n=M,
@@ -501,10 +503,20 @@ class Engine:
                             c=_p(X0, (t + 1) * B * LAP), ldc=LAP, bias=w("_dynamics.4.bias"),
                             c2=_p(b["ZP"], t * B * L), ldc2=L)])
             yield
+
+    def _reward_in(self, b, R):
+        """The reward head's input over the R rollout rows as prod() parts: (z_t, a_t)."""
+        return [(b["X0"][:R, :self.LA], 0, self.LA)]
+
+    def _head_fwd_steps(self, b, B):
+        """The Q / reward heads over the rollout's H B rows."""
+        H, L, M, LA, LAP = self.H, self.L, self.M, self.LA, self.LAP
+        R = H * B
+        w, X0 = self.w, b["X0"]
         # reward head layer 1 (ELU) rides in its own slot 2 of PA / Y2 buffers, in the Q heads' first-layer launch
         PA = b["PA"]
         PA, PB, Y1, Y2, XH1, XH2, RS1, RS2 = self.q_forward(
-            b, R, [(X0[:R, :LA], 0, LA)], extra=[([(X0[:R, :LA], 0, LA)], "_reward.0.weight", PA[2, :R], "_reward.0.bias",
+            b, R, [(X0[:R, :LA], 0, LA)], extra=[(self._reward_in(b, R), "_reward.0.weight", PA[2, :R], "_reward.0.bias",
                                               False, False, EPI_ELU, None)])
         yield
         self.prod([([(Y1[h, :R], 0, M)], f"_Q{h + 1}.3.weight", PB[h, :R], f"_Q{h + 1}.3.bias", False, False,
@@ -612,13 +624,12 @@ class Engine:
         # gradient of z_t from the three heads (+ the consistency term on z_t): S = sum_h dP1_h W1_h[:, :L] + dZP
         S, dZP = b["S"], b["dZP"]
         self.gemm([dict(segs=[_seg(_p(dP1[0]), M, w("_Q1.0.weight"), LA, M, bmode=1),
-                              _seg(_p(dP1[1]), M, w("_Q2.0.weight"), LA, M, bmode=1),
-                              _seg(_p(dP1[2]), M, w("_reward.0.weight"), LA, M, bmode=1)],
+                              _seg(_p(dP1[1]), M, w("_Q2.0.weight"), LA, M, bmode=1)] + self._reward_dz_segs(b),
                          m=R, n=L, c=_p(S), ldc=L, res=_p(dZP), ldres=L)])
         # ---- the heads' weight gradients (side stream) beside the latent rollout's backward ----
         sp = 4 if R >= 1024 else 1
         dw_h = [("_reward.2", M, M, [_seg(_p(dP2[2]), M, _p(PA[2]), M, R, 1, 1, M)], sp),
-                ("_reward.0", M, LA, [_seg(_p(dP1[2]), M, _p(X0), self.LAP, R, 1, 1, LA)], sp)]
+                self._reward0_dw(b, R, sp)]
         for h in range(2):
             dw_h += [(f"_Q{h + 1}.3", M, M, [_seg(_p(dP2[h]), M, _p(Y1[h]), M, R, 1, 1, M)], sp),
                      (f"_Q{h + 1}.0", M, LA, [_seg(_p(dP1[h]), M, _p(X0), self.LAP, R, 1, 1, LA)], sp)]
@@ -636,13 +647,7 @@ class Engine:
         dw_enc, conv = self._enc_bwd(b, obs, B)
 
         # ---- the rollout's weight gradients (one grouped launch) ----
-        g_dyn3 = ([_seg(_p(DG), L, _p(b["Yd2"]), M, R - B, 1, 1, M)] if H > 1 else []) + \
-            [_seg(_p(dZP, H * B * L), L, _p(b["Yd2"], (H - 1) * B * M), M, B, 1, 1, M)]
-        dw = dw_enc + [
-              ("_dynamics.4", L, M, g_dyn3, sp),
-              ("_dynamics.2", M, M, [_seg(_p(dP2d), M, _p(b["Yd1"]), M, R, 1, 1, M)], sp),
-              ("_dynamics.0", M, LA, [_seg(_p(dP1d), M, _p(X0), self.LAP, R, 1, 1, LA)], sp)] + \
-            self._main_dw_extra(b, B, sp)
+        dw = dw_enc + self._rollout_dw(b, B, sp) + self._main_dw_extra(b, B, sp)
         slots.update(self._dw(b, "main", dw))
         main.wait_stream(self.side)   # the heads' slices ready
         dw += dw_h
@@ -707,6 +712,29 @@ class Engine:
                       ("_encoder.0", E, O, [_seg(_p(b["dP1e"]), E, _p(obs), O, B, 1, 1, O)], 1)]
         return dw_enc, conv
 
+    def _reward_dz_segs(self, b):
+        """The reward head's share of the heads' gradient of z_t, as segments of that product."""
+        return [_seg(_p(b["dP1"][2]), self.M, self.w("_reward.0.weight"), self.LA, self.M, bmode=1)]
+
+    def _reward0_dw(self, b, R, sp):
+        """The weight-gradient job of the reward head's first layer."""
+        return ("_reward.0", self.M, self.LA, [_seg(_p(b["dP1"][2]), self.M, _p(b["X0"]), self.LAP, R, 1, 1, self.LA)],
+                sp)
+
+    def _last_step_segs(self, b, B, x):
+        """dY of the rollout's last layer over all steps' rows against its input x [H B, M]: b["DG"] holds d z_{t+1} of
+        steps 0 .. H - 2, the last block of b["dZP"] that of step H - 1."""
+        H, L, M, R = self.H, self.L, self.M, self.H * B
+        return ([_seg(_p(b["DG"]), L, _p(x), M, R - B, 1, 1, M)] if H > 1 else []) + \
+            [_seg(_p(b["dZP"], H * B * L), L, _p(x, (H - 1) * B * M), M, B, 1, 1, M)]
+
+    def _rollout_dw(self, b, B, sp):
+        """The rollout's weight-gradient jobs of the `main` grouped launch."""
+        M, LA, R = self.M, self.LA, self.H * B
+        return [("_dynamics.4", self.L, M, self._last_step_segs(b, B, b["Yd2"]), sp),
+                ("_dynamics.2", M, M, [_seg(_p(b["dP2d"]), M, _p(b["Yd1"]), M, R, 1, 1, M)], sp),
+                ("_dynamics.0", M, LA, [_seg(_p(b["dP1d"]), M, _p(b["X0"]), self.LAP, R, 1, 1, LA)], sp)]
+
     def _td_obs(self, b, next_obses, action, reward):
         """The state observations `_td_steps` encodes: the H next observations of the TD targets. An engine whose TD
         pass reads more of the batch keeps it in `b` here."""
@@ -717,7 +745,8 @@ class Engine:
         return []
 
     def _src_extra(self, b):
-        """Further tdmpc_lg_finalize sources {tensor: (ptr, rows, cols, ld, slices, slice stride)}."""
+        """Further tdmpc_lg_finalize sources {tensor: (ptr, rows, cols, ld, slices, slice stride[, the tensors that
+        follow it in the flat layout and in the source: `_optimise`])}."""
         return {}
 
     def _dw(self, b, tag, dw):
@@ -738,9 +767,16 @@ class Engine:
         names.sort(key=lambda k: self.off[k][0])
         arr = (_lib.LgGsrc * len(names))()
         for i, k in enumerate(names):
-            p, rows, cols, ld, ns, ss = src[k]
+            p, rows, cols, ld, ns, ss, *also = src[k]
             o, shape = self.off[k]
-            assert rows * cols == int(torch.Size(shape).numel()), k
+            # a source may cover further tensors that follow this one without a gap in the flat layout (src[k][6]: their
+            # names), where its slices hold them side by side: one tdmpc_lg_finalize tensor (it takes at most 48)
+            end = o + int(torch.Size(shape).numel())
+            for k2 in (also[0] if also else ()):
+                o2, shape2 = self.off[k2]
+                assert o2 == end and k2 not in src, (k, k2)
+                end += int(torch.Size(shape2).numel())
+            assert rows * cols == end - o, k
             T = arr[i]
             T.src, T.dst, T.sstride, T.rows, T.cols, T.ld, T.nslices = p, o - opt.lo, ss, rows, cols, ld, ns
         assert self.off[names[0]][0] == opt.lo

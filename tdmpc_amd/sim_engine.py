@@ -143,13 +143,12 @@ class SimEngine(Engine):
                 ("_encoder.0", E, O, [_seg(_p(b["dP1e"]), E, _p(obs), O, B, 1, 1, O)], 1)], {}
 
     # ------------------------------------------------------------------------------------------- the similarity head
-    def _loss(self, b, rew, weights, B):
-        """`_predictor` + cosine over b["ZP"] against b["NZ"], the loss composition and their backward -> b["lrows"],
-        b["scal"], b["dq"], and the queries' gradient in b["dZP"][B L:]."""
-        cfg, H, L, M, Q = self.cfg, self.H, self.L, self.M, b["Q"]
+    def _sim_fwd(self, b, B):
+        """`_predictor` + cosine over b["ZP"] against b["NZ"] -> b["sim"] [H B]."""
+        H, L, M = self.H, self.L, self.M
         R = H * B
         w, st, lib = self.w, self._stream(), self.lib
-        ZP, NZ, dq = b["ZP"], b["NZ"], b["dq"]
+        ZP, NZ = b["ZP"], b["NZ"]
         self.gemm([dict(segs=[_seg(_p(ZP), L, w("_predictor.0.weight"), L, L)], m=R, n=M, c=_p(b["SP1"]), ldc=M,
                         bias=w("_predictor.0.bias"))])
         _lib.check(lib.tdmpc_sim_bn_fwd(_p(b["SP1"]), w("_predictor.1.weight"), w("_predictor.1.bias"),
@@ -158,12 +157,27 @@ class SimEngine(Engine):
         self.gemm([dict(segs=[_seg(_p(b["SE"]), M, w("_predictor.3.weight"), M, M)], m=R, n=L, c=_p(b["SPR"]), ldc=L,
                         bias=w("_predictor.3.bias"))])
         _lib.check(lib.tdmpc_sim_cos_fwd(_p(b["SPR"]), _p(NZ), _p(b["sim"]), R, L, st), "tdmpc_sim_cos_fwd")
+
+    def _loss(self, b, rew, weights, B):
+        """The similarity head, the loss composition and their backward -> b["lrows"], b["scal"], b["dq"], and the
+        queries' gradient in b["dZP"][B L:]."""
+        cfg, H, Q, dq = self.cfg, self.H, b["Q"], b["dq"]
+        st, lib = self._stream(), self.lib
+        self._sim_fwd(b, B)
         la = _lib.SimLossArgs(_p(b["sim"]), _p(Q[0]), _p(Q[1]), _p(Q[2]), rew, _p(b["TD"]), _p(weights), H, B,
                               float(cfg.similarity_coef), float(cfg.reward_coef), float(cfg.value_coef),
                               float(cfg.rho))
         _lib.check(lib.tdmpc_sim_loss_forward(C.byref(la), _p(b["lrows"]), _p(b["scal"]), st), "tdmpc_sim_loss_forward")
         _lib.check(lib.tdmpc_sim_loss_backward(C.byref(la), _p(b["lrows"]), _p(b["scal"]), _p(self.one), _p(b["dsim"]),
                                                _p(dq[0]), _p(dq[1]), _p(dq[2]), st), "tdmpc_sim_loss_backward")
+        self._sim_bwd(b, B)
+
+    def _sim_bwd(self, b, B):
+        """b["dsim"] [H B] back through the cosine and `_predictor` -> the queries' gradient in b["dZP"][B L:]."""
+        H, L, M = self.H, self.L, self.M
+        R = H * B
+        w, st, lib = self.w, self._stream(), self.lib
+        NZ = b["NZ"]
         _lib.check(lib.tdmpc_sim_cos_bwd(_p(b["SPR"]), _p(NZ), _p(b["dsim"]), _p(b["dSPR"]), R, L, st),
                    "tdmpc_sim_cos_bwd")
         self.gemm([dict(segs=[_seg(_p(b["dSPR"]), L, w("_predictor.3.weight"), M, L, bmode=1)], m=R, n=M,

@@ -10,7 +10,8 @@ fixed batch:
               the two sides' losses are compared bitwise before timing.
   update:     `DssmLearner.update` on the HIP path, eagerly launched and as graph replay, against the same class built
               with TDMPC_DSSM_LEARNER_HIP=0 (the reference's order of operations on PyTorch-ROCm, eagerly launched and
-              as graph replay). The parent commit has no update to compare with.
+              as graph replay), and against `dssm_engine.DssmEngineLearner`, the same update on the explicit learner
+              engine, eagerly launched and as graph replay, all six legs in the same run.
 Per leg and side: a warm-up, then `reps` timed batches of `calls` calls between HIP events, the sides alternating batch
 by batch; the median is the figure, min / max the spread. No GPU: it fails.
 """
@@ -117,6 +118,20 @@ def learner(cfg, hip, graph):
     return ln, update
 
 
+def engine_learner(cfg, graph):
+    from tdmpc_amd.dssm_engine import DssmEngineLearner
+    model, target = models(cfg)
+    agent = SimpleNamespace(cfg=cfg, model=model, model_target=target, device=torch.device("cuda"), planner=None)
+    ln = DssmEngineLearner(agent, graph=graph, warmup=3)
+    buf = FixedBatch(cfg)
+    count = [0]
+
+    def update():
+        count[0] += 1
+        return ln.update(buf, 100000 + count[0])
+    return ln, update
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join("profiles", "r09", "drnn_update_bench.json"))
@@ -170,10 +185,16 @@ def main():
     for name, hip, graph in (("hip_eager", True, False), ("hip_graph", True, True), ("torch_eager", False, False),
                              ("torch_graph", False, True)):
         learners[name], sides[name] = learner(cfg, hip, graph)
+    for name, graph in (("engine_eager", False), ("engine_graph", True)):
+        learners[name], sides[name] = engine_learner(cfg, graph)
     res = alternate(sides, args.reps, args.calls)
-    for name in ("hip_graph", "torch_graph"):
+    for name in ("hip_graph", "torch_graph", "engine_graph"):
         assert learners[name]._graphs, f"{name}: never replayed a captured graph"
     out["update"] = {**res,
+                     "hip_graph_over_engine_graph": round(res["hip_graph"]["us_median"] /
+                                                          res["engine_graph"]["us_median"], 3),
+                     "hip_eager_over_engine_eager": round(res["hip_eager"]["us_median"] /
+                                                          res["engine_eager"]["us_median"], 3),
                      "torch_eager_over_hip_eager": round(res["torch_eager"]["us_median"] /
                                                          res["hip_eager"]["us_median"], 3),
                      "torch_graph_over_hip_graph": round(res["torch_graph"]["us_median"] /
